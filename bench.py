@@ -1,8 +1,15 @@
 #!/usr/bin/env python
 """Benchmark of the DAAM heat-map extraction path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the one JSON line (``value`` = maps/s, ``ms_per_step`` = ms per
+timed generation); ``--dump-outputs DIR`` also writes the global heat map of the last timed generation (rank 0's) as
+``DIR/global_heat_map.npy``, float32 ``[77, 64, 64]`` (the inputs are seeded: the same arguments give the same inputs; the
+finalize accumulates the mean with atomics, so two runs of one build may differ by a few float32 ulps).
+Everything else below -- the sustained-state leg, the other configurations, rooflines, counters, baselines, the full
+record -- runs only with ``--full``.
 
 One bench "step" = the extraction work of ONE generation (one prompt/seed) of the workload:
 reset of the running sums, ``denoise_steps`` x (all hooked cross-attention layers) taps from
@@ -22,11 +29,11 @@ all_gather of the final maps, inside the timed region.  ``scaling`` = weak.
 ``python bench.py --gpus N`` outside a launcher re-executes itself under ``torch.distributed.run`` with N ranks (one per
 GPU); it never reports ``n_gpus`` other than the N it was asked for.
 
-The default run also times short legs of the other single-GPU BASELINE configurations (``other_configs``: SD-v1.5 50 steps,
+The ``--full`` run also times short legs of the other single-GPU BASELINE configurations (``other_configs``: SD-v1.5 50 steps,
 SDXL 2048 x 2048 100 steps).  ``--gpus N --dist-backend gloo --shared-device`` runs the whole multi-rank path on a one-GPU box.
 Progress goes to stderr; stdout carries the one JSON line.
 
-The one JSON line also carries ``roofline`` (tap kernel: algorithmic bytes / HIP-event time of the launch
+The one JSON line of a ``--full`` run also carries ``roofline`` (tap kernel: algorithmic bytes / HIP-event time of the launch
 as it occurs in the timed region), ``roofline_issue`` (the same launch against its instruction-issue floor: VALU busy
 cycles from the committed PMC pass of this build + the MFMA issue cost, at the shader clock sampled IN this run while
 the kernel executes), ``roofline_finalize`` / ``roofline_finalize_issue``, ``integrated`` (extraction overhead per
@@ -682,10 +689,11 @@ class Comm:
         self.dist.destroy_process_group()
 
 
-def run_workload(name, denoise_steps, gens, warmup, device, args, comm=None, rank=0, world=1, detail=True):
+def run_workload(name, denoise_steps, gens, warmup, device, args, comm=None, rank=0, world=1, detail=True, full=True):
     """Warm up, time ``gens`` generations of workload ``name`` on this rank (+ the gather of the final maps when there are
-    several ranks) between barriers, then -- rank 0, ``detail`` -- the per-kernel measurements.  Returns the pieces of the
-    JSON line (rank 0) or None."""
+    several ranks) between barriers, then -- rank 0, ``full`` -- the sustained-state leg and the per-kernel measurements.
+    Returns the pieces of the JSON line (rank 0; ``last_map``: the global heat map of the last timed generation, on the host)
+    or None."""
     from daam_amd.engine import HeatMapEngine
     wl = WORKLOADS[name]
     note(f'{name}: inputs')
@@ -738,6 +746,7 @@ def run_workload(name, denoise_steps, gens, warmup, device, args, comm=None, ran
         comm.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    last_map = results[-1].float().cpu().numpy()                 # what the caller of the last timed generation received
     launches_per_gen = (eng.last_flush()['launches'] - launches0) / gens     # what the engine really launched
     flush = eng.last_flush()
     ran_tap, ran_fin = eng.last_kernels(0), eng.last_kernels(1)
@@ -751,7 +760,7 @@ def run_workload(name, denoise_steps, gens, warmup, device, args, comm=None, ran
     region_tap = history(0, int(round(launches_per_gen * gens)))
     region_fin = history(1, gens)
     sustained = None
-    if detail and not comm and args.defer > 0 and not getattr(args, 'no_sustained', False):
+    if full and detail and not comm and args.defer > 0 and not getattr(args, 'no_sustained', False):
         # The driver's timed region is a few dozen milliseconds; the board needs ~0.8 s of back-to-back launches to settle at its power
         # cap (profiles/r04_power_sclk.txt).  Beside it: >= 2 s of the same generations, the launches timed by the same event ring
         # (its last <= 256 launches = the settled state).
@@ -792,12 +801,17 @@ def run_workload(name, denoise_steps, gens, warmup, device, args, comm=None, ran
     acc_bytes = 2 if accumulate == 'exact' else 4
     out = dict(label=wl['label'], elapsed=elapsed, gens=gens, denoise_steps=denoise_steps, accumulate=accumulate,
                value=world * gens / elapsed, ms_per_step=elapsed / gens * 1e3, keys=sum(h for _, h, _, _ in layers), sustained=sustained,
-               warmup_effective=warmup_effective)
+               warmup_effective=warmup_effective, last_map=last_map)
     # steps one tap launch covers: the step window, or fewer when the recorded Q / K reach the engine's
     # byte budget (a launch is then forced at the next step boundary)
     step_bytes = sum(q.numel() * q.element_size() + k.numel() * k.element_size() for q, k in sets[0])
     spl = max(1, min(args.defer, denoise_steps, 64, -(-eng.defer_bytes // step_bytes)))
     out['steps_per_launch'] = spl
+    if not full:
+        eng.close()
+        del sets, calls
+        torch.cuda.empty_cache()
+        return out
     if args.defer > 0:
         expect = -(-denoise_steps // spl)
         if round(launches_per_gen) != expect:
@@ -964,10 +978,12 @@ def headline_line(full: dict) -> str:
                         'scaling', 'vs_baseline', 'dtype', 'data'))
     line['config'] = _pick(full.get('config'), ('workload', 'accumulate', 'defer_steps', 'parallelism', 'generations_per_rank', 'baseline_config',
                                                 'collective', 'collective_world_size', 'collective_library'))
-    line['roofline'] = _pick(full.get('roofline'), ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'bytes_per_launch', 'ms_per_launch',
-                                                    'traffic', 'traffic_over_algorithmic', 'traffic_measured_in_run', 'steps_per_launch',
-                                                    'launches_per_generation', 'sustained_frac'))
-    line['roofline'].setdefault('traffic', None)
+    line['roofline'] = None
+    if full.get('roofline'):                                     # (a run without --full measures no roofline)
+        line['roofline'] = _pick(full['roofline'], ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'bytes_per_launch', 'ms_per_launch',
+                                                     'traffic', 'traffic_over_algorithmic', 'traffic_measured_in_run', 'steps_per_launch',
+                                                     'launches_per_generation', 'sustained_frac'))
+        line['roofline'].setdefault('traffic', None)
     cpu = full.get('cpu_baseline')
     line['cpu_baseline'] = _pick(cpu, ('value', 'unit', 'cores', 'kind', 'cpu', 'sample')) if cpu else None
     # one scalar per extra measurement, most important first (dropped from the END if the line would not fit)
@@ -1036,6 +1052,15 @@ def write_full_record(full: dict):
         return None
 
 
+def dump_outputs(d, **arrays):
+    """``--dump-outputs``: each array as ``d/<name>.npy`` in float32 (what two builds of the project are compared by)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f'{name}.npy'), np.ascontiguousarray(a, dtype=np.float32))
+    note(f'outputs written to {d}: ' + ', '.join(f'{n}{list(a.shape)}' for n, a in arrays.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -1053,6 +1078,12 @@ def main():
                          'generation re-reads data an earlier one left in L2 / Infinity Cache; SDXL-2048: 25 sets = 39 GB)')
     ap.add_argument('--arena', action='store_true',
                     help='experiment: carve every synthetic Q / K out of ONE allocation (see make_inputs); never the reported configuration')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline figure, measure everything else: per-kernel rooflines and the in-run HBM traffic, the '
+                         'sustained-state leg, the other configurations and dtype legs, the integrated overhead, the CPU / eager-GPU '
+                         'baselines; writes the full record (the --no-* options below leave parts of this out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (rank 0\'s global heat map) as DIR/<name>.npy')
     ap.add_argument('--no-baselines', action='store_true', help='skip the CPU / eager-GPU reference timings')
     ap.add_argument('--no-integrated', action='store_true', help='skip the integrated-overhead leg')
     ap.add_argument('--no-pmc', action='store_true', help='skip the in-run HBM-traffic measurement (two short children under rocprofv3 --pmc)')
@@ -1086,67 +1117,71 @@ def main():
     comm = Comm(args.dist_backend, device, expect_world=args.gpus) if world > 1 else None
 
     denoise = args.denoise_steps or WORKLOADS[args.workload].get('denoise_steps', 50)
-    main_rec = run_workload(args.workload, denoise, args.steps, args.warmup, device, args, comm=comm, rank=rank, world=world)
+    main_rec = run_workload(args.workload, denoise, args.steps, args.warmup, device, args, comm=comm, rank=rank, world=world,
+                            full=args.full)
 
     out = None
     if rank == 0:
         r = main_rec
-        if world == 1 and not args.no_pmc:
-            note('HBM traffic + issue counters: children under rocprofv3 --pmc')
-            apply_counters(r, *measure_traffic(args, args.workload, denoise, r['roofline']['launches_per_generation']))
-        gpu_ms_per_gen = r['tap_ms_per_generation'] + r['fin_ms']
-        extra = dict(
-            extraction_overhead_ms_per_denoise_step=round(r['ms_per_step'] / denoise, 4),
-            gpu_ms_per_denoise_step=round(r['tap_ms_per_generation'] / denoise, 4),
-            gpu_bound_maps_per_s=round(1e3 / gpu_ms_per_gen, 1),
-            host_enqueue_ms_per_generation=round(r['host_ms'], 3),
-            raw_maps_per_s=round(world * args.steps * denoise * r['keys'] / r['elapsed'], 1),
-            roofline_finalize=r['roofline_finalize'], roofline_issue=r['roofline_issue'],
-            roofline_finalize_issue=r['roofline_finalize_issue'],
-        )
-        if world == 1 and not args.no_other_configs and args.workload == 'sdxl1024':
-            # the other single-GPU configurations of BASELINE.json, short legs (their parity: tests/test_gpu_integration.py)
-            others = {}
-            # (SD-v1.5: 100 generations = 45 ms, the length of the headline's region -- 20 generations are 9 ms, over before the board has
-            # left its idle clocks: the launches of so short a region read 10 % longer than the same launches a few milliseconds later)
-            legs = [('sd15', 100, 10), ('sdxl2048', 5, 2)]
-            if not args.no_dtype_legs:
-                legs += [('sdxl1024_bf16', 20, 5), ('sdxl1024_f32acc', 20, 5)]
-            for name, g, wu in legs:
-                ds = WORKLOADS[name].get('denoise_steps', 50)
-                o = run_workload(name, ds, g, wu, device, args, detail=False)
-                if not args.no_pmc:
-                    note(f'{name}: HBM traffic + issue counters under rocprofv3 --pmc')
-                    apply_counters(o, *measure_traffic(args, name, ds, o['roofline']['launches_per_generation'], sq=name in ('sd15', 'sdxl2048')))
-                dt = {'bfloat16': 'bf16'}.get(WORKLOADS[name].get('dtype'), 'fp16')
-                others[name] = dict(config=f'{o["label"]}, {ds} denoising steps, 77 tokens, CFG batch 2, {dt} Q/K, accumulate={o["accumulate"]}',
-                                    value=round(o['value'], 2), unit='maps/s', generations=g, warmup=wu,
-                                    ms_per_step=round(o['ms_per_step'], 3),
-                                    gpu_bound_maps_per_s=round(1e3 / (o['tap_ms_per_generation'] + o['fin_ms']), 1),
-                                    roofline=o['roofline'], roofline_issue=o['roofline_issue'],
-                                    roofline_finalize=o['roofline_finalize'], roofline_finalize_issue=o['roofline_finalize_issue'])
-            # the dtype legs against the headline: tap launch time relative to the fp16 / fp16-sums launch of THIS run
-            for name in ('sdxl1024_bf16', 'sdxl1024_f32acc'):
-                if name in others:
-                    others[name]['tap_ms_over_fp16_headline'] = round(others[name]['roofline']['ms_per_launch'] / r['roofline']['ms_per_launch'], 4)
-            extra['other_configs'] = others
-        if not args.no_integrated and world == 1 and args.workload == 'sdxl1024':
-            note('integrated overhead')
-            extra['integrated'] = integrated_overhead(device)
-            note('attend bench')
-            # the processor's attention on daam_attend (tools/attend_bench.py): per denoising step of 60 layer calls, next
-            # to torch's fused SDPA, and the cost of the in-kernel tap of an immediate (defer_steps=0) trace
-            from tools.attend_bench import measure as attend_measure
-            extra['attend'] = attend_measure(steps=20, reps=3, dev=device)
-        cpu = None
-        if not args.no_baselines and world == 1:
-            wl = WORKLOADS[args.workload]
-            note('cpu baseline + eager reference')
-            cpu = cpu_baseline(wl['kind'], wl['latent'], denoise, eager_device=device)
-            ref_gpu = cpu.pop('eager_mi355x')
-            extra['reference_eager_mi355x'] = {k: round(v, 4) for k, v in ref_gpu.items()}
-            extra['speedup_vs_eager_mi355x'] = round(r['value'] / ref_gpu['maps_per_s'], 1)
-            cpu = {k: (round(v, 6) if isinstance(v, float) else v) for k, v in cpu.items()}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, global_heat_map=r.pop('last_map'))
+        extra, cpu = {}, None
+        if args.full:
+            if world == 1 and not args.no_pmc:
+                note('HBM traffic + issue counters: children under rocprofv3 --pmc')
+                apply_counters(r, *measure_traffic(args, args.workload, denoise, r['roofline']['launches_per_generation']))
+            gpu_ms_per_gen = r['tap_ms_per_generation'] + r['fin_ms']
+            extra = dict(
+                extraction_overhead_ms_per_denoise_step=round(r['ms_per_step'] / denoise, 4),
+                gpu_ms_per_denoise_step=round(r['tap_ms_per_generation'] / denoise, 4),
+                gpu_bound_maps_per_s=round(1e3 / gpu_ms_per_gen, 1),
+                host_enqueue_ms_per_generation=round(r['host_ms'], 3),
+                raw_maps_per_s=round(world * args.steps * denoise * r['keys'] / r['elapsed'], 1),
+                roofline_finalize=r['roofline_finalize'], roofline_issue=r['roofline_issue'],
+                roofline_finalize_issue=r['roofline_finalize_issue'],
+            )
+            if world == 1 and not args.no_other_configs and args.workload == 'sdxl1024':
+                # the other single-GPU configurations of BASELINE.json, short legs (their parity: tests/test_gpu_integration.py)
+                others = {}
+                # (SD-v1.5: 100 generations = 45 ms, the length of the headline's region -- 20 generations are 9 ms, over before the board has
+                # left its idle clocks: the launches of so short a region read 10 % longer than the same launches a few milliseconds later)
+                legs = [('sd15', 100, 10), ('sdxl2048', 5, 2)]
+                if not args.no_dtype_legs:
+                    legs += [('sdxl1024_bf16', 20, 5), ('sdxl1024_f32acc', 20, 5)]
+                for name, g, wu in legs:
+                    ds = WORKLOADS[name].get('denoise_steps', 50)
+                    o = run_workload(name, ds, g, wu, device, args, detail=False)
+                    if not args.no_pmc:
+                        note(f'{name}: HBM traffic + issue counters under rocprofv3 --pmc')
+                        apply_counters(o, *measure_traffic(args, name, ds, o['roofline']['launches_per_generation'], sq=name in ('sd15', 'sdxl2048')))
+                    dt = {'bfloat16': 'bf16'}.get(WORKLOADS[name].get('dtype'), 'fp16')
+                    others[name] = dict(config=f'{o["label"]}, {ds} denoising steps, 77 tokens, CFG batch 2, {dt} Q/K, accumulate={o["accumulate"]}',
+                                        value=round(o['value'], 2), unit='maps/s', generations=g, warmup=wu,
+                                        ms_per_step=round(o['ms_per_step'], 3),
+                                        gpu_bound_maps_per_s=round(1e3 / (o['tap_ms_per_generation'] + o['fin_ms']), 1),
+                                        roofline=o['roofline'], roofline_issue=o['roofline_issue'],
+                                        roofline_finalize=o['roofline_finalize'], roofline_finalize_issue=o['roofline_finalize_issue'])
+                # the dtype legs against the headline: tap launch time relative to the fp16 / fp16-sums launch of THIS run
+                for name in ('sdxl1024_bf16', 'sdxl1024_f32acc'):
+                    if name in others:
+                        others[name]['tap_ms_over_fp16_headline'] = round(others[name]['roofline']['ms_per_launch'] / r['roofline']['ms_per_launch'], 4)
+                extra['other_configs'] = others
+            if not args.no_integrated and world == 1 and args.workload == 'sdxl1024':
+                note('integrated overhead')
+                extra['integrated'] = integrated_overhead(device)
+                note('attend bench')
+                # the processor's attention on daam_attend (tools/attend_bench.py): per denoising step of 60 layer calls, next
+                # to torch's fused SDPA, and the cost of the in-kernel tap of an immediate (defer_steps=0) trace
+                from tools.attend_bench import measure as attend_measure
+                extra['attend'] = attend_measure(steps=20, reps=3, dev=device)
+            if not args.no_baselines and world == 1:
+                wl = WORKLOADS[args.workload]
+                note('cpu baseline + eager reference')
+                cpu = cpu_baseline(wl['kind'], wl['latent'], denoise, eager_device=device)
+                ref_gpu = cpu.pop('eager_mi355x')
+                extra['reference_eager_mi355x'] = {k: round(v, 4) for k, v in ref_gpu.items()}
+                extra['speedup_vs_eager_mi355x'] = round(r['value'] / ref_gpu['maps_per_s'], 1)
+                cpu = {k: (round(v, 6) if isinstance(v, float) else v) for k, v in cpu.items()}
         out = {
             'metric': 'heat maps/sec, DAAM extraction (tap + compute_global_heat_map), ' + r['label'] +
                       f', {denoise}-step, 77-tok',
@@ -1166,7 +1201,7 @@ def main():
                                                                                         'scaling measurement)' if args.shared_device else ''),
                        'collective_world_size': comm.world if comm else 1,
                        'collective_library': comm.library() if comm else None},
-            'roofline': r['roofline'], 'cpu_baseline': cpu,
+            'roofline': r.get('roofline'), 'cpu_baseline': cpu,
         }
         if r.get('sustained'):
             su = r['sustained']
@@ -1182,7 +1217,8 @@ def main():
         comm.close()
     if rank == 0:
         out = _finite(out)
-        out['full_record'] = write_full_record(out)
+        if args.full:
+            out['full_record'] = write_full_record(out)
         note('done')
         print(headline_line(out), flush=True)
 

@@ -88,3 +88,17 @@ def test_multi_rank_line():
 def test_finite():
     assert bench._finite({'a': [1.0, float('nan'), {'b': float('-inf')}], 'c': 'x'}) == {'a': [1.0, None, {'b': None}], 'c': 'x'}
     assert math.isfinite(bench._finite(2.5))
+
+
+def test_plain_run_line():
+    """A run without --full measures the headline figure only: no roofline, no baseline, no extra scalars -- the contract's
+    fields are all there."""
+    full = json.load(open(RECORDS[-1]))
+    plain = {k: full[k] for k in CONTRACT if k not in ('roofline', 'cpu_baseline')}
+    plain.update(roofline=None, cpu_baseline=None, warmup_effective=full.get('warmup_effective', 20))
+    got = _strict(bench.headline_line(bench._finite(plain)))
+    for k in CONTRACT:
+        assert k in got, k
+    assert got['roofline'] is None and got['cpu_baseline'] is None and 'full_record' not in got
+    assert got['value'] == full['value'] and got['ms_per_step'] == full['ms_per_step']
+    assert set(got) == set(CONTRACT) | {'warmup_effective'}

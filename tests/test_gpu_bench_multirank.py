@@ -13,7 +13,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ['--steps', '3', '--warmup', '1', '--no-baselines', '--no-integrated', '--no-other-configs']
+COMMON = ['--steps', '3', '--warmup', '1', '--full', '--no-baselines', '--no-integrated', '--no-other-configs']
 
 
 def _bench(*extra, timeout=600, **env_extra):
@@ -129,3 +129,26 @@ def test_bench_refuses_more_gpus_than_visible():
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *COMMON, '--gpus', str(n)], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode != 0 and 'refusing' in (p.stderr + p.stdout)
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """The form every change is measured with -- no ``--full``: the headline figure only (no roofline, no sustained leg, no full
+    record) -- and ``--dump-outputs`` writing the global heat map of the last timed generation."""
+    import numpy as np
+    full_path = tmp_path / 'bench_full.json'
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', BENCH_FULL_RECORD=str(full_path))
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path / 'out')], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec['n_gpus'] == 1 and rec['steps'] == 3 and rec['warmup'] == 1 and rec['unit'] == 'maps/s' and rec['dtype'] == 'f16'
+    assert rec['metric'].startswith('heat maps/sec') and rec['higher_is_better'] is True
+    assert rec['value'] > 0 and abs(rec['value'] * rec['ms_per_step'] / 1e3 - 1.0) < 0.01, rec
+    assert rec['roofline'] is None and rec['cpu_baseline'] is None and 'sustained_maps_per_s' not in rec
+    assert 'full_record' not in rec and not full_path.exists()
+    m = np.load(tmp_path / 'out' / 'global_heat_map.npy')
+    assert m.dtype == np.float32 and m.shape == (77, 64, 64)
+    assert np.isfinite(m).all() and 0.0 <= m.min() and m.max() > 0.0

@@ -5,7 +5,7 @@ set -u
 R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/gen_gaps; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python $R/bench.py --no-baselines --no-integrated --no-pmc --no-other-configs --steps 30 --warmup 5 > $O/bench.json 2> $O/bench.log
+rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python $R/bench.py --full --no-baselines --no-integrated --no-pmc --no-other-configs --steps 30 --warmup 5 > $O/bench.json 2> $O/bench.log
 python - $O <<'PY'
 import csv, glob, json, sys
 O = sys.argv[1]

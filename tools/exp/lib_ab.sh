@@ -16,7 +16,7 @@ for i in range(rounds):
             env['DAAM_HIP_LIB'] = lib
         else:
             env.pop('DAAM_HIP_LIB', None)
-        p = subprocess.run([sys.executable, 'bench.py', '--no-baselines', '--no-integrated', '--no-pmc', '--no-other-configs', *extra], env=env,
+        p = subprocess.run([sys.executable, 'bench.py', '--full', '--no-baselines', '--no-integrated', '--no-pmc', '--no-other-configs', *extra], env=env,
                            stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
         r = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
         row = dict(lib=tag, maps_per_s=r['value'], tap_ms=r['roofline']['ms_per_launch'], hbm_frac=r['roofline']['frac'],

@@ -15,7 +15,7 @@ for i in range(rounds):
         env.pop('DAAM_HIP_LIB', None)
         if lib != 'default':
             env['DAAM_HIP_LIB'] = lib
-        p = subprocess.run([sys.executable, 'bench.py', '--no-baselines', '--no-integrated', '--no-pmc', '--no-other-configs', '--steps', '30', '--warmup', '5'], env=env,
+        p = subprocess.run([sys.executable, 'bench.py', '--full', '--no-baselines', '--no-integrated', '--no-pmc', '--no-other-configs', '--steps', '30', '--warmup', '5'], env=env,
                            stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
         r = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
         row = dict(lib=os.path.basename(lib), maps_per_s=r['value'], tap_ms=r['roofline']['ms_per_launch'],

@@ -5,7 +5,7 @@ set -u
 TAG=$1; LIB=${2:-}
 R=$(pwd); O=$R/gpurun_out/tl_$TAG; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 [ -n "$LIB" ] && export DAAM_HIP_LIB=$LIB
-rocprofv3 --kernel-trace --output-format csv -d $O/tr -- python $R/bench.py --no-baselines --no-integrated --no-other-configs --workload sd15 --steps 6 --warmup 2 > $O/log.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/tr -- python $R/bench.py --full --no-baselines --no-integrated --no-other-configs --workload sd15 --steps 6 --warmup 2 > $O/log.txt 2>&1
 cd $R
 python - $O <<'PY'
 import sys, glob, csv, collections

@@ -24,16 +24,16 @@ fi
 done
 # the bench lines read the counters measured minutes ago on this box (bench.py takes profiles/<tag>_counters.json when the kernels match)
 [ -f gpurun_out/profiles_$TAG/${TAG}_counters.json ] && cp gpurun_out/profiles_$TAG/${TAG}_counters.json profiles/
-timeout 600 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.log"; cp gpurun_out/bench_full.json "$out/bench_default_full.json"
+BENCH_FULL_RECORD="$out/bench_default_full.json" timeout 600 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.log"
 say "bench default: $(python -c "import json;r=json.loads([l for l in open('$out/bench_default.json') if l.startswith('{')][0]);print(r['value'], r['roofline']['ms_per_launch'], r['roofline']['frac'], r['roofline'].get('traffic_over_algorithmic'), r.get('finalize_ms'), r['cpu_baseline']['value'])")"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > "$out/bench_driver_form.json" 2> "$out/bench_driver_form.log"; cp gpurun_out/bench_full.json "$out/bench_driver_form_full.json"
+BENCH_FULL_RECORD="$out/bench_driver_form_full.json" timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out/bench_driver_form.json" 2> "$out/bench_driver_form.log"
 say "bench driver form: $(python -c "import json;r=json.loads([l for l in open('$out/bench_driver_form.json') if l.startswith('{')][0]);print(r['value'], r['roofline']['ms_per_launch'], r['roofline']['frac'])")"
 # power / clock while the tap launches run back to back: every byte from HBM (one step set per step) and a pool of 12 (re-used from the Infinity Cache)
 [ "${SKIP_POWER:-0}" = 1 ] || for pool in 0 12; do
   O=$out/power_pool$pool; mkdir -p $O
   sample() { rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power|sclk" | sed -E 's/^GPU\[0\][[:space:]]*:[[:space:]]*//' | tr '\n' ';'; echo; }
-  echo "# python bench.py --no-baselines --no-integrated --no-other-configs --no-pmc --no-sustained --steps 3000 --warmup 10 --pool $pool   (pool 0 = one distinct step set per denoising step)" > $O/power_sclk.txt
-  python bench.py --no-baselines --no-integrated --no-other-configs --no-pmc --no-sustained --steps 3000 --warmup 10 --pool $pool > $O/bench.json 2> /dev/null &
+  echo "# python bench.py --full --no-baselines --no-integrated --no-other-configs --no-pmc --no-sustained --steps 3000 --warmup 10 --pool $pool   (pool 0 = one distinct step set per denoising step)" > $O/power_sclk.txt
+  python bench.py --full --no-baselines --no-integrated --no-other-configs --no-pmc --no-sustained --steps 3000 --warmup 10 --pool $pool > $O/bench.json 2> /dev/null &
   BP=$!
   while kill -0 $BP 2>/dev/null; do echo "$(date +%s.%N) $(sample)" >> $O/power_sclk.txt; sleep 0.3; done
   python -c "
