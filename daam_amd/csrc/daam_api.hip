@@ -49,6 +49,12 @@ hipError_t launch_finalize_up(const FinLaunch&, int side, int, int mfma_ok, hipS
 bool finalize_up_supported(int side, int out_side);
 bool finalize_down2_supported(int side, int out_side);
 hipError_t launch_finalize_down2(const FinLaunch&, int, hipStream_t, int*);
+hipError_t launch_zero_groups(float* out, size_t stride, int plane, const int* rows, int n_groups, hipStream_t);
+hipError_t launch_finalize_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*, int*);
+hipError_t launch_finalize_same_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
+hipError_t launch_finalize_up_grouped(const FinGroupLaunch&, int n_groups, int side, int acc_dtype, hipStream_t, int*);
+hipError_t launch_finalize_down2_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
+hipError_t launch_finalize_up32_pipe_grouped(const FinPipeGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
 hipError_t launch_normalize(float*, int, int, hipStream_t);
 hipError_t launch_mask_overlap(const float*, int, int, const float*, int, int, int, float*, hipStream_t);
 bool attend_d64_supported(int in_dtype, int head_dim, int tokens, const int64_t* strides, int n_strides, const void* const* ptrs, int n_ptrs);
@@ -1280,6 +1286,7 @@ namespace {
 constexpr int kFinClasses = 5;       // 0 = same size (clamp + mean), 1 = x2 (32 -> 64), 2 = x4 (16 -> 64), 3 = general kernel, 4 = x0.5 (128 -> 64)
 struct FinPlan {
     std::vector<FinKey> keys[kFinClasses];
+    std::vector<int> pos[kFinClasses];  // layer-major index of every key (daam_finalize_groups: its group)
     int total = 0, max_side = 0;
     bool mfma_up = false, pipe_up = false, fold_same = false;
     int pipe_chunks = 0, pipe_nk = 0, pipe_stride = 0, same_per = 0;
@@ -1318,6 +1325,7 @@ static int fin_plan(DaamCtx* c, const uint8_t* key_mask, int rows, FinPlan& P)
             }
             if (cls == 3 && l.tab >= 0) P.max_side = std::max(P.max_side, l.side);
             keys[cls].push_back(k);
+            P.pos[cls].push_back(pos);
             ++P.total;
         }
     }
@@ -1646,6 +1654,266 @@ int daam_finalize(DaamCtx* c, const uint8_t* key_mask, int n_rows, float* out, v
             for (int i = 0; i < n_side; ++i) (void)hipStreamWaitEvent(s, c->aux_join[i], 0);
             release_tab();                                 // the table region is reusable once whatever did launch has run
             return fail((int)e, "finalize launch (class %d): %s", cls, hipGetErrorString(e));
+        }
+        c->last_grid[1] += grid;
+        c->last_lds[1] = std::max(c->last_lds[1], lds);
+    }
+    for (int i = 0; i < n_side; ++i)
+        if (hipStreamWaitEvent(s, c->aux_join[i], 0) != hipSuccess) { release_tab(); return fail(DAAM_E_STATE, "stream join failed"); }
+    c->last_fin_side = n_side;
+    c->last_kernels[1] = launched_names;
+    if (c->profile) { (void)hipEventRecord(c->prof_event(1, 1), s); ++c->hist_count[1]; }
+    release_tab();
+    return 0;
+}
+
+// daam_finalize_groups: N global heat maps, one launch per class.  The keys of every class are laid out group by group (a
+// group's keys are contiguous in the FinKey array and in the pointer tables of the pipelined x2 kernel, so no chunk straddles
+// two groups); the per-group part of a launch (key range, rows, 1/N, output base, pointer-table offsets) travels in the kernel
+// arguments and blockIdx.z selects it.
+int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, const int32_t* n_rows, float* out,
+                         size_t group_stride, void* stream)
+{
+    if (!c || !out || !key_group || !n_rows) return fail(DAAM_E_INVALID, "NULL argument");
+    if (n_groups < 1 || n_groups > kFinMaxGroups) return fail(DAAM_E_INVALID, "n_groups %d not in 1..%d", n_groups, kFinMaxGroups);
+    if (!c->pending.empty()) return fail(DAAM_E_STATE, "finalize with deferred taps pending: flush first");
+    int total_keys = 0;
+    daam_key_offset(c, 0, nullptr, &total_keys);
+    std::vector<int> rows(n_groups);
+    for (int g = 0; g < n_groups; ++g) rows[g] = fin_rows(c, n_rows[g]);
+    const size_t plane = (size_t)c->out_side * c->out_side;
+    for (int g = 0; g + 1 < n_groups; ++g)
+        if (group_stride < (size_t)rows[g] * plane)
+            return fail(DAAM_E_INVALID, "group_stride %zu < %d rows of %zu floats: groups would overlap", group_stride, rows[g], plane);
+    std::vector<uint8_t> mask(total_keys > 0 ? total_keys : 1);
+    std::vector<int> n_of(n_groups, 0);
+    for (int i = 0; i < total_keys; ++i) {
+        const int g = key_group[i];
+        if (g < -1 || g >= n_groups) return fail(DAAM_E_INVALID, "key_group[%d] = %d not in -1..%d", i, g, n_groups - 1);
+        mask[i] = g >= 0;
+        if (g >= 0) ++n_of[g];
+    }
+    for (int g = 0; g < n_groups; ++g)
+        if (!n_of[g]) return fail(DAAM_E_NOMAPS, "no heat maps selected for group %d", g);
+    if (n_groups == 1) return daam_finalize(c, mask.data(), n_rows[0], out, stream);
+    DeviceGuard on_device(c);
+    hipStream_t s = (hipStream_t)stream;
+    c->prep_out = c->fold_out = nullptr;
+    for (auto& l : c->layers)
+        if (l.configured) {
+            int zrc = ensure_zeroed(l, s);
+            if (zrc) return zrc;
+        }
+    FinPlan P;
+    {
+        int prc = fin_plan(c, mask.data(), c->tokens, P);
+        if (prc) return prc;
+    }
+    if (P.mfma_up && !P.pipe_up) {
+        // the round-2 MFMA x2 kernel (DAAM_NO_PIPE_FINALIZE): one daam_finalize per group
+        for (int g = 0; g < n_groups; ++g) {
+            for (int i = 0; i < total_keys; ++i) mask[i] = key_group[i] == g;
+            int rc = daam_finalize(c, mask.data(), n_rows[g], out + (size_t)g * group_stride, stream);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    static const int env_chunks = fin_env("DAAM_FIN_CHUNKS"), env_pipe_chunks = fin_env("DAAM_FIN_PIPE_CHUNKS");
+    static const int env_up_chunks = fin_env("DAAM_FIN_UP_CHUNKS");
+    int max_rows = 0, sum_rows = 0;
+    for (int g = 0; g < n_groups; ++g) { max_rows = std::max(max_rows, rows[g]); sum_rows += rows[g]; }
+    // every class's keys group by group (stable: layer-major order inside a group)
+    std::vector<FinKey> gk[kFinClasses];
+    std::vector<int> begin[kFinClasses], count[kFinClasses];
+    int max_n[kFinClasses] = {0, 0, 0, 0, 0};
+    for (int cls = 0; cls < kFinClasses; ++cls) {
+        begin[cls].assign(n_groups, 0);
+        count[cls].assign(n_groups, 0);
+        for (int g = 0; g < n_groups; ++g) {
+            begin[cls][g] = (int)gk[cls].size();
+            for (size_t j = 0; j < P.keys[cls].size(); ++j)
+                if (key_group[P.pos[cls][j]] == g) gk[cls].push_back(P.keys[cls][j]);
+            count[cls][g] = (int)gk[cls].size() - begin[cls][g];
+            if (!count[cls][g]) begin[cls][g] = 0;             // (a kernel reads keys[0].tab: stay inside the class)
+            max_n[cls] = std::max(max_n[cls], count[cls][g]);
+        }
+    }
+    // pipelined x2 kernel: ~1000 workgroups over the whole launch (every group's rows), one chunk length for every group
+    const bool pipe_up = P.pipe_up, fold_same = P.fold_same;
+    int pipe_chunks = 0, pipe_nk = 0, pipe_stride = 0, pipe_per = 0, same_per = 0;
+    if (pipe_up) {
+        const int want = env_pipe_chunks ? env_pipe_chunks : env_chunks ? env_chunks : std::max(1, (1024 + sum_rows / 2) / sum_rows);
+        pipe_chunks = std::max(1, std::min(want, (max_n[1] + 7) / 8));
+        pipe_per = (max_n[1] + pipe_chunks - 1) / pipe_chunks;
+        pipe_nk = std::max(4, (pipe_per + 1) & ~1);
+        pipe_stride = (pipe_nk + finalize_pipe_ring(c->acc_dtype) + 2) & ~1;
+        same_per = fold_same ? (max_n[0] + pipe_chunks - 1) / pipe_chunks : 0;
+    }
+    const size_t key_bytes = ((size_t)P.total * sizeof(FinKey) + 63) & ~size_t(63);
+    const size_t ptr_per_group = (size_t)pipe_chunks * pipe_stride, same_per_group = (size_t)pipe_chunks * same_per;
+    const size_t ptr_bytes = ptr_per_group * n_groups * sizeof(unsigned long long);
+    std::vector<char> tab(key_bytes + ptr_bytes + same_per_group * n_groups * sizeof(unsigned long long), 0);
+    {
+        FinKey* dst = reinterpret_cast<FinKey*>(tab.data());
+        for (auto& v : gk) {
+            if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(FinKey));
+            dst += v.size();
+        }
+    }
+    if (pipe_up) {
+        unsigned long long* pt = reinterpret_cast<unsigned long long*>(tab.data() + key_bytes);
+        unsigned long long* st = pt + ptr_per_group * n_groups;
+        const unsigned long long zero = reinterpret_cast<unsigned long long>(c->d_zero_planes);
+        for (int g = 0; g < n_groups; ++g) {
+            const FinKey* k1 = gk[1].data() + begin[1][g];
+            const FinKey* k0 = gk[0].data() + begin[0][g];
+            for (int ch = 0; ch < pipe_chunks; ++ch) {
+                for (int j = 0; j < pipe_stride; ++j) {
+                    const int k = ch * pipe_per + j;
+                    pt[g * ptr_per_group + (size_t)ch * pipe_stride + j] =
+                        (j < pipe_per && k < count[1][g]) ? reinterpret_cast<unsigned long long>(k1[k].base) : zero;
+                }
+                for (int j = 0; j < same_per; ++j) {
+                    const int k = ch * same_per + j;
+                    st[g * same_per_group + (size_t)ch * same_per + j] =
+                        k < count[0][g] ? reinterpret_cast<unsigned long long>(k0[k].base) : 0ull;
+                }
+            }
+        }
+    }
+    P.tab.swap(tab);
+    // the output is accumulated with atomics: rows [0, rows[g]) of every group are cleared first
+    if (c->profile) (void)hipEventRecord(c->prof_event(1, 0), s);
+    const char* tab_dev = nullptr;
+    bool ring_held = false;
+    if (fin_cache_hit(c, P, s)) {
+        tab_dev = c->d_fin_tab;
+    } else if (fin_cacheable(c, P, s)) {
+        int rc = fin_cache_upload(c, P, s, nullptr, 0);
+        if (rc) return rc;
+        tab_dev = c->d_fin_tab;
+    } else {
+        size_t off = 0;
+        HIP_TRY(c->ring.alloc(P.tab.size(), &off));
+        memcpy(c->ring.host + off, P.tab.data(), P.tab.size());
+        hipError_t ce = c->ring.commit(off, P.tab.size(), s, nullptr, 0);
+        if (ce != hipSuccess) {
+            (void)c->ring.release(s);
+            return fail((int)ce, "table upload: %s", hipGetErrorString(ce));
+        }
+        tab_dev = c->ring.dev + off;
+        ring_held = true;
+    }
+    auto release_tab = [&]() { if (ring_held) (void)c->ring.release(s); ring_held = false; };
+    {
+        hipError_t ze = launch_zero_groups(out, group_stride, (int)plane, rows.data(), n_groups, s);
+        if (ze != hipSuccess) { release_tab(); return fail((int)ze, "output zeroing: %s", hipGetErrorString(ze)); }
+    }
+    FinGroupLaunch GL[kFinClasses];
+    bool have[kFinClasses] = {false, false, false, false, false};
+    const FinKey* dev = reinterpret_cast<const FinKey*>(tab_dev);
+    const int want_up = env_up_chunks ? env_up_chunks : env_chunks ? env_chunks : std::max(1, (1024 + sum_rows / 2) / sum_rows);
+    auto up_chunks = [&](int n) { return std::max(std::max(1, std::min((n + 15) / 16, want_up)), (n + 127) / 128); };
+    for (int cls = 0; cls < kFinClasses; ++cls) {
+        const int n = (int)gk[cls].size();
+        if (n == 0) continue;
+        FinGroupLaunch& G = GL[cls];
+        memset(&G, 0, sizeof G);
+        FinLaunch& L = G.L;
+        L.keys = dev;
+        dev += n;
+        L.tab_idx = c->d_tab_idx;
+        L.tab_w = c->d_tab_w;
+        L.out = out;
+        L.n_keys = max_n[cls];
+        L.tokens = max_rows;
+        L.out_side = c->out_side;
+        L.inv_n = 0.f;
+        L.max_side = P.max_side;
+        L.mfma_ops = nullptr;
+        const int m = max_n[cls];
+        if (cls == 0) L.n_chunks = std::max(1, std::min(m, env_chunks ? env_chunks : std::min(9, std::max(4, m / 32))));
+        else if (cls == 3) L.n_chunks = std::max(1, std::min(m, 32));
+        else L.n_chunks = up_chunks(m);
+        for (int g = 0; g < n_groups; ++g) {
+            FinGroup& q = G.g[g];
+            q.key_begin = begin[cls][g];
+            q.n_keys = count[cls][g];
+            q.rows = rows[g];
+            q.inv_n = 1.0f / (float)n_of[g];
+            q.out_off = (int64_t)((size_t)g * group_stride);
+            q.ptr_off = (int32_t)(g * ptr_per_group);
+            q.same_off = (int32_t)(g * same_per_group);
+        }
+        have[cls] = true;
+    }
+    if (fold_same) have[0] = false;                            // done inside the pipelined kernel
+    int n_classes = 0;
+    size_t side_bytes = 0;
+    for (int cls = 0; cls < kFinClasses; ++cls) {
+        n_classes += have[cls] ? 1 : 0;
+        if (have[cls] && cls != 1)
+            for (auto& k : gk[cls]) side_bytes += (size_t)c->tokens * k.side * k.side * acc_elem(c->acc_dtype);
+    }
+    bool fork = pipe_up && n_classes > 1 && n_classes <= DaamCtx::kAux + 1 && !c->no_side_stream && side_bytes >= ((size_t)16 << 20);
+    if (fork) {
+        hipError_t ae = ensure_aux(c);
+        if (ae != hipSuccess || hipEventRecord(c->aux_fork, s) != hipSuccess) fork = false;
+    }
+    c->last_block[1] = 256;
+    c->last_grid[1] = 0;
+    c->last_lds[1] = 0;
+    std::string launched_names;
+    auto names = [&](const char* kernel, const std::string& what) {
+        launched_names += (launched_names.empty() ? "" : "+") + std::string(kernel) + "<" + what + ">";
+    };
+    const std::string dt = dtype_name(c->acc_dtype);
+    auto launch_class = [&](int cls, hipStream_t ks, int* grid, int* lds) -> hipError_t {
+        const FinGroupLaunch& G = GL[cls];
+        if (cls == 1 && pipe_up) {
+            FinPipeGroupLaunch PG;
+            memset(&PG, 0, sizeof PG);
+            FinPipeLaunch& PL = PG.L;
+            PL.key_ptrs = reinterpret_cast<const unsigned long long*>(tab_dev + key_bytes);
+            PL.same_ptrs = fold_same ? reinterpret_cast<const unsigned long long*>(tab_dev + key_bytes + ptr_bytes) : nullptr;
+            PL.same_per = same_per;
+            PL.mfma_ops = c->acc_dtype == DAAM_BF16 ? c->d_up32_ops_bf16 : c->d_up32_ops;
+            PL.out = out;
+            PL.n_chunks = pipe_chunks;
+            PL.nk_pad = pipe_nk;
+            PL.ptr_stride = pipe_stride;
+            PL.tokens = max_rows;
+            PL.inv_n = 0.f;
+            memcpy(PG.g, G.g, sizeof PG.g);
+            names("finalize_up32_pipe_grouped_kernel", dt + (fold_same ? " + same-size keys" : ""));
+            return launch_finalize_up32_pipe_grouped(PG, n_groups, c->acc_dtype, ks, grid);
+        }
+        if (cls == 0) { names("finalize_same_grouped_kernel", dt); return launch_finalize_same_grouped(G, n_groups, c->acc_dtype, ks, grid); }
+        if (cls == 3) { names("finalize_grouped_kernel", dt); return launch_finalize_grouped(G, n_groups, c->acc_dtype, ks, grid, lds); }
+        if (cls == 4) { names("finalize_down2_grouped_kernel", dt); return launch_finalize_down2_grouped(G, n_groups, c->acc_dtype, ks, grid); }
+        names(gk[cls][0].side == 32 ? "finalize_up_grouped_kernel<32>" : "finalize_up_grouped_kernel<16>", dt);
+        return launch_finalize_up_grouped(G, n_groups, gk[cls][0].side, c->acc_dtype, ks, grid);
+    };
+    int n_side = 0;
+    const int order[kFinClasses] = {0, 2, 3, 4, 1};
+    for (int oi = 0; oi < kFinClasses; ++oi) {
+        const int cls = order[oi];
+        if (!have[cls]) continue;
+        hipStream_t ks = s;
+        if (fork && cls != 1) {
+            ks = c->aux_stream[n_side];
+            if (hipStreamWaitEvent(ks, c->aux_fork, 0) != hipSuccess) ks = s;
+        }
+        int grid = 0, lds = 0;
+        hipError_t e = launch_class(cls, ks, &grid, &lds);
+        if (e == hipSuccess && ks != s) {
+            e = hipEventRecord(c->aux_join[n_side], ks);
+            ++n_side;
+        }
+        if (e != hipSuccess) {
+            for (int i = 0; i < n_side; ++i) (void)hipStreamWaitEvent(s, c->aux_join[i], 0);
+            release_tab();
+            return fail((int)e, "grouped finalize launch (class %d): %s", cls, hipGetErrorString(e));
         }
         c->last_grid[1] += grid;
         c->last_lds[1] = std::max(c->last_lds[1], lds);

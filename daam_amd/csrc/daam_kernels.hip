@@ -197,49 +197,16 @@ __global__ __launch_bounds__(256) void tap_probs_kernel(const ProbsLaunch L)
 template <typename ACC_T>
 __global__ __launch_bounds__(256) void finalize_kernel(const FinLaunch L)
 {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    const int tok = blockIdx.x;
-    const int chunk = blockIdx.y;
-    const int O = L.out_side;
-    float* outt = reinterpret_cast<float*>(smem_raw);            // [O][O]
-    float* plane = outt + O * O;                                 // [max_side][max_side]
-    float* tmp = plane + L.max_side * L.max_side;                // [max_side][O]
-    const int tid = threadIdx.x;
-    for (int i = tid; i < O * O; i += 256) outt[i] = 0.f;
+#include "daam_fin_kernel_body.inc"
+}
 
-    for (int kidx = chunk; kidx < L.n_keys; kidx += L.n_chunks) {
-        const FinKey key = L.keys[kidx];
-        const int S = key.side;
-        const ACC_T* src = reinterpret_cast<const ACC_T*>(key.base) + (size_t)tok * S * S;
-        if (key.tab < 0) {                                       // same size: copy (+ clamp)
-            for (int i = tid; i < O * O; i += 256) outt[i] += fmaxf(ld<ACC_T>(src + i), 0.f);
-            continue;
-        }
-        const int16_t* tix = L.tab_idx + (size_t)key.tab * O * 4;
-        const float* tw = L.tab_w + (size_t)key.tab * O * 4;
-        __syncthreads();                                         // previous key done with plane/tmp
-        for (int i = tid; i < S * S; i += 256) plane[i] = ld<ACC_T>(src + i);
-        __syncthreads();
-        for (int i = tid; i < S * O; i += 256) {
-            const int y = i / O, ox = i - y * O;
-            const float* row = plane + y * S;
-            const int16_t* ix = tix + ox * 4;
-            const float* w = tw + ox * 4;
-            tmp[i] = row[ix[0]] * w[0] + row[ix[1]] * w[1] + row[ix[2]] * w[2] + row[ix[3]] * w[3];
-        }
-        __syncthreads();
-        for (int i = tid; i < O * O; i += 256) {
-            const int oy = i / O, ox = i - oy * O;
-            const int16_t* iy = tix + oy * 4;
-            const float* w = tw + oy * 4;
-            const float v = tmp[iy[0] * O + ox] * w[0] + tmp[iy[1] * O + ox] * w[1] +
-                            tmp[iy[2] * O + ox] * w[2] + tmp[iy[3] * O + ox] * w[3];
-            outt[i] += fmaxf(v, 0.f);
-        }
-    }
-    // each thread only ever touched its own outt[i] entries (i = tid mod 256): no barrier needed
-    float* out = L.out + (size_t)tok * O * O;
-    for (int i = tid; i < O * O; i += 256) atomicAdd(out + i, outt[i] * L.inv_n);
+// daam_finalize_groups: blockIdx.z = group (daam_types.h FinGroupLaunch)
+template <typename ACC_T>
+__global__ __launch_bounds__(256) void finalize_grouped_kernel(const FinGroupLaunch G)
+{
+    if ((int)blockIdx.x >= G.g[blockIdx.z].rows) return;
+    const FinLaunch L = fin_group_view(G, blockIdx.z);
+#include "daam_fin_kernel_body.inc"
 }
 
 // trace.py:129-130  maps[:n] / (maps[1:n-1].sum(0) + 1e-6)
@@ -454,6 +421,21 @@ hipError_t launch_upload(void* dst, const void* src_host_mapped, size_t bytes, v
     return hipGetLastError();
 }
 
+// daam_finalize_groups: clear rows [0, rows[g]) of every group's output (out + g * stride floats), plane floats per row
+struct ZeroGroups {
+    float* out;
+    int64_t stride;
+    int32_t plane;
+    int32_t rows[kFinMaxGroups];
+};
+__global__ __launch_bounds__(256) void zero_groups_kernel(const ZeroGroups Z)
+{
+    const int g = blockIdx.y;
+    const size_t n = (size_t)Z.rows[g] * Z.plane;
+    float* o = Z.out + (size_t)g * Z.stride;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) o[i] = 0.f;
+}
+
 // ---------------------------------------------------------------------------------------
 // host-callable launchers (called from daam_api.hip)
 // ---------------------------------------------------------------------------------------
@@ -524,6 +506,45 @@ hipError_t launch_finalize(const FinLaunch& L, int acc_dtype, hipStream_t stream
     } else {
         if ((e = allow_lds(finalize_kernel<float>, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL((finalize_kernel<float>), dim3(L.tokens, L.n_chunks), dim3(256), lds, stream, L);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_zero_groups(float* out, size_t stride, int plane, const int* rows, int n_groups, hipStream_t stream)
+{
+    ZeroGroups Z;
+    Z.out = out;
+    Z.stride = (int64_t)stride;
+    Z.plane = plane;
+    int max_rows = 0;
+    for (int g = 0; g < kFinMaxGroups; ++g) {
+        Z.rows[g] = g < n_groups ? rows[g] : 0;
+        max_rows = max_rows > Z.rows[g] ? max_rows : Z.rows[g];
+    }
+    const size_t blocks = ((size_t)max_rows * plane + 1023) / 1024;
+    const int bx = blocks > 1024 ? 1024 : (int)blocks;
+    hipLaunchKernelGGL(zero_groups_kernel, dim3(bx > 0 ? bx : 1, n_groups), dim3(256), 0, stream, Z);
+    return hipGetLastError();
+}
+
+hipError_t launch_finalize_grouped(const FinGroupLaunch& G, int n_groups, int acc_dtype, hipStream_t stream, int* grid_out, int* lds_out)
+{
+    const FinLaunch& L = G.L;
+    const size_t lds = sizeof(float) * ((size_t)L.out_side * L.out_side + (size_t)L.max_side * L.max_side +
+                                        (size_t)L.max_side * L.out_side);
+    const dim3 grid(L.tokens, L.n_chunks, n_groups);
+    *grid_out = grid.x * grid.y * grid.z;
+    *lds_out = (int)lds;
+    hipError_t e;
+    if (acc_dtype == 0) {
+        if ((e = allow_lds(finalize_grouped_kernel<__half>, lds)) != hipSuccess) return e;
+        hipLaunchKernelGGL((finalize_grouped_kernel<__half>), grid, dim3(256), lds, stream, G);
+    } else if (acc_dtype == 2) {
+        if ((e = allow_lds(finalize_grouped_kernel<bf16_t>, lds)) != hipSuccess) return e;
+        hipLaunchKernelGGL((finalize_grouped_kernel<bf16_t>), grid, dim3(256), lds, stream, G);
+    } else {
+        if ((e = allow_lds(finalize_grouped_kernel<float>, lds)) != hipSuccess) return e;
+        hipLaunchKernelGGL((finalize_grouped_kernel<float>), grid, dim3(256), lds, stream, G);
     }
     return hipGetLastError();
 }

@@ -136,6 +136,39 @@ struct FinPipeLaunch {
     float inv_n;
 };
 
+// daam_finalize_groups: one launch per class for N global heat maps.  blockIdx.z = group; the group fixes its key range
+// (keys of one group are contiguous in the class's FinKey array / pointer tables), the row limit, 1/N and the output base.
+// Workgroups with blockIdx.x past the group's rows exit at once (grid x is the largest row count).
+constexpr int kFinMaxGroups = 64;
+struct FinGroup {
+    int32_t key_begin;      // first FinKey of the group in the class's array (general / same / up / x0.5 kernels)
+    int32_t n_keys;
+    int32_t rows;           // token rows of this group's output
+    float inv_n;            // 1 / (keys of the group over every class)
+    int64_t out_off;        // floats from FinLaunch::out / FinPipeLaunch::out to the group's [rows, O, O]
+    int32_t ptr_off;        // pipelined x2 kernel: entries from key_ptrs / same_ptrs to the group's first chunk
+    int32_t same_off;
+};
+struct FinGroupLaunch {
+    FinLaunch L;            // shared fields; keys / n_keys / tokens / inv_n / out are per group
+    FinGroup g[kFinMaxGroups];
+};
+struct FinPipeGroupLaunch {
+    FinPipeLaunch L;
+    FinGroup g[kFinMaxGroups];
+};
+// the group's view of a grouped launch
+__host__ __device__ inline FinLaunch fin_group_view(const FinGroupLaunch& G, int g)
+{
+    FinLaunch L = G.L;
+    L.keys += G.g[g].key_begin;
+    L.n_keys = G.g[g].n_keys;
+    L.tokens = G.g[g].rows;
+    L.inv_n = G.g[g].inv_n;
+    L.out += G.g[g].out_off;
+    return L;
+}
+
 // bfloat16 storage type (no arithmetic): values cross to f32 by a shift, back by round-to-nearest-even
 struct bf16_t { uint16_t bits; };
 __host__ __device__ inline float bf16_to_f32(bf16_t v) {

@@ -55,26 +55,37 @@ def gather_heat_maps(local_maps: torch.Tensor, n_items: int, group=None) -> torc
 def trace_prompts(pipe, prompts: Sequence[str], seeds: Optional[Sequence[int]] = None,
                   num_inference_steps: int = 50, trace_kwargs: Optional[dict] = None,
                   compute_kwargs: Optional[dict] = None, group=None,
-                  pipe_kwargs: Optional[dict] = None) -> Tuple[torch.Tensor, List[int]]:
+                  pipe_kwargs: Optional[dict] = None, prompts_per_call: int = 1) -> Tuple[torch.Tensor, List[int]]:
     """Run this rank's shard of ``prompts`` through ``pipe`` under ``daam_amd.trace`` and gather the
     global heat maps of ALL prompts (padded to 77 rows) on every rank.  Returns ``(maps
-    [n_prompts, 77, x, x], rows)`` with ``rows[i]`` = valid rows (``n_tokens + 2``) of prompt i."""
+    [n_prompts, 77, x, x], rows)`` with ``rows[i]`` = valid rows (``n_tokens + 2``) of prompt i.
+    ``prompts_per_call`` > 1: the shard goes through ``pipe`` in calls of up to that many prompts (one generator per
+    prompt, a list as diffusers takes it; ``trace(..., batch_prompts=True)``), each call's maps from one grouped finalize."""
     from .trace import trace
     from .utils import set_seed
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     mine = shard_indices(len(prompts), rank, world)
+    per_call = max(1, int(prompts_per_call))
+    filters = {k: v for k, v in (compute_kwargs or {}).items() if k in ('factors', 'head_idx', 'layer_idx')}
     local = []
-    with trace(pipe, **(trace_kwargs or {})) as tc:
-        for i in mine:
-            gen = set_seed(seeds[i]) if seeds is not None else None
+    tkw = dict(trace_kwargs or {})
+    if per_call > 1:
+        tkw['batch_prompts'] = True
+    with trace(pipe, **tkw) as tc:
+        for c0 in range(0, len(mine), per_call):
+            idx = mine[c0:c0 + per_call]
             kw = dict(pipe_kwargs or {})
-            if gen is not None:
-                kw['generator'] = gen
-            pipe(prompts[i], num_inference_steps=num_inference_steps, **kw)
-            # full 77 rows so that every rank contributes the same shape
-            local.append(tc.engine.global_heat_map(**{k: v for k, v in (compute_kwargs or {}).items()
-                                                       if k in ('factors', 'head_idx', 'layer_idx')}))
+            if seeds is not None:
+                gens = [set_seed(seeds[i]) for i in idx]
+                kw['generator'] = gens if per_call > 1 else gens[0]
+            if per_call == 1:
+                pipe(prompts[idx[0]], num_inference_steps=num_inference_steps, **kw)
+                # full 77 rows so that every rank contributes the same shape
+                local.append(tc.engine.global_heat_map(**filters))
+            else:
+                pipe([prompts[i] for i in idx], num_inference_steps=num_inference_steps, **kw)
+                local.extend(tc.engine.global_heat_maps(len(idx), [tc.engine.tokens] * len(idx), **filters).unbind(0))
     tokens, side = tc.engine.tokens, tc.engine.out_side
     if local:
         local_maps = torch.stack(local)

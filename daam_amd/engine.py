@@ -660,10 +660,75 @@ class HeatMapEngine:
         nat.check(self.lib.daam_finalize(self.ctx, mask, rows, optr, self.stream))
         return out
 
+    def key_groups(self, n_groups: int, factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None,
+                   layer_idx: Optional[int] = None) -> List[int]:
+        """The prompt of every key in the library's key order (-1: not selected), for ``n_groups`` prompts traced in one batch
+        under classifier-free guidance: a layer's kept keys are ``[cond x N*k]`` batch items of H heads each, so prompt ``p``
+        owns the block ``[p * kept/N, (p+1) * kept/N)``.  ``head_idx`` counts inside a prompt's block (the reference's
+        ``head_idx`` on a single prompt), ``factors`` / ``layer_idx`` filter as in ``global_heat_map``."""
+        total = ctypes.c_int()
+        nat.check(self.lib.daam_key_offset(self.ctx, 0, None, ctypes.byref(total)))
+        layout = []
+        for layer in self.touched:
+            factor, heads, _ = self.layer_info[layer]
+            off = ctypes.c_int()
+            nat.check(self.lib.daam_key_offset(self.ctx, layer, ctypes.byref(off), None))
+            layout.append((layer, off.value, factor, heads))
+        return prompt_key_groups(layout, total.value, n_groups, factors, head_idx, layer_idx)
+
+    def global_heat_maps(self, n_groups: int, n_rows: Sequence[int], factors: Optional[Sequence[int]] = None,
+                         head_idx: Optional[int] = None, layer_idx: Optional[int] = None) -> torch.Tensor:
+        """One global heat map per prompt of a batched generation, in ONE ``daam_finalize_groups`` call: returns
+        ``[n_groups, tokens, x, x]`` fp32 whose rows ``[0, n_rows[p])`` of prompt ``p`` are its map (the others are not written)."""
+        if self.ctx is None or not self.touched:
+            raise LookupError('no heat maps')
+        if len(n_rows) != n_groups:
+            raise ValueError(f'{len(n_rows)} row counts for {n_groups} prompts')
+        sel = ('groups', n_groups, None if factors is None else tuple(sorted(set(factors))), head_idx, layer_idx,
+               tuple(self.touched), len(self.layer_info))
+        cached = self._mask_cache.get(sel)
+        if cached is None:
+            groups = self.key_groups(n_groups, factors, head_idx, layer_idx)
+            counts = [groups.count(p) for p in range(n_groups)]
+            if len(self._mask_cache) > 64:
+                self._mask_cache.clear()
+            cached = self._mask_cache[sel] = ((ctypes.c_int32 * len(groups))(*groups), counts)
+        table, counts = cached
+        if min(counts) == 0:
+            self.flush()
+            raise LookupError('no heat maps')
+        rows = [max(1, min(int(r), self.tokens)) for r in n_rows]
+        self.flush()
+        out = torch.empty(n_groups, self.tokens, self.out_side, self.out_side, dtype=torch.float32, device=self.device)
+        nat.check(self.lib.daam_finalize_groups(self.ctx, table, n_groups, (ctypes.c_int32 * n_groups)(*rows), out.data_ptr(),
+                                                self.tokens * self.out_side * self.out_side, self.stream))
+        return out
+
     def normalize_(self, maps: torch.Tensor) -> torch.Tensor:
         """trace.py:129-130, in place on ``maps`` [n_rows, x, x] (contiguous fp32)."""
         nat.check(self.lib.daam_epilogue_normalize(maps.data_ptr(), maps.shape[0], maps.shape[-1], self.stream))
         return maps
+
+
+def prompt_key_groups(layout: Sequence[Tuple[int, int, int, int]], total: int, n_groups: int,
+                      factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None,
+                      layer_idx: Optional[int] = None) -> List[int]:
+    """``daam_finalize_groups``' key -> prompt table.  ``layout`` = ``(layer, key offset, factor, kept heads)`` of every tapped
+    layer; a layer's kept keys are the conditional half ``[cond x N*k]`` of H heads each, so prompt ``p`` owns
+    ``[p * kept/N, (p+1) * kept/N)``; ``head_idx`` counts inside that block."""
+    fset = {0, 1, 2, 4, 8, 16, 32, 64} if factors is None else set(factors)
+    groups = [-1] * total
+    for layer, off, factor, heads in layout:
+        if factor not in fset or (layer_idx is not None and layer_idx != layer):
+            continue
+        if heads % n_groups:
+            raise ValueError(f'layer {layer} keeps {heads} batch*heads entries, not divisible by {n_groups} prompts')
+        block = heads // n_groups
+        for p in range(n_groups):
+            for h in range(block):
+                if head_idx is None or head_idx == h:
+                    groups[off + p * block + h] = p
+    return groups
 
 
 def word_heat_map(maps: torch.Tensor, idxs: Sequence[int]) -> torch.Tensor:

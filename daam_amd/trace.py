@@ -14,6 +14,7 @@ The materialised path (``get_attention_scores`` -> ``daam_tap_probs`` -> ``bmm``
 """
 from __future__ import annotations
 
+import inspect
 import math
 import os
 import weakref
@@ -66,7 +67,7 @@ def _default_defer_bytes(pipeline=None) -> int:
 class DiffusionHeatMapHooker(AggregateHooker):
     def __init__(self, pipeline, low_memory: bool = False, load_heads: bool = False, save_heads: bool = False,
                  data_dir: Optional[str] = None, *, accumulate: str = 'exact', tap: str = 'qk',
-                 defer_steps: Optional[int] = None):
+                 defer_steps: Optional[int] = None, batch_prompts: bool = False):
         """Positional arguments as in the reference (trace.py:23-30).  Keyword-only extras:
         ``accumulate`` = ``'exact'`` (running sums in the pipeline dtype, like the reference) or
         ``'float32'``; ``tap`` = ``'qk'`` (fused, default) or ``'probs'`` (materialised
@@ -74,7 +75,10 @@ class DiffusionHeatMapHooker(AggregateHooker):
         (0 = one launch per layer call; default ``$DAAM_DEFER_STEPS`` or 64, the most one launch takes).
         The Q / K of the recorded steps are kept alive until their launch: at most ``$DAAM_DEFER_BYTES``
         (default: 40 % of the device memory free at set-up; a 50-step SDXL-1024 generation holds 19.4 GB -- both CFG
-        halves of every Q -- and runs as ONE tap launch, issued when the maps are first read)."""
+        halves of every Q -- and runs as ONE tap launch, issued when the maps are first read).
+        ``batch_prompts=True`` accepts ``pipe([p0, ..., pN-1])`` (classifier-free guidance, any ``num_images_per_prompt``):
+        ``compute_global_heat_maps`` then gives one map per prompt from one grouped finalize; ``False`` keeps the
+        reference's single-prompt rule."""
         if tap not in ('qk', 'probs'):
             raise ValueError("tap must be 'qk' or 'probs'")
         h = pipeline.unet.config.sample_size * pipeline.vae_scale_factor
@@ -89,7 +93,12 @@ class DiffusionHeatMapHooker(AggregateHooker):
                                     defer_bytes=_default_defer_bytes(pipeline), reuse_context=True)
         self.all_heat_maps = RawHeatMapCollection(self.engine)
         self.last_prompt: str = ''
+        self.last_prompts: List[str] = []
         self.last_image = None
+        self.last_images: list = []
+        self.batch_prompts = bool(batch_prompts)
+        self._batch_unchecked = False                                      # the first tapped call of a generation validates its batch
+        self._encode_args = None                                           # (num_images_per_prompt, do_classifier_free_guidance)
         self.time_idx = 0
         self._gen_idx = 0
         self.tap_mode = tap
@@ -129,19 +138,94 @@ class DiffusionHeatMapHooker(AggregateHooker):
             member._pinned_trace = None
         self.engine.flush()
 
-    def to_experiment(self, path, seed=None, id='.', subtype='.', **compute_kwargs):
-        """trace.py:68-81."""
+    def to_experiment(self, path, seed=None, id='.', subtype='.', prompt_idx: Optional[int] = None, **compute_kwargs):
+        """trace.py:68-81.  ``prompt_idx`` (batched trace): export prompt ``prompt_idx`` -- its text, its map and its first image."""
         from .experiment import GenerationExperiment
-        return GenerationExperiment(self.last_image, self.compute_global_heat_map(**compute_kwargs).heat_maps,
-                                    self.last_prompt, seed=seed, id=id, subtype=subtype, path=path,
+        if prompt_idx is None:
+            return GenerationExperiment(self.last_image, self.compute_global_heat_map(**compute_kwargs).heat_maps,
+                                        self.last_prompt, seed=seed, id=id, subtype=subtype, path=path,
+                                        tokenizer=self.pipe.tokenizer)
+        prompt_idx = self._check_prompt_idx(prompt_idx)
+        image = self.last_image
+        n = len(self.last_prompts)
+        if self.last_images and len(self.last_images) % n == 0:            # one image per sample: prompt p's first is p * k
+            image = self.last_images[prompt_idx * (len(self.last_images) // n)]
+        maps = self.compute_global_heat_map(prompt_idx=prompt_idx, **compute_kwargs).heat_maps
+        return GenerationExperiment(image, maps, self.last_prompts[prompt_idx], seed=seed, id=id, subtype=subtype, path=path,
                                     tokenizer=self.pipe.tokenizer)
 
-    def compute_global_heat_map(self, prompt=None, factors=None, head_idx=None, layer_idx=None, normalize=False):
+    # -- batched prompts ---------------------------------------------------------------------------
+    def _check_prompt_idx(self, prompt_idx: int) -> int:
+        n = len(self.last_prompts)
+        if not isinstance(prompt_idx, int) or not 0 <= prompt_idx < max(n, 1):
+            raise ValueError(f'prompt_idx {prompt_idx!r} out of range: the last generation traced {n} prompt(s)')
+        return prompt_idx
+
+    def _check_batch(self, batch: int):
+        """First tapped call of a batched generation: the batch must be [uncond x N*k ; cond x N*k]."""
+        self._batch_unchecked = False
+        n = len(self.last_prompts)
+        if n <= 1:                     # one prompt: any batch, with or without guidance, exactly as the default trace
+            return
+        if self._encode_args is not None:
+            k, cfg = self._encode_args
+            if not cfg:
+                raise ValueError(f'{n} prompts traced without classifier-free guidance: per-prompt heat maps need the '
+                                 f'[uncond ; cond] batch layout (the kept second half would split the prompts)')
+            if k is not None and batch != 2 * n * int(k):
+                raise ValueError(f'batch {batch} is not 2 x {n} prompts x {k} images per prompt (classifier-free guidance layout)')
+        if batch % (2 * n):
+            raise ValueError(f'batch {batch} does not divide into {n} prompt(s) under classifier-free guidance '
+                             f'([uncond x N*k ; cond x N*k] needs a multiple of 2 x {n})')
+
+    def compute_global_heat_maps(self, factors=None, head_idx=None, layer_idx=None, normalize=False,
+                                 prompts: Optional[List[str]] = None) -> List[GlobalHeatMap]:
+        """One ``GlobalHeatMap`` per prompt of the last (batched) generation, each cropped to its own
+        ``len(tokenize(p)) + 2`` rows, from ONE grouped finalize (``daam_finalize_groups``); the maps are views of one
+        ``[N, 77, x, x]`` buffer.  Filters are per prompt: ``head_idx`` counts inside the prompt's keys.  ``prompts`` (one per
+        traced prompt) replaces the texts that label and crop the maps, as ``prompt`` does in ``compute_global_heat_map``."""
+        if prompts is None:
+            prompts = self.last_prompts or [self.last_prompt]
+        elif len(prompts) != max(1, len(self.last_prompts)):
+            raise ValueError(f'{len(prompts)} prompts given for {len(self.last_prompts)} traced')
+        n_rows = [len(self.pipe.tokenizer.tokenize(p)) + 2 for p in prompts]
+        try:
+            maps = self.engine.global_heat_maps(len(prompts), n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx)
+        except LookupError:
+            if head_idx is not None or layer_idx is not None:
+                raise RuntimeError('No heat maps found for the given parameters.') from None
+            raise RuntimeError('No heat maps found. Did you forget to call `with trace(...)` during generation?') \
+                from None
+        out = []
+        for p, (prompt, rows) in enumerate(zip(prompts, n_rows)):
+            m = maps[p, :rows]
+            if normalize:
+                m = self.engine.normalize_(m)
+            out.append(GlobalHeatMap(self.pipe.tokenizer, prompt, m))
+        return out
+
+    def compute_global_heat_map(self, prompt=None, factors=None, head_idx=None, layer_idx=None, normalize=False,
+                                prompt_idx: Optional[int] = None):
         """Aggregate over time (already summed by the tap), layers and heads (trace.py:83-132):
         per selected ``(factor, layer, head)`` key bicubic-resize the summed map to ``x*x``, clamp
         at 0, average the keys, keep ``len(tokenize(prompt)) + 2`` rows, optionally normalise per
         pixel over the content tokens.  Returns a ``GlobalHeatMap`` whose ``heat_maps`` is an
-        fp32 device tensor."""
+        fp32 device tensor.  After a batched generation of N > 1 prompts, ``prompt_idx`` picks the prompt
+        (``compute_global_heat_maps`` gives all of them from one call)."""
+        n = len(self.last_prompts)
+        if prompt_idx is not None:
+            prompt_idx = self._check_prompt_idx(prompt_idx)
+        if n > 1:
+            if prompt_idx is None:
+                raise ValueError(f'the last generation traced {n} prompts: pass prompt_idx, or use compute_global_heat_maps() '
+                                 f'(a mean over every prompt\'s keys has no meaning)')
+            prompts = list(self.last_prompts)
+            if prompt is not None:
+                prompts[prompt_idx] = prompt                              # labels AND crops, as on one prompt
+            maps = self.compute_global_heat_maps(factors=factors, head_idx=head_idx, layer_idx=layer_idx, prompts=prompts)[prompt_idx]
+            if normalize:
+                self.engine.normalize_(maps.heat_maps)
+            return maps
         if prompt is None:
             prompt = self.last_prompt
         n_rows = len(self.pipe.tokenizer.tokenize(prompt)) + 2                 # 1 for SOS and 1 for padding (trace.py:127)
@@ -183,6 +267,7 @@ class ImageProcessorHooker(_CallInterceptor):
     def _after_postprocess(self, _processor, *args, **kwargs):
         images = self.monkey_super('postprocess', *args, **kwargs)
         self.parent_trace.last_image = images[0]
+        self.parent_trace.last_images = list(images)
         return images
 
 
@@ -191,7 +276,8 @@ class PipelineHooker(_CallInterceptor):
     running sums start from zero, the prompt and the generated image are remembered."""
 
     WRAPS = (('run_safety_checker', '_after_safety_checker', False),      # absent in SDXL pipelines
-             ('check_inputs', '_before_generation', True))
+             ('check_inputs', '_before_generation', True),
+             ('encode_prompt', '_on_encode_prompt', False))                 # batched traces: images per prompt, CFG
 
     def __init__(self, pipeline, parent_trace: 'trace'):
         super().__init__(pipeline, parent_trace)
@@ -199,11 +285,25 @@ class PipelineHooker(_CallInterceptor):
 
     def _before_generation(self, _pipe, prompt: Union[str, List[str]], *args, **kwargs):
         single = isinstance(prompt, str)
-        if not single and len(prompt) > 1:
+        t = self.parent_trace
+        if not single and len(prompt) > 1 and not t.batch_prompts:
             raise ValueError('Only single prompt generation is supported for heat map computation.')
         self.heat_maps.clear()                                             # RawHeatMapCollection.clear -> daam_reset
-        self.parent_trace.last_prompt = prompt if single else prompt[0]
+        t.last_prompt = prompt if single else prompt[0]
+        t.last_prompts = [prompt] if single else list(prompt)
+        t._batch_unchecked = t.batch_prompts
+        t._encode_args = None
         return self.monkey_super('check_inputs', prompt, *args, **kwargs)
+
+    def _on_encode_prompt(self, _pipe, *args, **kwargs):
+        try:
+            original = next(v for n, v in reversed(self._journal) if n == 'encode_prompt')
+            bound = inspect.signature(original).bind_partial(*args, **kwargs).arguments
+        except (TypeError, ValueError, StopIteration):
+            bound = kwargs
+        if 'do_classifier_free_guidance' in bound:
+            self.parent_trace._encode_args = (bound.get('num_images_per_prompt'), bool(bound['do_classifier_free_guidance']))
+        return self.monkey_super('encode_prompt', *args, **kwargs)
 
     def _after_safety_checker(self, pipe, image, *args, **kwargs):
         checked = self.monkey_super('run_safety_checker', image, *args, **kwargs)
@@ -215,6 +315,7 @@ class PipelineHooker(_CallInterceptor):
         else:
             pils = processor.numpy_to_pil(checked[0])
         self.parent_trace.last_image = pils[-1]
+        self.parent_trace.last_images = list(pils)
         return checked
 
 
@@ -292,6 +393,8 @@ class UNetCrossAttentionHooker(ObjectHooker):
         batch, positions, channels = query.shape
         factor = self._factor(positions)
         tapped = factor != 8 and key.shape[1] == self.context_size          # trace.py:289
+        if tapped and self.trace._batch_unchecked:
+            self.trace._check_batch(batch)
         if self._attend is not None and key.shape[1] == self.context_size:
             out = self._attend(self.layer_idx, query, key, value, self._heads, self._scale, factor, self._round_logits, tapped)
             if out is not None:
@@ -316,6 +419,8 @@ class UNetCrossAttentionHooker(ObjectHooker):
         self.trace._gen_idx += 1
         factor = self._factor(probs.shape[1])
         if self._is_tapped(probs.shape[-1], factor):
+            if self.trace._batch_unchecked:
+                self.trace._check_batch(probs.shape[0] // attn.heads)
             self.trace.engine.tap_probs(self.layer_idx, probs, factor)
         return attn.batch_to_head_dim(torch.bmm(probs, value))
 

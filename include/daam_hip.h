@@ -174,6 +174,17 @@ DAAM_API int daam_finalize(DaamCtx* ctx, const uint8_t* key_mask, int n_rows, fl
  * everything itself, as without this call) and by the next daam_tap_flush. */
 DAAM_API int daam_finalize_prepare(DaamCtx* ctx, const uint8_t* key_mask, int n_rows, float* out, void* stream);
 
+/* N global heat maps in one call (one prompt each, when a batch of N prompts was traced): key i (layer-major order, as key_mask)
+ * belongs to group key_group[i] (HOST int32, one per key of daam_key_offset's `total`; -1 = not selected).  out[g] (device, fp32,
+ * g * group_stride floats from `out`) = mean over the keys of group g of clamp(bicubic(plane), 0) for the token rows
+ * [0, n_rows[g]) (HOST int32, the daam_finalize rule for <= 0 / > tokens); rows >= n_rows[g] of out[g] are left untouched.
+ * 1 <= n_groups <= 64; a group with no keys: DAAM_E_NOMAPS.  n_groups == 1 is daam_finalize (and honours a
+ * daam_finalize_prepare announcement of it).  Otherwise the call clears the groups' rows itself and launches each class kernel
+ * ONCE for all groups (grouped forms: grid z = group); the device table cache of daam_finalize applies.  Exception: the round-2
+ * MFMA x2 kernel behind DAAM_NO_PIPE_FINALIZE=1 serves a grouped call as one daam_finalize per group. */
+DAAM_API int daam_finalize_groups(DaamCtx* ctx, const int32_t* key_group, int n_groups, const int32_t* n_rows,
+                                  float* out, size_t group_stride, void* stream);
+
 /* trace.py:129-130: maps[:n_rows] / (maps[1:n_rows-1].sum(0) + 1e-6), in place on the first
  * n_rows planes of `maps` [*, side, side] fp32. */
 DAAM_API int daam_epilogue_normalize(float* maps, int n_rows, int side, void* stream);
