@@ -20,8 +20,8 @@ E_INVALID, E_STATE, E_NOMAPS, E_UNSUPPORTED = -1, -2, -3, -4
 # every symbol include/daam_hip.h declares (tests check the library exports exactly these)
 EXPORTS = (
     'daam_abi_version', 'daam_last_error', 'daam_ctx_create', 'daam_ctx_destroy', 'daam_layer_configure',
-    'daam_layer_acc', 'daam_layer_touch', 'daam_layer_release', 'daam_reset', 'daam_tap_qk', 'daam_tap_qk_enqueue', 'daam_tap_qk_enqueue_many', 'daam_tap_pending', 'daam_tap_flush',
-    'daam_tap_probs', 'daam_attend_supported', 'daam_attend', 'daam_key_offset', 'daam_finalize', 'daam_finalize_prepare', 'daam_finalize_groups', 'daam_epilogue_normalize', 'daam_word_heat_map', 'daam_mask_overlap',
+    'daam_layer_acc', 'daam_layer_touch', 'daam_layer_release', 'daam_ctx_set_time_bins', 'daam_tap_steps', 'daam_reset', 'daam_tap_qk', 'daam_tap_qk_enqueue', 'daam_tap_qk_enqueue_many', 'daam_tap_pending', 'daam_tap_flush',
+    'daam_tap_probs', 'daam_attend_supported', 'daam_attend', 'daam_key_offset', 'daam_finalize', 'daam_finalize_prepare', 'daam_finalize_groups', 'daam_finalize_bins', 'daam_epilogue_normalize', 'daam_word_heat_map', 'daam_mask_overlap',
     'daam_last_launch', 'daam_last_flush', 'daam_last_kernels', 'daam_profile_enable', 'daam_profile_last_ms', 'daam_profile_history', 'daam_clock_monitor_start', 'daam_clock_monitor_read',
 )
 
@@ -63,6 +63,10 @@ def load() -> ctypes.CDLL:
             f'{LIB_PATH} is missing: the MI355X heat-map path has no fallback. '
             f'Build it with `python -m daam_amd.build` (needs hipcc, --offload-arch=gfx950).')
     lib = ctypes.CDLL(LIB_PATH)
+    # a library built before an entry point was added: same ABI version, fewer symbols -- as stale as a version mismatch
+    missing = [name for name in EXPORTS if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError(f'{LIB_PATH}: lacks {", ".join(missing)} (stale build); rebuild')
     lib.daam_abi_version.restype = c_int
     lib.daam_last_error.restype = c_char_p
     lib.daam_ctx_create.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_void_p)]
@@ -84,6 +88,10 @@ def load() -> ctypes.CDLL:
     lib.daam_finalize.argtypes = [c_void_p, POINTER(c_uint8), c_int, c_void_p, c_void_p]
     lib.daam_finalize_prepare.argtypes = [c_void_p, POINTER(c_uint8), c_int, c_void_p, c_void_p]
     lib.daam_finalize_groups.argtypes = [c_void_p, POINTER(c_int32), c_int, POINTER(c_int32), c_void_p, c_size_t, c_void_p]
+    lib.daam_finalize_bins.argtypes = [c_void_p, POINTER(c_int32), c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                       POINTER(c_int32), c_void_p, c_size_t, c_void_p]
+    lib.daam_ctx_set_time_bins.argtypes = [c_void_p, c_int, POINTER(c_int32)]
+    lib.daam_tap_steps.argtypes = [c_void_p, c_int, POINTER(c_int)]
     lib.daam_epilogue_normalize.argtypes = [c_void_p, c_int, c_int, c_void_p]
     lib.daam_word_heat_map.argtypes = [c_void_p, c_int, POINTER(c_int32), c_int, c_void_p, c_void_p, c_int, c_int,
                                        c_int, c_float, c_void_p, c_void_p]

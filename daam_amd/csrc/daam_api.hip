@@ -2,6 +2,7 @@
 // Owns no activations; owns (optionally) the running sums, the bicubic tap tables and a
 // small pinned upload ring for the per-launch device tables.
 #include "daam_types.h"
+#include "daam_fin_bins.h"
 #include "../../include/daam_hip.h"
 
 #include <algorithm>
@@ -64,6 +65,8 @@ hipError_t launch_start_gate(const unsigned* counter, unsigned target, int timeo
 constexpr int kClockMaxSamples = 4096;
 hipError_t launch_word(const float*, int, const int32_t*, int, float*, float*, int, int, int, float, float*,
                        hipStream_t);
+hipError_t launch_finalize_bin_sum(const BinSumLaunch&, int acc_dtype, hipStream_t);
+int bin_sum_elems_per_tile(int acc_dtype);
 }  // namespace daam
 
 using namespace daam;
@@ -190,13 +193,30 @@ struct Pending {
 };
 
 constexpr int kMaxTabs = 16;
+constexpr int kMaxBins = 64;         // time windows of a binned context (daam_ctx_set_time_bins)
 
 }  // namespace
 
 struct DaamCtx {
     int device = 0;                    // HIP device the context was created on; every entry point runs there
     int max_layers, tokens, out_side, acc_dtype;
+    // Layer slots.  Un-binned: slot = layer.  Time-binned (daam_ctx_set_time_bins): slot = window * max_layers + layer, an
+    // ordinary Layer over the window's slice of the layer's sums [n_bins][heads, tokens, side, side]; every tap entry point maps
+    // (layer, step) to its slot, so the deferred launch chains the steps of one window per table entry (TapLayer) as it
+    // chains the steps of a layer without windows.
     std::vector<Layer> layers;
+    int n_bins = 0;                    // 0: no windows (daam_ctx_set_time_bins never called)
+    int bin_first[kMaxBins] = {0};     // first step of each window
+    std::vector<int> tap_steps;        // per layer: taps since daam_reset (the step index of the next tap)
+    void* bin_scratch = nullptr;       // daam_finalize_bins: f32 planes of the window-range reduction (grows, never shrinks)
+    size_t bin_scratch_bytes = 0;
+    int slot_of(int layer) const {
+        if (n_bins <= 1) return layer;
+        const int step = tap_steps[layer];
+        int b = n_bins - 1;
+        while (b > 0 && bin_first[b] > step) --b;
+        return b * max_layers + layer;
+    }
     Ring ring;
     int16_t* d_tab_idx = nullptr;
     float* d_tab_w = nullptr;
@@ -456,6 +476,7 @@ int daam_ctx_create(int max_layers, int tokens, int out_side, int acc_dtype, Daa
     c->out_side = out_side;
     c->acc_dtype = acc_dtype;
     c->layers.resize(max_layers);
+    c->tap_steps.assign(max_layers, 0);
     hipError_t e = c->ring.init();
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tab_idx), sizeof(int16_t) * kMaxTabs * out_side * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tab_w), sizeof(float) * kMaxTabs * out_side * 4);
@@ -530,6 +551,7 @@ int daam_ctx_destroy(DaamCtx* c)
     if (c->d_fin_tab) (void)hipFree(c->d_fin_tab);
     if (c->d_tab_idx) (void)hipFree(c->d_tab_idx);
     if (c->d_tab_w) (void)hipFree(c->d_tab_w);
+    if (c->bin_scratch) (void)hipFree(c->bin_scratch);
     delete c;
     return 0;
 }
@@ -541,7 +563,7 @@ int daam_layer_configure(DaamCtx* c, int layer, int heads, int side, int factor,
     if (heads <= 0 || side <= 0 || side > 1024) return fail(DAAM_E_INVALID, "heads %d / side %d", heads, side);
     DeviceGuard on_device(c);
     for (auto& p : c->pending)
-        if (p.layer == layer) return fail(DAAM_E_STATE, "layer %d re-configured with un-flushed taps pending", layer);
+        if (p.layer % c->max_layers == layer) return fail(DAAM_E_STATE, "layer %d re-configured with un-flushed taps pending", layer);
     Layer& l = c->layers[layer];
     if (l.owned && l.acc) { HIP_TRY(hipFree(l.acc)); }
     l = Layer();
@@ -550,11 +572,12 @@ int daam_layer_configure(DaamCtx* c, int layer, int heads, int side, int factor,
     l.hw = side * side;
     l.factor = factor;
     l.bytes = (size_t)heads * c->tokens * l.hw * acc_elem(c->acc_dtype);
+    const int nb = std::max(1, c->n_bins);                     // a binned layer's buffer holds every window
     if (acc) {
         l.acc = acc;
     } else {
-        HIP_TRY(hipMalloc(&l.acc, l.bytes));
-        HIP_TRY(hipMemset(l.acc, 0, l.bytes));
+        HIP_TRY(hipMalloc(&l.acc, l.bytes * nb));
+        HIP_TRY(hipMemset(l.acc, 0, l.bytes * nb));
         l.owned = true;
     }
     if (side != c->out_side) {
@@ -600,6 +623,12 @@ int daam_layer_configure(DaamCtx* c, int layer, int heads, int side, int factor,
         l.tab = tab;
     }
     l.configured = true;
+    for (int b = 1; b < nb; ++b) {                             // window b: its slice of the same buffer
+        Layer& w = c->layers[(size_t)b * c->max_layers + layer];
+        w = l;
+        w.acc = static_cast<char*>(l.acc) + (size_t)b * l.bytes;
+        w.owned = false;
+    }
     return 0;
 }
 
@@ -608,7 +637,33 @@ int daam_layer_acc(DaamCtx* c, int layer, void** acc, size_t* bytes)
     if (!c || layer < 0 || layer >= c->max_layers || !c->layers[layer].configured)
         return fail(DAAM_E_STATE, "layer %d not configured", layer);
     if (acc) *acc = c->layers[layer].acc;
-    if (bytes) *bytes = c->layers[layer].bytes;
+    if (bytes) *bytes = c->layers[layer].bytes * std::max(1, c->n_bins);
+    return 0;
+}
+
+int daam_ctx_set_time_bins(DaamCtx* c, int n_bins, const int32_t* first_step)
+{
+    if (!c || !first_step) return fail(DAAM_E_INVALID, "NULL argument");
+    if (n_bins < 1 || n_bins > kMaxBins) return fail(DAAM_E_INVALID, "n_bins %d not in 1..%d", n_bins, kMaxBins);
+    if (first_step[0] != 0) return fail(DAAM_E_INVALID, "the first window starts at step %d, not 0", first_step[0]);
+    for (int b = 1; b < n_bins; ++b)
+        if (first_step[b] <= first_step[b - 1])
+            return fail(DAAM_E_INVALID, "window starts not strictly increasing: %d after %d", first_step[b], first_step[b - 1]);
+    for (const Layer& l : c->layers)
+        if (l.configured) return fail(DAAM_E_STATE, "time windows must be set before any layer is configured");
+    if (!c->pending.empty()) return fail(DAAM_E_STATE, "time windows set with deferred taps pending");
+    c->n_bins = n_bins;
+    for (int b = 0; b < kMaxBins; ++b) c->bin_first[b] = b < n_bins ? first_step[b] : 0;
+    c->layers.assign((size_t)n_bins * c->max_layers, Layer());
+    std::fill(c->tap_steps.begin(), c->tap_steps.end(), 0);
+    return 0;
+}
+
+int daam_tap_steps(DaamCtx* c, int layer, int* steps)
+{
+    if (!c || !steps) return fail(DAAM_E_INVALID, "NULL argument");
+    if (layer < 0 || layer >= c->max_layers) return fail(DAAM_E_INVALID, "layer %d out of range", layer);
+    *steps = c->tap_steps[layer];
     return 0;
 }
 
@@ -616,6 +671,7 @@ int daam_layer_touch(DaamCtx* c, int layer, void* stream)
 {
     if (!c || layer < 0 || layer >= c->max_layers || !c->layers[layer].configured)
         return fail(DAAM_E_STATE, "layer %d not configured", layer);
+    if (c->n_bins) return fail(DAAM_E_UNSUPPORTED, "a time-binned context does not take hand-written sums (which window?)");
     if (!c->pending.empty()) return fail(DAAM_E_STATE, "layer touched with deferred taps pending: flush first");
     DeviceGuard on_device(c);
     Layer& l = c->layers[layer];
@@ -629,13 +685,14 @@ int daam_layer_release(DaamCtx* c, int layer)
 {
     if (!c || layer < 0 || layer >= c->max_layers) return fail(DAAM_E_INVALID, "layer %d out of range", layer);
     for (auto& p : c->pending)
-        if (p.layer == layer) return fail(DAAM_E_STATE, "layer %d released with un-flushed taps pending", layer);
+        if (p.layer % c->max_layers == layer) return fail(DAAM_E_STATE, "layer %d released with un-flushed taps pending", layer);
     Layer& l = c->layers[layer];
     if (l.owned && l.acc) {
         DeviceGuard on_device(c);
         HIP_TRY(hipFree(l.acc));
     }
     l = Layer();                                               // unconfigured: no later call touches the old buffer
+    for (int b = 1; b < c->n_bins; ++b) c->layers[(size_t)b * c->max_layers + layer] = Layer();
     return 0;
 }
 
@@ -644,6 +701,7 @@ int daam_reset(DaamCtx* c, void* stream)
     if (!c) return fail(DAAM_E_INVALID, "ctx is NULL");
     c->drop_pending();
     c->prep_out = c->fold_out = nullptr;
+    std::fill(c->tap_steps.begin(), c->tap_steps.end(), 0);    // step indices of the time windows restart
     (void)stream;
     for (auto& l : c->layers)
         if (l.configured) {
@@ -798,11 +856,12 @@ int daam_tap_qk(DaamCtx* c, int layer, const void* q, const void* k, const DaamQ
     if (rc) return rc;
     if (!c->pending.empty()) return fail(DAAM_E_STATE, "immediate tap with deferred taps pending: flush first");
     DeviceGuard on_device(c);
+    const int slot = c->slot_of(layer);                        // the window of this step (= layer without windows)
     const bool mfma = use_mfma(c, *d, q, k);
-    if (!mfma && (rc = ensure_zeroed(c->layers[layer], (hipStream_t)stream))) return rc;
+    if (!mfma && (rc = ensure_zeroed(c->layers[slot], (hipStream_t)stream))) return rc;
     TapLaunch L;
     memset(&L, 0, sizeof L);
-    fill_layer(c, c->layers[layer], *d, mfma ? tap_mfma_tile_pixels() : kTapPixels, &L.one);
+    fill_layer(c, c->layers[slot], *d, mfma ? tap_mfma_tile_pixels() : kTapPixels, &L.one);
     L.one_ptr.q = q;
     L.one_ptr.k = k;
     L.n_layers = 1;
@@ -819,8 +878,9 @@ int daam_tap_qk(DaamCtx* c, int layer, const void* q, const void* k, const DaamQ
                                              &c->last_grid[0], &c->last_lds[0]);
     if (e != hipSuccess) return fail((int)e, "tap launch: %s", hipGetErrorString(e));
     c->last_kernels[0] = tap_kernel_name(kd1);
-    c->layers[layer].dirty = true;
-    c->layers[layer].zero_pending = false;
+    c->layers[slot].dirty = true;
+    c->layers[slot].zero_pending = false;
+    ++c->tap_steps[layer];
     return 0;
 }
 
@@ -853,6 +913,7 @@ int daam_attend(DaamCtx* c, int layer, const void* q, const void* k, const void*
         if (!c->pending.empty()) return fail(DAAM_E_STATE, "fused tap with deferred taps pending: flush first");
     }
     DeviceGuard on_device(c);
+    const int slot = tap ? c->slot_of(layer) : layer;
     AttendLaunch L;
     memset(&L, 0, sizeof L);
     L.q = q; L.k = k; L.v = v; L.out = out;
@@ -868,8 +929,8 @@ int daam_attend(DaamCtx* c, int layer, const void* q, const void* k, const void*
     L.v_sb = d->v_stride_b; L.v_sh = d->v_stride_h; L.v_st = d->v_stride_t;
     L.o_sb = d->o_stride_b; L.o_sh = d->o_stride_h; L.o_sp = d->o_stride_p;
     if (tap) {
-        L.acc = c->layers[layer].acc;
-        L.fresh = c->layers[layer].dirty ? 0 : 1;
+        L.acc = c->layers[slot].acc;
+        L.fresh = c->layers[slot].dirty ? 0 : 1;
     }
     int grid = 0, lds = 0;
     hipError_t e = launch_attend_d64(L, d->qk.in_dtype, c->acc_dtype, c->fast_exp && d->qk.round_logits, (hipStream_t)stream, &grid, &lds);
@@ -878,21 +939,21 @@ int daam_attend(DaamCtx* c, int layer, const void* q, const void* k, const void*
         c->last_grid[0] = grid;
         c->last_block[0] = 256;
         c->last_lds[0] = lds;
-        c->layers[layer].dirty = true;
-        c->layers[layer].zero_pending = false;
+        c->layers[slot].dirty = true;
+        c->layers[slot].zero_pending = false;
+        ++c->tap_steps[layer];
     }
     return 0;
 }
 
-int daam_tap_qk_enqueue(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d)
+// record one validated call for `slot` (a layer, or a (window, layer) slot of a binned context)
+static int enqueue_slot(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d)
 {
-    int rc = check_qk(c, layer, q, k, d);
-    if (rc) return rc;
     if (!c->pending.empty() && c->pending.front().d.in_dtype != d->in_dtype)
         return fail(DAAM_E_STATE, "mixed activation dtypes in one deferred batch: flush first");
-    if (c->pending_count.size() != (size_t)c->max_layers) {
-        c->pending_count.assign(c->max_layers, 0);
-        c->pending_last.assign(c->max_layers, -1);
+    if (c->pending_count.size() != c->layers.size()) {
+        c->pending_count.assign(c->layers.size(), 0);
+        c->pending_last.assign(c->layers.size(), -1);
     }
     if (c->pending_count[layer] > 0) {
         // every recorded step of a layer must share shape and strides
@@ -912,18 +973,29 @@ int daam_tap_qk_enqueue(DaamCtx* c, int layer, const void* q, const void* k, con
     return 0;
 }
 
+int daam_tap_qk_enqueue(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d)
+{
+    int rc = check_qk(c, layer, q, k, d);
+    if (rc) return rc;
+    rc = enqueue_slot(c, c->slot_of(layer), q, k, d);
+    if (!rc) ++c->tap_steps[layer];
+    return rc;
+}
+
 int daam_tap_qk_enqueue_many(DaamCtx* c, int n, const int32_t* layers, const void* const* q, const void* const* k,
                              const DaamQKDesc* const* descs)
 {
     if (!c || n < 0 || (n > 0 && (!layers || !q || !k || !descs))) return fail(DAAM_E_INVALID, "NULL argument");
     const size_t before = c->pending.size();
+    const std::vector<int> steps_before = c->tap_steps;
     for (int i = 0; i < n; ++i) {
         int rc = daam_tap_qk_enqueue(c, layers[i], q[i], k[i], descs[i]);
         if (rc) {
-            // all or nothing: rebuild the per-layer bookkeeping for the surviving prefix
+            // all or nothing: rebuild the per-slot bookkeeping for the surviving prefix, and the step counts
             std::vector<Pending> keep(c->pending.begin(), c->pending.begin() + before);
             c->drop_pending();
-            for (auto& p : keep) (void)daam_tap_qk_enqueue(c, p.layer, p.q, p.k, &p.d);
+            c->tap_steps = steps_before;
+            for (auto& p : keep) (void)enqueue_slot(c, p.layer, p.q, p.k, &p.d);
             return rc;
         }
     }
@@ -933,7 +1005,7 @@ int daam_tap_qk_enqueue_many(DaamCtx* c, int n, const int32_t* layers, const voi
 int daam_tap_pending(DaamCtx* c, int* n_calls, int* max_steps)
 {
     if (!c) return fail(DAAM_E_INVALID, "ctx is NULL");
-    std::vector<int> cnt(c->max_layers, 0);
+    std::vector<int> cnt(c->layers.size(), 0);
     int mx = 0;
     for (auto& p : c->pending) mx = std::max(mx, ++cnt[p.layer]);
     if (n_calls) *n_calls = (int)c->pending.size();
@@ -951,7 +1023,7 @@ int daam_tap_flush(DaamCtx* c, void* stream)
     // group the recorded calls by layer (first-seen order, steps in recorded order), and the
     // layers by kernel: MFMA k-step count ceil(d/16), or 0 = generic kernel.
     std::vector<int> order;
-    std::vector<int> slot(c->max_layers, -1);
+    std::vector<int> slot(c->layers.size(), -1);              // (a binned context: per (window, layer) slot)
     std::vector<std::vector<const Pending*>> per;
     std::vector<int> kind;
     for (auto& p : c->pending) {
@@ -1247,12 +1319,13 @@ int daam_tap_probs(DaamCtx* c, int layer, const void* probs, int in_dtype, int b
         return fail(DAAM_E_INVALID, "layer %d is [%d heads, %d positions], call has [%d kept, %d]", layer, l.heads, l.hw,
                     batch_heads - batch_heads / 2, hw);
     DeviceGuard on_device(c);
+    const int slot = c->slot_of(layer);
     {
-        int zrc = ensure_zeroed(c->layers[layer], (hipStream_t)stream);
+        int zrc = ensure_zeroed(c->layers[slot], (hipStream_t)stream);
         if (zrc) return zrc;
     }
     ProbsLaunch L;
-    L.acc = l.acc;
+    L.acc = c->layers[slot].acc;
     L.probs = probs;
     L.heads_kept = l.heads;
     L.bh_first = batch_heads / 2;
@@ -1264,7 +1337,8 @@ int daam_tap_probs(DaamCtx* c, int layer, const void* probs, int in_dtype, int b
     c->last_block[0] = 256;
     hipError_t e = launch_tap_probs(L, in_dtype, c->acc_dtype, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0]);
     if (e != hipSuccess) return fail((int)e, "probs tap launch: %s", hipGetErrorString(e));
-    c->layers[layer].dirty = true;
+    c->layers[slot].dirty = true;
+    ++c->tap_steps[layer];
     return 0;
 }
 
@@ -1303,18 +1377,20 @@ int fin_env(const char* name)
 // token rows a finalize call covers (ABI v6: the caller may pass the prompt's n_tokens + 2, daam/trace.py:127)
 static int fin_rows(const DaamCtx* c, int n_rows) { return (n_rows <= 0 || n_rows > c->tokens) ? c->tokens : n_rows; }
 
-static int fin_plan(DaamCtx* c, const uint8_t* key_mask, int rows, FinPlan& P)
+// the plan over `n_layers` entries of `layers` whose planes are of `dtype` (the context's sums: c->layers / max_layers / acc_dtype;
+// daam_finalize_bins also plans over the window slots of a binned context and over f32 scratch planes)
+static int fin_plan_on(DaamCtx* c, const Layer* layers, int n_layers, int dtype, const uint8_t* key_mask, int rows, FinPlan& P)
 {
     static const int env_chunks = fin_env("DAAM_FIN_CHUNKS"), env_pipe_chunks = fin_env("DAAM_FIN_PIPE_CHUNKS");   // pipelined x2 kernel only (A/B)
     auto& keys = P.keys;
     int pos = 0;
-    for (int i = 0; i < c->max_layers; ++i) {
-        const Layer& l = c->layers[i];
+    for (int i = 0; i < n_layers; ++i) {
+        const Layer& l = layers[i];
         if (!l.configured) continue;
         for (int h = 0; h < l.heads; ++h, ++pos) {
             if (key_mask && !key_mask[pos]) continue;
             FinKey k;
-            k.base = static_cast<const char*>(l.acc) + (size_t)h * c->tokens * l.hw * acc_elem(c->acc_dtype);
+            k.base = static_cast<const char*>(l.acc) + (size_t)h * c->tokens * l.hw * acc_elem(dtype);
             k.side = l.side;
             k.tab = l.tab;
             int cls = 3;
@@ -1340,15 +1416,15 @@ static int fin_plan(DaamCtx* c, const uint8_t* key_mask, int rows, FinPlan& P)
     P.pipe_up = P.mfma_up && !c->no_pipe_finalize && c->d_zero_planes;
     // bf16 / f32 sums (round 6): the pipelined kernel only (bf16: the tap matrix must split into two bf16 MFMA operands); the round-2 MFMA
     // kernels behind DAAM_NO_PIPE_FINALIZE take fp16 planes
-    if (c->acc_dtype == DAAM_BF16) P.pipe_up = P.pipe_up && c->d_up32_ops_bf16;
-    if (c->acc_dtype != DAAM_F16) P.mfma_up = P.pipe_up;
+    if (dtype == DAAM_BF16) P.pipe_up = P.pipe_up && c->d_up32_ops_bf16;
+    if (dtype != DAAM_F16) P.mfma_up = P.pipe_up;
     if (P.pipe_up) {
         const int n = (int)keys[1].size();
         const int want = env_pipe_chunks ? env_pipe_chunks : env_chunks ? env_chunks : std::max(1, (1024 + rows / 2) / rows);
         P.pipe_chunks = std::max(1, std::min(want, (n + 7) / 8));
         const int per = (n + P.pipe_chunks - 1) / P.pipe_chunks;
         P.pipe_nk = std::max(4, (per + 1) & ~1);
-        P.pipe_stride = (P.pipe_nk + finalize_pipe_ring(c->acc_dtype) + 2) & ~1;
+        P.pipe_stride = (P.pipe_nk + finalize_pipe_ring(dtype) + 2) & ~1;
     }
     // The same-size (64 x 64) keys ride along in the pipelined kernel (every wave adds its share of them to its accumulators
     // before the x2 loop) unless they outnumber the x2 keys 2 : 1 -- then they keep their own streaming kernel.
@@ -1379,6 +1455,11 @@ static int fin_plan(DaamCtx* c, const uint8_t* key_mask, int rows, FinPlan& P)
             }
     }
     return 0;
+}
+
+static int fin_plan(DaamCtx* c, const uint8_t* key_mask, int rows, FinPlan& P)
+{
+    return fin_plan_on(c, c->layers.data(), c->max_layers, c->acc_dtype, key_mask, rows, P);
 }
 
 // the device copy of the tables is the one these bytes were uploaded to, on this stream?
@@ -1419,6 +1500,7 @@ static bool fin_out_zeroable(const DaamCtx* c, const float* out, int rows)
 int daam_finalize_prepare(DaamCtx* c, const uint8_t* key_mask, int n_rows, float* out, void* stream)
 {
     if (!c || !out) return fail(DAAM_E_INVALID, "NULL argument");
+    if (c->n_bins > 1) return fail(DAAM_E_UNSUPPORTED, "daam_finalize_prepare: not on a time-binned context (daam_finalize_bins)");
     DeviceGuard on_device(c);
     hipStream_t s = (hipStream_t)stream;
     const int rows = fin_rows(c, n_rows);
@@ -1453,6 +1535,14 @@ int daam_finalize(DaamCtx* c, const uint8_t* key_mask, int n_rows, float* out, v
 {
     if (!c || !out) return fail(DAAM_E_INVALID, "NULL argument");
     if (!c->pending.empty()) return fail(DAAM_E_STATE, "finalize with deferred taps pending: flush first");
+    if (c->n_bins > 1) {                                       // a binned context: the whole generation = windows [0, n_bins)
+        int total = 0;
+        daam_key_offset(c, 0, nullptr, &total);
+        std::vector<int32_t> kg(total > 0 ? total : 1, -1);
+        for (int i = 0; i < total; ++i) kg[i] = (!key_mask || key_mask[i]) ? 0 : -1;
+        const int32_t b0 = 0, b1 = c->n_bins, r = n_rows;
+        return daam_finalize_bins(c, kg.data(), 1, nullptr, &b0, &b1, &r, out, 0, stream);
+    }
     DeviceGuard on_device(c);
     hipStream_t s = (hipStream_t)stream;
     const int rows = fin_rows(c, n_rows);
@@ -1671,49 +1761,31 @@ int daam_finalize(DaamCtx* c, const uint8_t* key_mask, int n_rows, float* out, v
 // group's keys are contiguous in the FinKey array and in the pointer tables of the pipelined x2 kernel, so no chunk straddles
 // two groups); the per-group part of a launch (key range, rows, 1/N, output base, pointer-table offsets) travels in the kernel
 // arguments and blockIdx.z selects it.
-int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, const int32_t* n_rows, float* out,
-                         size_t group_stride, void* stream)
+// The grouped finalize over the planes of `layers[0, n_layers)` (plane dtype `dtype`): key i of that table (layer-major, heads
+// inside) belongs to group key_group[i].  Arguments validated by the caller; `mask` = key_group[i] >= 0; `n_of` = keys per group.
+// per_group_fallback: the round-2 MFMA x2 kernel (DAAM_NO_PIPE_FINALIZE) may serve the call as one daam_finalize per group (only
+// over the context's own sums); otherwise such keys take the grouped LDS kernel.  timed_start: this call opens the profiled span.
+static int fin_groups_core(DaamCtx* c, Layer* layers, int n_layers, int dtype, const int32_t* key_group, int total_keys,
+                           int n_groups, const int32_t* n_rows, const std::vector<int>& rows, const std::vector<int>& n_of,
+                           std::vector<uint8_t>& mask, float* out, size_t group_stride, hipStream_t s, bool per_group_fallback,
+                           bool timed_start)
 {
-    if (!c || !out || !key_group || !n_rows) return fail(DAAM_E_INVALID, "NULL argument");
-    if (n_groups < 1 || n_groups > kFinMaxGroups) return fail(DAAM_E_INVALID, "n_groups %d not in 1..%d", n_groups, kFinMaxGroups);
-    if (!c->pending.empty()) return fail(DAAM_E_STATE, "finalize with deferred taps pending: flush first");
-    int total_keys = 0;
-    daam_key_offset(c, 0, nullptr, &total_keys);
-    std::vector<int> rows(n_groups);
-    for (int g = 0; g < n_groups; ++g) rows[g] = fin_rows(c, n_rows[g]);
     const size_t plane = (size_t)c->out_side * c->out_side;
-    for (int g = 0; g + 1 < n_groups; ++g)
-        if (group_stride < (size_t)rows[g] * plane)
-            return fail(DAAM_E_INVALID, "group_stride %zu < %d rows of %zu floats: groups would overlap", group_stride, rows[g], plane);
-    std::vector<uint8_t> mask(total_keys > 0 ? total_keys : 1);
-    std::vector<int> n_of(n_groups, 0);
-    for (int i = 0; i < total_keys; ++i) {
-        const int g = key_group[i];
-        if (g < -1 || g >= n_groups) return fail(DAAM_E_INVALID, "key_group[%d] = %d not in -1..%d", i, g, n_groups - 1);
-        mask[i] = g >= 0;
-        if (g >= 0) ++n_of[g];
-    }
-    for (int g = 0; g < n_groups; ++g)
-        if (!n_of[g]) return fail(DAAM_E_NOMAPS, "no heat maps selected for group %d", g);
-    if (n_groups == 1) return daam_finalize(c, mask.data(), n_rows[0], out, stream);
-    DeviceGuard on_device(c);
-    hipStream_t s = (hipStream_t)stream;
-    c->prep_out = c->fold_out = nullptr;
-    for (auto& l : c->layers)
-        if (l.configured) {
-            int zrc = ensure_zeroed(l, s);
+    for (int i = 0; i < n_layers; ++i)
+        if (layers[i].configured) {
+            int zrc = ensure_zeroed(layers[i], s);
             if (zrc) return zrc;
         }
     FinPlan P;
     {
-        int prc = fin_plan(c, mask.data(), c->tokens, P);
+        int prc = fin_plan_on(c, layers, n_layers, dtype, mask.data(), c->tokens, P);
         if (prc) return prc;
     }
-    if (P.mfma_up && !P.pipe_up) {
+    if (P.mfma_up && !P.pipe_up && per_group_fallback) {
         // the round-2 MFMA x2 kernel (DAAM_NO_PIPE_FINALIZE): one daam_finalize per group
         for (int g = 0; g < n_groups; ++g) {
             for (int i = 0; i < total_keys; ++i) mask[i] = key_group[i] == g;
-            int rc = daam_finalize(c, mask.data(), n_rows[g], out + (size_t)g * group_stride, stream);
+            int rc = daam_finalize(c, mask.data(), n_rows[g], out + (size_t)g * group_stride, s);
             if (rc) return rc;
         }
         return 0;
@@ -1746,7 +1818,7 @@ int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, con
         pipe_chunks = std::max(1, std::min(want, (max_n[1] + 7) / 8));
         pipe_per = (max_n[1] + pipe_chunks - 1) / pipe_chunks;
         pipe_nk = std::max(4, (pipe_per + 1) & ~1);
-        pipe_stride = (pipe_nk + finalize_pipe_ring(c->acc_dtype) + 2) & ~1;
+        pipe_stride = (pipe_nk + finalize_pipe_ring(dtype) + 2) & ~1;
         same_per = fold_same ? (max_n[0] + pipe_chunks - 1) / pipe_chunks : 0;
     }
     const size_t key_bytes = ((size_t)P.total * sizeof(FinKey) + 63) & ~size_t(63);
@@ -1783,7 +1855,7 @@ int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, con
     }
     P.tab.swap(tab);
     // the output is accumulated with atomics: rows [0, rows[g]) of every group are cleared first
-    if (c->profile) (void)hipEventRecord(c->prof_event(1, 0), s);
+    if (c->profile && timed_start) (void)hipEventRecord(c->prof_event(1, 0), s);
     const char* tab_dev = nullptr;
     bool ring_held = false;
     if (fin_cache_hit(c, P, s)) {
@@ -1853,7 +1925,7 @@ int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, con
     for (int cls = 0; cls < kFinClasses; ++cls) {
         n_classes += have[cls] ? 1 : 0;
         if (have[cls] && cls != 1)
-            for (auto& k : gk[cls]) side_bytes += (size_t)c->tokens * k.side * k.side * acc_elem(c->acc_dtype);
+            for (auto& k : gk[cls]) side_bytes += (size_t)c->tokens * k.side * k.side * acc_elem(dtype);
     }
     bool fork = pipe_up && n_classes > 1 && n_classes <= DaamCtx::kAux + 1 && !c->no_side_stream && side_bytes >= ((size_t)16 << 20);
     if (fork) {
@@ -1867,7 +1939,7 @@ int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, con
     auto names = [&](const char* kernel, const std::string& what) {
         launched_names += (launched_names.empty() ? "" : "+") + std::string(kernel) + "<" + what + ">";
     };
-    const std::string dt = dtype_name(c->acc_dtype);
+    const std::string dt = dtype_name(dtype);
     auto launch_class = [&](int cls, hipStream_t ks, int* grid, int* lds) -> hipError_t {
         const FinGroupLaunch& G = GL[cls];
         if (cls == 1 && pipe_up) {
@@ -1877,7 +1949,7 @@ int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, con
             PL.key_ptrs = reinterpret_cast<const unsigned long long*>(tab_dev + key_bytes);
             PL.same_ptrs = fold_same ? reinterpret_cast<const unsigned long long*>(tab_dev + key_bytes + ptr_bytes) : nullptr;
             PL.same_per = same_per;
-            PL.mfma_ops = c->acc_dtype == DAAM_BF16 ? c->d_up32_ops_bf16 : c->d_up32_ops;
+            PL.mfma_ops = dtype == DAAM_BF16 ? c->d_up32_ops_bf16 : c->d_up32_ops;
             PL.out = out;
             PL.n_chunks = pipe_chunks;
             PL.nk_pad = pipe_nk;
@@ -1886,13 +1958,13 @@ int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, con
             PL.inv_n = 0.f;
             memcpy(PG.g, G.g, sizeof PG.g);
             names("finalize_up32_pipe_grouped_kernel", dt + (fold_same ? " + same-size keys" : ""));
-            return launch_finalize_up32_pipe_grouped(PG, n_groups, c->acc_dtype, ks, grid);
+            return launch_finalize_up32_pipe_grouped(PG, n_groups, dtype, ks, grid);
         }
-        if (cls == 0) { names("finalize_same_grouped_kernel", dt); return launch_finalize_same_grouped(G, n_groups, c->acc_dtype, ks, grid); }
-        if (cls == 3) { names("finalize_grouped_kernel", dt); return launch_finalize_grouped(G, n_groups, c->acc_dtype, ks, grid, lds); }
-        if (cls == 4) { names("finalize_down2_grouped_kernel", dt); return launch_finalize_down2_grouped(G, n_groups, c->acc_dtype, ks, grid); }
+        if (cls == 0) { names("finalize_same_grouped_kernel", dt); return launch_finalize_same_grouped(G, n_groups, dtype, ks, grid); }
+        if (cls == 3) { names("finalize_grouped_kernel", dt); return launch_finalize_grouped(G, n_groups, dtype, ks, grid, lds); }
+        if (cls == 4) { names("finalize_down2_grouped_kernel", dt); return launch_finalize_down2_grouped(G, n_groups, dtype, ks, grid); }
         names(gk[cls][0].side == 32 ? "finalize_up_grouped_kernel<32>" : "finalize_up_grouped_kernel<16>", dt);
-        return launch_finalize_up_grouped(G, n_groups, gk[cls][0].side, c->acc_dtype, ks, grid);
+        return launch_finalize_up_grouped(G, n_groups, gk[cls][0].side, dtype, ks, grid);
     };
     int n_side = 0;
     const int order[kFinClasses] = {0, 2, 3, 4, 1};
@@ -1925,6 +1997,187 @@ int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, con
     if (c->profile) { (void)hipEventRecord(c->prof_event(1, 1), s); ++c->hist_count[1]; }
     release_tab();
     return 0;
+}
+
+int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, const int32_t* n_rows, float* out,
+                         size_t group_stride, void* stream)
+{
+    if (!c || !out || !key_group || !n_rows) return fail(DAAM_E_INVALID, "NULL argument");
+    if (n_groups < 1 || n_groups > kFinMaxGroups) return fail(DAAM_E_INVALID, "n_groups %d not in 1..%d", n_groups, kFinMaxGroups);
+    if (!c->pending.empty()) return fail(DAAM_E_STATE, "finalize with deferred taps pending: flush first");
+    if (c->n_bins > 1) {                                       // a binned context: every group over the whole generation
+        std::vector<int32_t> b0(n_groups, 0), b1(n_groups, c->n_bins);
+        return daam_finalize_bins(c, key_group, n_groups, nullptr, b0.data(), b1.data(), n_rows, out, group_stride, stream);
+    }
+    int total_keys = 0;
+    daam_key_offset(c, 0, nullptr, &total_keys);
+    std::vector<int> rows(n_groups);
+    for (int g = 0; g < n_groups; ++g) rows[g] = fin_rows(c, n_rows[g]);
+    const size_t plane = (size_t)c->out_side * c->out_side;
+    for (int g = 0; g + 1 < n_groups; ++g)
+        if (group_stride < (size_t)rows[g] * plane)
+            return fail(DAAM_E_INVALID, "group_stride %zu < %d rows of %zu floats: groups would overlap", group_stride, rows[g], plane);
+    std::vector<uint8_t> mask(total_keys > 0 ? total_keys : 1);
+    std::vector<int> n_of(n_groups, 0);
+    for (int i = 0; i < total_keys; ++i) {
+        const int g = key_group[i];
+        if (g < -1 || g >= n_groups) return fail(DAAM_E_INVALID, "key_group[%d] = %d not in -1..%d", i, g, n_groups - 1);
+        mask[i] = g >= 0;
+        if (g >= 0) ++n_of[g];
+    }
+    for (int g = 0; g < n_groups; ++g)
+        if (!n_of[g]) return fail(DAAM_E_NOMAPS, "no heat maps selected for group %d", g);
+    if (n_groups == 1) return daam_finalize(c, mask.data(), n_rows[0], out, stream);
+    DeviceGuard on_device(c);
+    hipStream_t s = (hipStream_t)stream;
+    c->prep_out = c->fold_out = nullptr;
+    return fin_groups_core(c, c->layers.data(), c->max_layers, c->acc_dtype, key_group, total_keys, n_groups, n_rows, rows, n_of, mask,
+                           out, group_stride, s, true, true);
+}
+
+// daam_finalize_bins: daam_finalize_groups with a window range per group.  Groups that each take ONE window (and no two of them
+// the same key of the same window) run the grouped class kernels straight on the windows' planes: the key space of the call is
+// the window slots' (window-major), and the per-group key table points at window bin_begin[g].  Otherwise one launch of
+// finalize_bin_sum_kernel adds every selected key's windows [bin_begin[g], bin_end[g]) into f32 scratch planes (rows
+// [0, n_rows[g]) only) and the grouped class kernels run on those, dispatched on THEIR dtype (f32).
+int daam_finalize_bins(DaamCtx* c, const int32_t* key_group, int n_groups, const int32_t* group_set, const int32_t* bin_begin,
+                       const int32_t* bin_end, const int32_t* n_rows, float* out, size_t group_stride, void* stream)
+{
+    if (!c || !out || !key_group || !bin_begin || !bin_end || !n_rows) return fail(DAAM_E_INVALID, "NULL argument");
+    if (n_groups < 1 || n_groups > kFinMaxGroups) return fail(DAAM_E_INVALID, "n_groups %d not in 1..%d", n_groups, kFinMaxGroups);
+    if (!c->pending.empty()) return fail(DAAM_E_STATE, "finalize with deferred taps pending: flush first");
+    const int nb = std::max(1, c->n_bins);
+    int n_sets = group_set ? 0 : n_groups;
+    for (int g = 0; g < n_groups; ++g) {
+        if (bin_begin[g] < 0 || bin_end[g] > nb || bin_begin[g] >= bin_end[g])
+            return fail(DAAM_E_INVALID, "group %d: window range [%d, %d) not a non-empty part of [0, %d)", g, bin_begin[g], bin_end[g], nb);
+        if (group_set) {
+            if (group_set[g] < 0) return fail(DAAM_E_INVALID, "group_set[%d] = %d < 0", g, group_set[g]);
+            n_sets = std::max(n_sets, group_set[g] + 1);
+        }
+    }
+    auto set_of = [&](int g) { return group_set ? group_set[g] : g; };
+    int total_keys = 0;
+    daam_key_offset(c, 0, nullptr, &total_keys);
+    std::vector<int> rows(n_groups);
+    for (int g = 0; g < n_groups; ++g) rows[g] = fin_rows(c, n_rows[g]);
+    const size_t plane = (size_t)c->out_side * c->out_side;
+    for (int g = 0; g + 1 < n_groups; ++g)
+        if (group_stride < (size_t)rows[g] * plane)
+            return fail(DAAM_E_INVALID, "group_stride %zu < %d rows of %zu floats: groups would overlap", group_stride, rows[g], plane);
+    std::vector<int> per_set(n_sets, 0);
+    for (int i = 0; i < total_keys; ++i) {
+        const int k = key_group[i];
+        // (with group_set: keys of a set no group takes are simply not selected)
+        if (k < -1 || (!group_set && k >= n_sets)) return fail(DAAM_E_INVALID, "key_group[%d] = %d not in -1..%d", i, k, n_sets - 1);
+        if (k >= 0 && k < n_sets) ++per_set[k];
+    }
+    std::vector<int> n_of(n_groups, 0);
+    for (int g = 0; g < n_groups; ++g)
+        if (!(n_of[g] = per_set[set_of(g)])) return fail(DAAM_E_NOMAPS, "no heat maps selected for group %d", g);
+    bool direct = true;
+    for (int g = 0; g < n_groups && direct; ++g) {
+        direct = bin_end[g] - bin_begin[g] == 1;
+        for (int h = 0; h < g && direct; ++h) direct = !(bin_begin[h] == bin_begin[g] && set_of(h) == set_of(g));
+    }
+    if (direct && nb == 1 && !group_set) return daam_finalize_groups(c, key_group, n_groups, n_rows, out, group_stride, stream);
+    DeviceGuard on_device(c);
+    hipStream_t s = (hipStream_t)stream;
+    c->prep_out = c->fold_out = nullptr;
+    if (direct) {
+        // key (window b, key i) of the slots' key space = b * total_keys + i
+        const size_t ext = (size_t)nb * total_keys;
+        std::vector<int32_t> kg(ext > 0 ? ext : 1, -1);
+        std::vector<uint8_t> mask(ext > 0 ? ext : 1, 0);
+        for (int g = 0; g < n_groups; ++g)
+            for (int i = 0; i < total_keys; ++i)
+                if (key_group[i] == set_of(g)) {
+                    kg[(size_t)bin_begin[g] * total_keys + i] = g;
+                    mask[(size_t)bin_begin[g] * total_keys + i] = 1;
+                }
+        return fin_groups_core(c, c->layers.data(), nb * c->max_layers, c->acc_dtype, kg.data(), (int)ext, n_groups, n_rows, rows, n_of,
+                               mask, out, group_stride, s, false, true);
+    }
+    // ---- window-range reduction: one task per (group, selected key)
+    std::vector<std::pair<int, int>> key_at;                  // key i -> (layer, head)
+    for (int l = 0; l < c->max_layers; ++l)
+        if (c->layers[l].configured)
+            for (int h = 0; h < c->layers[l].heads; ++h) key_at.push_back({l, h});
+    const size_t elem = acc_elem(c->acc_dtype);
+    const int per_tile = bin_sum_elems_per_tile(c->acc_dtype);
+    std::vector<BinSumTask> tasks;
+    std::vector<Layer> vl;                                     // the scratch planes as one-head layers
+    std::vector<int32_t> vg;
+    size_t scratch = 0;
+    int tiles = 0;
+    for (int g = 0; g < n_groups; ++g)
+        for (int i = 0; i < total_keys; ++i) {
+            if (key_group[i] != set_of(g)) continue;
+            const Layer& l = c->layers[(size_t)bin_begin[g] * c->max_layers + key_at[i].first];
+            BinSumTask t;
+            memset(&t, 0, sizeof t);
+            t.src = static_cast<const char*>(l.acc) + (size_t)key_at[i].second * c->tokens * l.hw * elem;
+            t.dst = reinterpret_cast<float*>(scratch);             // offset for now
+            t.win_stride = (int64_t)(l.bytes / elem);
+            t.n_elem = (int64_t)rows[g] * l.hw;
+            t.n_win = bin_end[g] - bin_begin[g];
+            t.tile_begin = tiles;
+            t.vec = ((reinterpret_cast<uintptr_t>(t.src) | l.bytes) & 15) == 0;
+            tiles += (int)((t.n_elem + per_tile - 1) / per_tile);
+            tasks.push_back(t);
+            Layer v;
+            v.configured = true;
+            v.heads = 1;
+            v.side = l.side;
+            v.hw = l.hw;
+            v.factor = l.factor;
+            v.tab = l.tab;
+            v.bytes = (size_t)t.n_elem * sizeof(float);
+            vl.push_back(v);
+            vg.push_back(g);
+            scratch += (v.bytes + 255) & ~size_t(255);
+        }
+    if (scratch > c->bin_scratch_bytes) {
+        if (c->bin_scratch) {
+            HIP_TRY(hipDeviceSynchronize());                   // earlier finalize calls may still read the old scratch
+            HIP_TRY(hipFree(c->bin_scratch));
+            c->bin_scratch = nullptr;
+            c->bin_scratch_bytes = 0;
+        }
+        HIP_TRY(hipMalloc(&c->bin_scratch, scratch));
+        c->bin_scratch_bytes = scratch;
+    }
+    for (size_t j = 0; j < tasks.size(); ++j) {
+        tasks[j].dst = reinterpret_cast<float*>(static_cast<char*>(c->bin_scratch) + reinterpret_cast<size_t>(tasks[j].dst));
+        tasks[j].vec = tasks[j].vec && (reinterpret_cast<uintptr_t>(tasks[j].dst) & 15) == 0;
+        vl[j].acc = tasks[j].dst;
+    }
+    // the windows' sums must hold what they should: a zeroing still owed since daam_reset comes first
+    for (int g = 0; g < n_groups; ++g)
+        for (int b = bin_begin[g]; b < bin_end[g]; ++b)
+            for (int l = 0; l < c->max_layers; ++l) {
+                int zrc = ensure_zeroed(c->layers[(size_t)b * c->max_layers + l], s);
+                if (zrc) return zrc;
+            }
+    const size_t tab_bytes = tasks.size() * sizeof(BinSumTask);
+    if (tab_bytes > Ring::kBytes) return fail(DAAM_E_UNSUPPORTED, "%zu window-range tasks in one call", tasks.size());
+    if (c->profile) (void)hipEventRecord(c->prof_event(1, 0), s);   // timed: the reduction and the class kernels
+    size_t off = 0;
+    HIP_TRY(c->ring.alloc(tab_bytes, &off));
+    memcpy(c->ring.host + off, tasks.data(), tab_bytes);
+    hipError_t e = c->ring.commit(off, tab_bytes, s);
+    BinSumLaunch BL;
+    BL.tasks = reinterpret_cast<const BinSumTask*>(c->ring.dev + off);
+    BL.n_tasks = (int32_t)tasks.size();
+    BL.n_tiles = tiles;
+    if (e == hipSuccess) e = launch_finalize_bin_sum(BL, c->acc_dtype, s);
+    (void)c->ring.release(s);
+    if (e != hipSuccess) return fail((int)e, "window-range reduction: %s", hipGetErrorString(e));
+    std::vector<uint8_t> mask(vg.size(), 1);
+    int rc = fin_groups_core(c, vl.data(), (int)vl.size(), DAAM_F32, vg.data(), (int)vg.size(), n_groups, n_rows, rows, n_of, mask, out,
+                             group_stride, s, false, false);
+    if (!rc) c->last_kernels[1] = std::string("finalize_bin_sum_kernel<") + dtype_name(c->acc_dtype) + ">+" + c->last_kernels[1];
+    return rc;
 }
 
 int daam_epilogue_normalize(float* maps, int n_rows, int side, void* stream)

@@ -85,6 +85,44 @@ def drain_released() -> None:
         fp.drain()
 
 
+MAX_TIME_BINS = 64
+
+
+def check_time_bins(time_bins) -> Optional[Tuple[int, ...]]:
+    """``time_bins`` of ``trace``: ``None`` (no windows), or the first denoising step of each window -- ints, starting at 0,
+    strictly increasing, 1 to 64 of them (``daam_ctx_set_time_bins``).  Returns them as a tuple."""
+    if time_bins is None:
+        return None
+    if isinstance(time_bins, (str, bytes)):
+        raise ValueError('time_bins must be an iterable of ints (first step of each window)')
+    try:
+        bins = list(time_bins)
+    except TypeError:
+        raise ValueError('time_bins must be an iterable of ints (first step of each window)') from None
+    if not 1 <= len(bins) <= MAX_TIME_BINS:
+        raise ValueError(f'time_bins must hold 1 to {MAX_TIME_BINS} window starts, got {len(bins)}')
+    for b in bins:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)):
+            raise ValueError(f'time_bins entries must be ints, got {b!r}')
+    bins = [int(b) for b in bins]
+    if bins[0] != 0:
+        raise ValueError(f'time_bins must start at step 0, got {bins[0]}')
+    if any(b <= a for a, b in zip(bins, bins[1:])):
+        raise ValueError(f'time_bins must be strictly increasing: {bins}')
+    return tuple(bins)
+
+
+def window_steps(time_bins: Sequence[int], layer_steps: Sequence[int]) -> List[int]:
+    """Steps each window received: a layer tapped n times put its steps ``[0, n)`` into the windows by their first steps; a
+    window's count is the most any layer put there."""
+    out = [0] * len(time_bins)
+    for n in layer_steps:
+        for w, first in enumerate(time_bins):
+            end = time_bins[w + 1] if w + 1 < len(time_bins) else n
+            out[w] = max(out[w], max(0, min(n, end) - first))
+    return out
+
+
 def release_parked_contexts() -> None:
     """Destroy every parked context now (frees their sum buffers too).  Not called at interpreter exit on purpose:
     process teardown reclaims them, and no HIP call has to run while the runtime is shutting down."""
@@ -96,7 +134,7 @@ def release_parked_contexts() -> None:
 
 class HeatMapEngine:
     def __init__(self, n_layers: int, tokens: int = 77, out_side: int = 64, accumulate: str = 'exact',
-                 defer_steps: int = 0, defer_bytes: int = 32 << 30, reuse_context: bool = False):
+                 defer_steps: int = 0, defer_bytes: int = 32 << 30, reuse_context: bool = False, time_bins=None):
         """``accumulate``: ``'exact'`` keeps the running sums in the pipeline dtype like the
         reference (fp16 sums on an fp16 pipeline, heatmap.py:156); ``'float32'`` is the
         accuracy mode.  ``defer_steps`` > 0 records Q/K pointers and taps ``defer_steps``
@@ -104,7 +142,8 @@ class HeatMapEngine:
         alive until then, and a launch is forced at the next step boundary once they add up to
         ``defer_bytes`` (both CFG halves count: 388 MB per SDXL-1024 step).  ``reuse_context``: ``close()`` parks
         the native context and the sum buffers for the next engine of the same geometry instead of destroying them
-        (what ``trace`` asks for: one trace per generation is the normal use)."""
+        (what ``trace`` asks for: one trace per generation is the normal use).  ``time_bins``: first step of each time window
+        (``check_time_bins``); every layer then keeps one running sum per window, ``[n_bins, heads, tokens, side, side]``."""
         if accumulate not in ('exact', 'float32'):
             raise ValueError("accumulate must be 'exact' or 'float32'")
         self.lib = nat.load()
@@ -112,6 +151,8 @@ class HeatMapEngine:
         self.tokens = int(tokens)
         self.out_side = int(out_side)
         self.accumulate = accumulate
+        self.time_bins = check_time_bins(time_bins)
+        self.n_bins = len(self.time_bins) if self.time_bins is not None else 0
         self.defer_steps = min(int(defer_steps), 64)     # the kernels stage at most 64 steps of pointers per launch
         self.defer_bytes = int(defer_bytes) if defer_bytes and defer_bytes > 0 else 1 << 62
         self.reuse_context = bool(reuse_context) and not os.environ.get('DAAM_NO_CTX_POOL')
@@ -201,11 +242,17 @@ class HeatMapEngine:
             nat.check(self.lib.daam_ctx_create(self.n_layers, self.tokens, self.out_side,
                                                _DTYPE_CODE[self.acc_dtype],
                                                nat.byref(ctx)))
+        if self.time_bins is not None:
+            try:
+                nat.check(self.lib.daam_ctx_set_time_bins(ctx, self.n_bins, (ctypes.c_int32 * self.n_bins)(*self.time_bins)))
+            except Exception:
+                self.lib.daam_ctx_destroy(ctx)
+                raise
         self.ctx = ctx
         self._sync_native()
 
     def _park_key(self) -> tuple:
-        return (str(self.device), self.n_layers, self.tokens, self.out_side, self.acc_dtype)
+        return (str(self.device), self.n_layers, self.tokens, self.out_side, self.acc_dtype, self.time_bins)
 
     def close(self) -> None:
         if self.ctx is not None:
@@ -254,7 +301,8 @@ class HeatMapEngine:
         if info is not None:
             # the reference would simply start a new key set / fail on a shape mismatch in `+`
             self.flush()
-        buf = torch.zeros(heads, self.tokens, side, side, dtype=self.acc_dtype, device=self.device)
+        shape = (heads, self.tokens, side, side) if self.time_bins is None else (self.n_bins, heads, self.tokens, side, side)
+        buf = torch.zeros(shape, dtype=self.acc_dtype, device=self.device)
         nat.check(self.lib.daam_layer_configure(self.ctx, layer, heads, side, factor, buf.data_ptr()))
         self.acc[layer] = buf
         self.layer_info[layer] = (factor, heads, side)
@@ -578,6 +626,8 @@ class HeatMapEngine:
     def add_map(self, factor: int, layer: int, head: int, heat_map: torch.Tensor) -> None:
         """``RawHeatMapCollection.update`` called by hand (heatmap.py:153-156): rare, done with a
         torch add on the layer's buffer."""
+        if self.time_bins is not None:
+            raise RuntimeError('daam_amd: update() is not supported on a trace with time_bins (which window would it add to?)')
         self._require_device(heat_map)
         self._ensure_ctx(heat_map.dtype)
         self.flush()
@@ -604,6 +654,8 @@ class HeatMapEngine:
         end of the trace -- like the reference's tensors -- because an engine whose buffers were handed out starts its
         next generation on fresh buffers and does not park them for reuse.  Taps of the SAME generation that follow
         the iteration do show up in them."""
+        if self.time_bins is not None:
+            raise RuntimeError('daam_amd: a trace with time_bins keeps one sum per window: use raw_heat_maps(time_bin)')
         self.flush()
         self._views_out = True
         for layer in list(self.touched):
@@ -612,12 +664,59 @@ class HeatMapEngine:
             for h in range(heads):
                 yield (factor, layer, h), buf[h]
 
+    def window_items(self, window: int) -> Dict[Key, torch.Tensor]:
+        """``{(factor, layer, head): running sum of window ``window`` [tokens, h, w]}`` -- views of the live buffers, with the
+        lifetime rules of ``items``."""
+        self.flush()
+        self._views_out = True
+        out: Dict[Key, torch.Tensor] = {}
+        for layer in list(self.touched):
+            factor, heads, _ = self.layer_info[layer]
+            buf = self.acc[layer][window]
+            for h in range(heads):
+                out[(factor, layer, h)] = buf[h]
+        return out
+
+    def tap_steps(self) -> Dict[int, int]:
+        """Taps each touched layer received since the last reset (``daam_tap_steps``; pending deferred taps are launched first)."""
+        self.flush()
+        if self.ctx is None:
+            return {}
+        n = ctypes.c_int()
+        out = {}
+        for layer in self.touched:
+            nat.check(self.lib.daam_tap_steps(self.ctx, layer, ctypes.byref(n)))
+            out[layer] = n.value
+        return out
+
+    def window_steps(self) -> List[int]:
+        """Steps each time window received in the last generation (one entry without ``time_bins``)."""
+        steps = list(self.tap_steps().values())
+        if self.time_bins is None:
+            return [max(steps, default=0)]
+        return window_steps(self.time_bins, steps)
+
+    def _binned(self, bins: Optional[Tuple[int, int]]) -> bool:
+        """Does this selection take ``daam_finalize_bins``?  Only a trace of several windows: one window is the default layout
+        (the library's un-binned calls, bit for bit)."""
+        if self.n_bins > 1:
+            return True
+        if bins is not None and tuple(bins) != (0, 1):
+            raise ValueError(f'time window range {bins} on a trace of one window')
+        return False
+
     # ---- finalize ---------------------------------------------------------------------------------
     def global_heat_map(self, factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None,
-                        layer_idx: Optional[int] = None, n_rows: Optional[int] = None) -> torch.Tensor:
+                        layer_idx: Optional[int] = None, n_rows: Optional[int] = None,
+                        bins: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """trace.py:103-126: returns ``[n_rows, x, x]`` fp32 on the device.  ``n_rows`` (default: every token row) is the
         crop of trace.py:127 applied BEFORE the work: the planes of the token rows nobody reads are neither fetched nor
-        written (``daam_finalize``'s ``n_rows``, ABI v6)."""
+        written (``daam_finalize``'s ``n_rows``, ABI v6).  ``bins`` = ``(first, end)`` window range of a trace with ``time_bins``
+        (default: the whole generation)."""
+        if self._binned(bins):
+            b0, b1 = bins if bins is not None else (0, self.n_bins)
+            rows = self.tokens if n_rows is None else max(1, min(int(n_rows), self.tokens))
+            return self.time_heat_maps([(b0, b1, 0)], 1, [rows], factors, head_idx, layer_idx)[0, :rows]
         rows = self.tokens if n_rows is None else max(1, min(int(n_rows), self.tokens))
         fset = {0, 1, 2, 4, 8, 16, 32, 64} if factors is None else set(factors)
         if self.ctx is None or not self.touched:
@@ -677,9 +776,16 @@ class HeatMapEngine:
         return prompt_key_groups(layout, total.value, n_groups, factors, head_idx, layer_idx)
 
     def global_heat_maps(self, n_groups: int, n_rows: Sequence[int], factors: Optional[Sequence[int]] = None,
-                         head_idx: Optional[int] = None, layer_idx: Optional[int] = None) -> torch.Tensor:
+                         head_idx: Optional[int] = None, layer_idx: Optional[int] = None,
+                         bins: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """One global heat map per prompt of a batched generation, in ONE ``daam_finalize_groups`` call: returns
-        ``[n_groups, tokens, x, x]`` fp32 whose rows ``[0, n_rows[p])`` of prompt ``p`` are its map (the others are not written)."""
+        ``[n_groups, tokens, x, x]`` fp32 whose rows ``[0, n_rows[p])`` of prompt ``p`` are its map (the others are not written).
+        ``bins``: window range, as in ``global_heat_map``."""
+        if self._binned(bins):
+            if len(n_rows) != n_groups:
+                raise ValueError(f'{len(n_rows)} row counts for {n_groups} prompts')
+            b0, b1 = bins if bins is not None else (0, self.n_bins)
+            return self.time_heat_maps([(b0, b1, p) for p in range(n_groups)], n_groups, n_rows, factors, head_idx, layer_idx)
         if self.ctx is None or not self.touched:
             raise LookupError('no heat maps')
         if len(n_rows) != n_groups:
@@ -702,6 +808,42 @@ class HeatMapEngine:
         out = torch.empty(n_groups, self.tokens, self.out_side, self.out_side, dtype=torch.float32, device=self.device)
         nat.check(self.lib.daam_finalize_groups(self.ctx, table, n_groups, (ctypes.c_int32 * n_groups)(*rows), out.data_ptr(),
                                                 self.tokens * self.out_side * self.out_side, self.stream))
+        return out
+
+    def time_heat_maps(self, groups: Sequence[Tuple[int, int, int]], n_prompts: int, n_rows: Sequence[int],
+                       factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None,
+                       layer_idx: Optional[int] = None) -> torch.Tensor:
+        """Global heat maps of ``(first window, end window, prompt)`` groups (``daam_finalize_bins``, at most 64 groups per call):
+        returns ``[len(groups), tokens, x, x]`` fp32 whose rows ``[0, n_rows[prompt])`` of each group are its map.  ``n_prompts``
+        prompts share the key table (``key_groups``); the filters are per prompt."""
+        if self.ctx is None or not self.touched:
+            raise LookupError('no heat maps')
+        if len(n_rows) != n_prompts:
+            raise ValueError(f'{len(n_rows)} row counts for {n_prompts} prompts')
+        sel = ('bins', n_prompts, None if factors is None else tuple(sorted(set(factors))), head_idx, layer_idx,
+               tuple(self.touched), len(self.layer_info))
+        cached = self._mask_cache.get(sel)
+        if cached is None:
+            table = self.key_groups(n_prompts, factors, head_idx, layer_idx)
+            counts = [table.count(p) for p in range(n_prompts)]
+            if len(self._mask_cache) > 64:
+                self._mask_cache.clear()
+            cached = self._mask_cache[sel] = ((ctypes.c_int32 * len(table))(*table), counts)
+        table, counts = cached
+        if any(counts[p] == 0 for _, _, p in groups):
+            self.flush()
+            raise LookupError('no heat maps')
+        rows = [max(1, min(int(r), self.tokens)) for r in n_rows]
+        self.flush()
+        plane = self.tokens * self.out_side * self.out_side
+        out = torch.empty(len(groups), self.tokens, self.out_side, self.out_side, dtype=torch.float32, device=self.device)
+        for start in range(0, len(groups), 64):                 # the library takes at most 64 groups per call
+            part = groups[start:start + 64]
+            n = len(part)
+            i32 = ctypes.c_int32 * n
+            nat.check(self.lib.daam_finalize_bins(self.ctx, table, n, i32(*[p for _, _, p in part]), i32(*[b for b, _, _ in part]),
+                                                  i32(*[e for _, e, _ in part]), i32(*[rows[p] for _, _, p in part]),
+                                                  out.data_ptr() + start * plane * 4, plane, self.stream))
         return out
 
     def normalize_(self, maps: torch.Tensor) -> torch.Tensor:

@@ -38,6 +38,8 @@ class RawHeatMapCollection:
         return {k[2] for k in self._engine.keys()}
 
     def __iter__(self) -> Iterator[Tuple[RawHeatMapKey, torch.Tensor]]:
+        if self._engine.time_bins is not None:
+            raise RuntimeError('this trace has time_bins: it keeps one sum per window, use raw_heat_maps(time_bin)')
         return self._engine.items()
 
     def __len__(self) -> int:

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import inspect
 import math
+import numbers
 import os
 import weakref
 from pathlib import Path
@@ -24,7 +25,7 @@ from typing import Any, List, Optional, Type, Union
 import torch
 import torch.nn.functional as F
 
-from .engine import HeatMapEngine
+from .engine import HeatMapEngine, check_time_bins
 from .heatmap import GlobalHeatMap, RawHeatMapCollection
 from .hook import AggregateHooker, ObjectHooker, UNetCrossAttentionLocator
 from .utils import cache_dir
@@ -67,7 +68,7 @@ def _default_defer_bytes(pipeline=None) -> int:
 class DiffusionHeatMapHooker(AggregateHooker):
     def __init__(self, pipeline, low_memory: bool = False, load_heads: bool = False, save_heads: bool = False,
                  data_dir: Optional[str] = None, *, accumulate: str = 'exact', tap: str = 'qk',
-                 defer_steps: Optional[int] = None, batch_prompts: bool = False):
+                 defer_steps: Optional[int] = None, batch_prompts: bool = False, time_bins=None):
         """Positional arguments as in the reference (trace.py:23-30).  Keyword-only extras:
         ``accumulate`` = ``'exact'`` (running sums in the pipeline dtype, like the reference) or
         ``'float32'``; ``tap`` = ``'qk'`` (fused, default) or ``'probs'`` (materialised
@@ -78,9 +79,16 @@ class DiffusionHeatMapHooker(AggregateHooker):
         halves of every Q -- and runs as ONE tap launch, issued when the maps are first read).
         ``batch_prompts=True`` accepts ``pipe([p0, ..., pN-1])`` (classifier-free guidance, any ``num_images_per_prompt``):
         ``compute_global_heat_maps`` then gives one map per prompt from one grouped finalize; ``False`` keeps the
-        reference's single-prompt rule."""
+        reference's single-prompt rule.
+        ``time_bins`` (ints: the first denoising step of each window, starting at 0, strictly increasing, 1 to 64 of them) splits
+        the running sums by time: window ``i`` holds the steps ``[time_bins[i], time_bins[i+1])``, the last one is open-ended.  A
+        call's step is the number of tapped calls of its layer since the generation began.  ``compute_global_heat_map(time_bin=)``
+        then selects a window or a range of them, ``compute_time_heat_maps`` gives one map per window; ``None`` keeps one sum
+        over the whole generation (the reference's running sum, which the reference's unused ``time_idx`` never splits,
+        trace.py:38,61-62)."""
         if tap not in ('qk', 'probs'):
             raise ValueError("tap must be 'qk' or 'probs'")
+        self.time_bins = check_time_bins(time_bins)
         h = pipeline.unet.config.sample_size * pipeline.vae_scale_factor
         self.latent_hw = 4096 if h == 512 or h == 1024 else 9216          # trace.py:32-33
         locate_middle = load_heads or save_heads
@@ -90,7 +98,7 @@ class DiffusionHeatMapHooker(AggregateHooker):
         self.engine = HeatMapEngine(max(1, len(modules_found)), tokens=77, out_side=int(math.sqrt(self.latent_hw)),
                                     accumulate=accumulate,
                                     defer_steps=_default_defer() if defer_steps is None else defer_steps,
-                                    defer_bytes=_default_defer_bytes(pipeline), reuse_context=True)
+                                    defer_bytes=_default_defer_bytes(pipeline), reuse_context=True, time_bins=self.time_bins)
         self.all_heat_maps = RawHeatMapCollection(self.engine)
         self.last_prompt: str = ''
         self.last_prompts: List[str] = []
@@ -154,6 +162,105 @@ class DiffusionHeatMapHooker(AggregateHooker):
         return GenerationExperiment(image, maps, self.last_prompts[prompt_idx], seed=seed, id=id, subtype=subtype, path=path,
                                     tokenizer=self.pipe.tokenizer)
 
+    # -- time windows ------------------------------------------------------------------------------
+    @property
+    def n_time_bins(self) -> int:
+        bins = getattr(self, 'time_bins', None)
+        return len(bins) if bins is not None else 1
+
+    def _bin_range(self, time_bin):
+        """``time_bin`` -> ``(first, end)`` window range, or ``None`` (the whole generation).  An int (negative counts from the
+        end) is one window; a slice with step ``None`` / 1 is a range, which must not be empty."""
+        if time_bin is None:
+            return None
+        n = self.n_time_bins
+        if isinstance(time_bin, slice):
+            if time_bin.step not in (None, 1):
+                raise ValueError(f'time_bin slice step must be None or 1, got {time_bin.step!r}')
+            try:
+                b0, b1, _ = time_bin.indices(n)
+            except TypeError:
+                raise ValueError(f'time_bin slice bounds must be ints: {time_bin!r}') from None
+            if b0 >= b1:
+                raise ValueError(f'time_bin {time_bin!r} selects no window of {n}')
+            return b0, b1
+        if isinstance(time_bin, bool) or not isinstance(time_bin, numbers.Integral):
+            raise ValueError(f'time_bin must be an int, a slice or None, got {time_bin!r}')
+        i = int(time_bin)
+        if not -n <= i < n:
+            raise ValueError(f'time_bin {i} out of range: the trace has {n} time window(s)')
+        i %= n
+        return i, i + 1
+
+    def _check_bin_steps(self, rng) -> None:
+        """A selected window range that received no step: RuntimeError naming the windows."""
+        if rng is None or self.n_time_bins == 1:
+            return
+        steps = self.time_bin_steps()
+        if not any(steps[rng[0]:rng[1]]):
+            names = ', '.join(str(b) for b in range(*rng))
+            raise RuntimeError(f'time window(s) {names} received no denoising steps in the last generation '
+                               f'(steps per window: {steps})')
+
+    def time_bin_steps(self) -> List[int]:
+        """How many denoising steps each time window received in the last generation (one entry without ``time_bins``)."""
+        return self.engine.window_steps()
+
+    def raw_heat_maps(self, time_bin: int) -> dict:
+        """``{(factor, layer, head): running sum [77, h, w]}`` of one time window: zero-copy views of the live sums, like
+        ``all_heat_maps`` (which a trace with ``time_bins`` does not offer: it holds one sum per window)."""
+        if isinstance(time_bin, slice):
+            raise ValueError('raw_heat_maps takes one window (an int)')
+        b0, _ = self._bin_range(time_bin)
+        if self.engine.time_bins is None:
+            return dict(self.engine.items())
+        return self.engine.window_items(b0)
+
+    def compute_time_heat_maps(self, prompt=None, factors=None, head_idx=None, layer_idx=None, normalize=False,
+                               prompt_idx: Optional[int] = None) -> list:
+        """One ``GlobalHeatMap`` per time window, from ONE grouped finalize per class (``daam_finalize_bins``; groups = windows,
+        or windows x prompts; 64 groups per call).  The entry of a window that received no step is ``None``.  After a batched
+        generation of N > 1 prompts, ``prompt_idx`` picks the prompt; without it each entry is the list of the N prompts' maps."""
+        n = len(self.last_prompts)
+        if prompt_idx is not None:
+            prompt_idx = self._check_prompt_idx(prompt_idx)
+        batched = n > 1
+        if batched:
+            prompts = list(self.last_prompts)
+            if prompt is not None:
+                prompts[prompt_idx if prompt_idx is not None else 0] = prompt
+        else:
+            prompts = [self.last_prompt if prompt is None else prompt]
+        if self.engine.time_bins is None:                                  # one window: the whole generation
+            if batched and prompt_idx is None:
+                return [self.compute_global_heat_maps(factors, head_idx, layer_idx, normalize, prompts=prompts)]
+            return [self.compute_global_heat_map(prompt, factors, head_idx, layer_idx, normalize, prompt_idx=prompt_idx)]
+        steps = self.time_bin_steps()
+        windows = [w for w, k in enumerate(steps) if k > 0]
+        if not windows:
+            raise RuntimeError('No heat maps found. Did you forget to call `with trace(...)` during generation?')
+        n_rows = [len(self.pipe.tokenizer.tokenize(p)) + 2 for p in prompts]
+        which = [prompt_idx] if (batched and prompt_idx is not None) else list(range(len(prompts)))
+        groups = [(w, w + 1, p) for w in windows for p in which]
+        try:
+            maps = self.engine.time_heat_maps(groups, len(prompts), n_rows, factors=factors, head_idx=head_idx,
+                                              layer_idx=layer_idx)
+        except LookupError:
+            raise RuntimeError('No heat maps found for the given parameters.') from None
+        out: list = [None] * len(steps)
+        for gi, (w, _, p) in enumerate(groups):
+            m = maps[gi, :n_rows[p]]
+            if normalize:
+                m = self.engine.normalize_(m)
+            hm = GlobalHeatMap(self.pipe.tokenizer, prompts[p], m)
+            if batched and prompt_idx is None:
+                if out[w] is None:
+                    out[w] = []
+                out[w].append(hm)
+            else:
+                out[w] = hm
+        return out
+
     # -- batched prompts ---------------------------------------------------------------------------
     def _check_prompt_idx(self, prompt_idx: int) -> int:
         n = len(self.last_prompts)
@@ -179,18 +286,22 @@ class DiffusionHeatMapHooker(AggregateHooker):
                              f'([uncond x N*k ; cond x N*k] needs a multiple of 2 x {n})')
 
     def compute_global_heat_maps(self, factors=None, head_idx=None, layer_idx=None, normalize=False,
-                                 prompts: Optional[List[str]] = None) -> List[GlobalHeatMap]:
+                                 prompts: Optional[List[str]] = None, time_bin=None) -> List[GlobalHeatMap]:
         """One ``GlobalHeatMap`` per prompt of the last (batched) generation, each cropped to its own
         ``len(tokenize(p)) + 2`` rows, from ONE grouped finalize (``daam_finalize_groups``); the maps are views of one
         ``[N, 77, x, x]`` buffer.  Filters are per prompt: ``head_idx`` counts inside the prompt's keys.  ``prompts`` (one per
-        traced prompt) replaces the texts that label and crop the maps, as ``prompt`` does in ``compute_global_heat_map``."""
+        traced prompt) replaces the texts that label and crop the maps, as ``prompt`` does in ``compute_global_heat_map``.
+        ``time_bin``: the time window(s) to aggregate, as in ``compute_global_heat_map``."""
+        rng = self._bin_range(time_bin)
+        self._check_bin_steps(rng)
         if prompts is None:
             prompts = self.last_prompts or [self.last_prompt]
         elif len(prompts) != max(1, len(self.last_prompts)):
             raise ValueError(f'{len(prompts)} prompts given for {len(self.last_prompts)} traced')
         n_rows = [len(self.pipe.tokenizer.tokenize(p)) + 2 for p in prompts]
         try:
-            maps = self.engine.global_heat_maps(len(prompts), n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx)
+            kw = {} if rng is None else dict(bins=rng)
+            maps = self.engine.global_heat_maps(len(prompts), n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx, **kw)
         except LookupError:
             if head_idx is not None or layer_idx is not None:
                 raise RuntimeError('No heat maps found for the given parameters.') from None
@@ -205,16 +316,19 @@ class DiffusionHeatMapHooker(AggregateHooker):
         return out
 
     def compute_global_heat_map(self, prompt=None, factors=None, head_idx=None, layer_idx=None, normalize=False,
-                                prompt_idx: Optional[int] = None):
+                                prompt_idx: Optional[int] = None, time_bin=None):
         """Aggregate over time (already summed by the tap), layers and heads (trace.py:83-132):
         per selected ``(factor, layer, head)`` key bicubic-resize the summed map to ``x*x``, clamp
         at 0, average the keys, keep ``len(tokenize(prompt)) + 2`` rows, optionally normalise per
         pixel over the content tokens.  Returns a ``GlobalHeatMap`` whose ``heat_maps`` is an
         fp32 device tensor.  After a batched generation of N > 1 prompts, ``prompt_idx`` picks the prompt
-        (``compute_global_heat_maps`` gives all of them from one call)."""
+        (``compute_global_heat_maps`` gives all of them from one call).  ``time_bin`` (a trace with ``time_bins``): an int
+        selects one time window, a slice a range of them (their sums are added per key before the bicubic and the clamp: the map
+        of a generation that ran exactly those steps); ``None`` is the whole generation."""
         n = len(self.last_prompts)
         if prompt_idx is not None:
             prompt_idx = self._check_prompt_idx(prompt_idx)
+        rng = self._bin_range(time_bin)
         if n > 1:
             if prompt_idx is None:
                 raise ValueError(f'the last generation traced {n} prompts: pass prompt_idx, or use compute_global_heat_maps() '
@@ -222,16 +336,19 @@ class DiffusionHeatMapHooker(AggregateHooker):
             prompts = list(self.last_prompts)
             if prompt is not None:
                 prompts[prompt_idx] = prompt                              # labels AND crops, as on one prompt
-            maps = self.compute_global_heat_maps(factors=factors, head_idx=head_idx, layer_idx=layer_idx, prompts=prompts)[prompt_idx]
+            maps = self.compute_global_heat_maps(factors=factors, head_idx=head_idx, layer_idx=layer_idx, prompts=prompts,
+                                                 time_bin=time_bin)[prompt_idx]
             if normalize:
                 self.engine.normalize_(maps.heat_maps)
             return maps
         if prompt is None:
             prompt = self.last_prompt
         n_rows = len(self.pipe.tokenizer.tokenize(prompt)) + 2                 # 1 for SOS and 1 for padding (trace.py:127)
+        self._check_bin_steps(rng)
         try:
             # the crop is handed to the finalize: rows nobody reads are not computed (daam_finalize n_rows, ABI v6)
-            maps = self.engine.global_heat_map(factors=factors, head_idx=head_idx, layer_idx=layer_idx, n_rows=n_rows)
+            kw = {} if rng is None else dict(bins=rng)
+            maps = self.engine.global_heat_map(factors=factors, head_idx=head_idx, layer_idx=layer_idx, n_rows=n_rows, **kw)
         except LookupError:
             if head_idx is not None or layer_idx is not None:
                 raise RuntimeError('No heat maps found for the given parameters.') from None

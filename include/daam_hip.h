@@ -103,6 +103,22 @@ DAAM_API int daam_layer_touch(DaamCtx* ctx, int layer, void* stream);
  * tensors live on unchanged.  The layer must be configured again before its next tap.  DAAM_E_STATE with taps pending. */
 DAAM_API int daam_layer_release(DaamCtx* ctx, int layer);
 
+/* ---- time windows ------------------------------------------------------------------------
+ * The reference adds every denoising step into one running sum per (layer, head) (heatmap.py:153-156) and leaves the time
+ * axis of DiffusionHeatMapHooker (time_idx / time_callback, trace.py:38,61-62) unused.  daam_ctx_set_time_bins splits it:
+ * window b covers the steps [first_step[b], first_step[b + 1]) (the last window is open-ended), 1 <= n_bins <= 64,
+ * first_step[0] == 0, strictly increasing (HOST array).  Call it before any layer is configured.  A layer's sums then
+ * become [n_bins][heads, tokens, side, side] (daam_layer_configure's caller-owned `acc` holds all windows, daam_layer_acc
+ * reports all of them) and every tap -- daam_tap_qk, daam_tap_qk_enqueue*, daam_attend with tap != 0, daam_tap_probs -- adds
+ * into the window of its step.  A tap's step is the number of taps of THAT layer since daam_reset (the t-th tapped call of a
+ * layer is denoising step t in diffusers' loop, with or without guidance; calls the reference's gate does not tap,
+ * trace.py:289, never reach the library).  The deferred launch is unchanged: one table entry per (window, layer) chain.
+ * On a binned context daam_layer_touch is DAAM_E_UNSUPPORTED, daam_finalize / daam_finalize_groups mean the whole generation
+ * (windows [0, n_bins)) and daam_finalize_prepare is DAAM_E_UNSUPPORTED when n_bins > 1. */
+DAAM_API int daam_ctx_set_time_bins(DaamCtx* ctx, int n_bins, const int32_t* first_step);
+/* taps counted for `layer` since the last daam_reset (any context) */
+DAAM_API int daam_tap_steps(DaamCtx* ctx, int layer, int* steps);
+
 /* RawHeatMapCollection.clear (heatmap.py:170-172; called from check_inputs, trace.py:179):
  * zero every running sum and drop any un-flushed deferred taps. */
 DAAM_API int daam_reset(DaamCtx* ctx, void* stream);
@@ -184,6 +200,18 @@ DAAM_API int daam_finalize_prepare(DaamCtx* ctx, const uint8_t* key_mask, int n_
  * MFMA x2 kernel behind DAAM_NO_PIPE_FINALIZE=1 serves a grouped call as one daam_finalize per group. */
 DAAM_API int daam_finalize_groups(DaamCtx* ctx, const int32_t* key_group, int n_groups, const int32_t* n_rows,
                                   float* out, size_t group_stride, void* stream);
+
+/* daam_finalize_groups with a window range per group: group g's map is computed from the sums of the windows
+ * [bin_begin[g], bin_end[g]) added per key BEFORE the bicubic and the clamp (trace.py:118-124; the clamp is not linear) -- what the
+ * reference computes from a generation that ran exactly those steps.  `key_group` indexes the key space of ONE window
+ * (daam_key_offset); group g takes the keys whose entry equals group_set[g] (HOST int32 per group, >= 0), or g when group_set is
+ * NULL -- so windows x prompts can share one prompt table (with group_set, keys of a set that no group takes are not selected).  bin_begin / bin_end / n_rows: HOST int32 per group,
+ * 0 <= bin_begin[g] < bin_end[g] <= n_bins (1 on an un-binned context).  out / group_stride / rows as daam_finalize_groups.
+ * Groups that each span one window run the grouped class kernels on that window's planes; otherwise one reduction launch adds the
+ * windows' planes (rows [0, n_rows[g]) only) into f32 scratch planes first. */
+DAAM_API int daam_finalize_bins(DaamCtx* ctx, const int32_t* key_group, int n_groups, const int32_t* group_set,
+                                const int32_t* bin_begin, const int32_t* bin_end, const int32_t* n_rows, float* out,
+                                size_t group_stride, void* stream);
 
 /* trace.py:129-130: maps[:n_rows] / (maps[1:n_rows-1].sum(0) + 1e-6), in place on the first
  * n_rows planes of `maps` [*, side, side] fp32. */
