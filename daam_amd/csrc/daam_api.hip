@@ -38,6 +38,8 @@ bool tap_slab_supported(int in_dtype, int batch, int heads, int head_dim, int hw
 int tap_slab_heads(int head_dim);
 int tap_slab_tile_pixels();
 hipError_t launch_tap_slab(const TapLaunch&, int acc_dtype, int fast_exp, hipStream_t, int*, int*);
+int tap_pair_tile_pixels();
+hipError_t launch_tap_pair(const TapLaunch&, int fast_exp, hipStream_t, int*, int*);
 
 hipError_t launch_tap_probs(const ProbsLaunch&, int, int, hipStream_t, int*, int*);
 hipError_t launch_finalize(const FinLaunch&, int, hipStream_t, int*, int*);
@@ -290,6 +292,7 @@ struct DaamCtx {
     int force_generic = 0;
     int fast_exp = 0;
     int no_d64 = 0;
+    int no_tap_pair = 0;
     int slab_tail_pct = 25;           // DAAM_SLAB_TAIL: percent of a head_dim-40 layer's pixels the slab kernel takes in 16-pixel tiles at the end of the launch
                                       // (SD-v1.5, alternating on one box: 0 -> 2390, 25 -> 2415, 50 -> 2316, 100 -> 2204 maps/s: half-size units cost K traffic)
     int tap_slab = 1;                 // tap_slab_kernel (daam_tap_slab.hip): deferred fp16 layers of head_dim 40 / 80 / 160 in 640-byte slabs of adjacent heads
@@ -449,7 +452,7 @@ static hipError_t ensure_aux(DaamCtx* c)
 static const char* tap_kernel_name(int kd)
 {
     return (kd == 65 || kd == 66) ? "tap_d64_kernel" : (kd == 67 || kd == 69) ? "tap_wide_kernel" : kd == 70 ? "tap_chunk_kernel"
-           : kd == 71 ? "tap_slab_kernel" : kd ? "tap_mfma_kernel" : "tap_generic_kernel";
+           : kd == 71 ? "tap_slab_kernel" : kd == 72 ? "tap_pair_kernel" : kd ? "tap_mfma_kernel" : "tap_generic_kernel";
 }
 static const char* dtype_name(int dt) { return dt == DAAM_F32 ? "f32" : dt == DAAM_BF16 ? "bf16" : "f16"; }
 
@@ -511,6 +514,8 @@ int daam_ctx_create(int max_layers, int tokens, int out_side, int acc_dtype, Daa
     c->tap_slab = !(tsl && tsl[0] == '0');
     const char* tck = getenv("DAAM_TAP_CHUNKED");           // daam_tap_chunk.hip: unset = launches that mix head dims, 1 = always, 0 = never
     c->tap_chunked = !tck || !tck[0] ? 2 : tck[0] == '1' ? 1 : tck[0] == '0' ? 0 : 2;
+    const char* ntp = getenv("DAAM_TAP_PAIR");              // 1: chains that share Q pair up on tap_pair_kernel; default: separate chains
+    c->no_tap_pair = !(ntp && ntp[0] == '1');
 
     // softmax flavour of the MFMA tap: fast (default; exponent by one mixed-precision FMA, ~1e-6 relative,
     // same deviation class as the f32 summation order of q.k -- DESIGN.md section 3.1) or compensated
@@ -1078,9 +1083,42 @@ int daam_tap_flush(DaamCtx* c, void* stream)
             if (ok) kind[i] = 71;
         }
     }
+    // Chains that read the same recorded Q (probes): head_dim-64 fp16 chains with fp16 sums pair up on tap_pair_kernel -- chain A
+    // any such chain, chain B one whose K is the same pointer at every step (a probe); in recorded order: generation + probe 0, probe 1 +
+    // probe 2, ...  The partner's kind becomes -1 (it rides with its chain A).  Unpaired chains keep their kernel.  Only with DAAM_TAP_PAIR=1:
+    // measured slower than separate chains for one and two probes, 4 % faster for four, so separate chains are the default.
+    std::vector<int> partner(order.size(), -1);
+    if (!c->no_tap_pair && !c->no_w8 && in_dtype == DAAM_F16 && c->acc_dtype == DAAM_F16) {
+        auto fixed_k = [&](size_t i) {
+            for (const Pending* p : per[i]) if (p->k != per[i][0]->k) return false;
+            return true;
+        };
+        auto same_q = [&](size_t a, size_t b) {
+            if (per[a].size() != per[b].size()) return false;
+            const DaamQKDesc &x = per[a][0]->d, &y = per[b][0]->d;
+            if (x.head_dim != 64 || y.head_dim != 64 || x.hw != y.hw || x.heads != y.heads || x.batch != y.batch ||
+                x.q_stride_b != y.q_stride_b || x.q_stride_h != y.q_stride_h || x.q_stride_p != y.q_stride_p ||
+                x.k_stride_h != y.k_stride_h || x.k_stride_t != y.k_stride_t || x.scale != y.scale || x.round_logits != y.round_logits ||
+                c->layers[order[a]].heads != c->layers[order[b]].heads)
+                return false;
+            for (size_t st = 0; st < per[a].size(); ++st) if (per[a][st]->q != per[b][st]->q) return false;
+            return true;
+        };
+        for (size_t a = 0; a < order.size(); ++a) {
+            if (kind[a] != 65 || partner[a] >= 0) continue;
+            for (size_t b = a + 1; b < order.size(); ++b) {
+                if (kind[b] != 65 || partner[b] >= 0 || !fixed_k(b) || !same_q(a, b)) continue;
+                partner[a] = (int)b;
+                partner[b] = (int)a;
+                kind[a] = 72;
+                kind[b] = -1;
+                break;
+            }
+        }
+    }
     std::vector<int> kinds;
     for (int kd : kind)
-        if (std::find(kinds.begin(), kinds.end(), kd) == kinds.end()) kinds.push_back(kd);
+        if (kd >= 0 && std::find(kinds.begin(), kinds.end(), kd) == kinds.end()) kinds.push_back(kd);
     int rc = 0;
     int grid_total = 0;
     // pass 1: the tables of every kernel kind -> ring -> device (all on the caller's stream)
@@ -1089,8 +1127,8 @@ int daam_tap_flush(DaamCtx* c, void* stream)
     for (int kd : kinds) {
         size_t n_layers = 0, n_ptrs = 0;
         for (size_t i = 0; i < order.size(); ++i)
-            if (kind[i] == kd) { ++n_layers; n_ptrs += per[i].size(); }
-        int tile = kd == 71 ? tap_slab_tile_pixels() : kd ? tap_mfma_tile_pixels() : kTapPixels;
+            if (kind[i] == kd) { ++n_layers; n_ptrs += per[i].size() * (kd == 72 ? 2 : 1); }
+        int tile = kd == 72 ? tap_pair_tile_pixels() : kd == 71 ? tap_slab_tile_pixels() : kd ? tap_mfma_tile_pixels() : kTapPixels;
         bool w8 = false;
         if ((kd == 65 || kd == 66) && !c->no_w8) {
             // head_dim-64 launches with fp16 Q / K and fp16 sums: 256-pixel tiles on eight-wave workgroups (one K tile for twice the pixels)
@@ -1129,7 +1167,8 @@ int daam_tap_flush(DaamCtx* c, void* stream)
         }
         if (kd == 71) std::stable_sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.rank < b.rank; });
         n_layers = ents.size();
-        const size_t bytes_layers = n_layers * sizeof(TapLayer), bytes = bytes_layers + n_ptrs * sizeof(TapPtr);
+        // tap_pair_kernel: the chain-B entries follow the chain-A entries, one per pair, in the same order
+        const size_t bytes_layers = n_layers * (kd == 72 ? 2 : 1) * sizeof(TapLayer), bytes = bytes_layers + n_ptrs * sizeof(TapPtr);
         size_t off = 0;
         hipError_t e = c->ring.alloc(bytes, &off);
         if (e != hipSuccess) { rc = fail((int)e, "upload ring: %s", hipGetErrorString(e)); break; }
@@ -1139,8 +1178,11 @@ int daam_tap_flush(DaamCtx* c, void* stream)
         std::vector<int> ptr_of(order.size(), -1);             // a layer's step pointers are written once, both of its entries point at them
         for (size_t i = 0; i < order.size(); ++i) {
             if (kind[i] != kd) continue;
-            ptr_of[i] = ptr;
-            for (auto* p : per[i]) { hp[ptr].q = p->q; hp[ptr].k = p->k; ++ptr; }
+            for (size_t m = 0; m < (kd == 72 ? 2u : 1u); ++m) {
+                const size_t ci = m ? (size_t)partner[i] : i;
+                ptr_of[ci] = ptr;
+                for (auto* p : per[ci]) { hp[ptr].q = p->q; hp[ptr].k = p->k; ++ptr; }
+            }
         }
         size_t j = 0;
         int seg_begin[kMaxSlabSegs + 1] = {0}, n_seg = 0;
@@ -1164,6 +1206,15 @@ int daam_tap_flush(DaamCtx* c, void* stream)
             max_d = std::max(max_d, v[0]->d.head_dim);
             min_d = std::min(min_d, v[0]->d.head_dim);
             all_round = all_round && v[0]->d.round_logits;
+            if (kd == 72) {                                  // chain B: its own sums, fresh flag, K batch stride and pointer pair
+                const size_t bi = (size_t)partner[en.i];
+                TapLayer& hb = hl[n_layers + j];
+                fill_layer(c, c->layers[order[bi]], per[bi][0]->d, en.tile, &hb);
+                hb.wg_begin = hl[j].wg_begin;
+                hb.n_steps = hl[j].n_steps;
+                hb.ptr_begin = ptr_of[bi];
+                hb.tiles_per_head = hl[j].tiles_per_head;
+            }
             ++j;
         }
         seg_begin[n_seg] = wg;
@@ -1266,6 +1317,7 @@ int daam_tap_flush(DaamCtx* c, void* stream)
                      : (pr.kd == 67 || pr.kd == 69) ? launch_tap_wide(pr.L, c->acc_dtype, pr.max_d, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
                      : pr.kd == 70 ? launch_tap_chunk(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d != pr.max_d, ks, &grid, &c->last_lds[0])
                      : pr.kd == 71 ? launch_tap_slab(pr.L, c->acc_dtype, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
+                     : pr.kd == 72 ? launch_tap_pair(pr.L, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
                      : pr.kd ? launch_tap_mfma(pr.L, c->acc_dtype, pr.max_d, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
                              : launch_tap_generic(pr.L, in_dtype, c->acc_dtype, pr.max_d, ks, &grid, &c->last_lds[0]);
         grid_total += grid;
@@ -1278,7 +1330,7 @@ int daam_tap_flush(DaamCtx* c, void* stream)
             ++n_side;
         }
         for (size_t i = 0; i < order.size(); ++i)
-            if (kind[i] == pr.kd) { c->layers[order[i]].dirty = true; c->layers[order[i]].zero_pending = false; }
+            if (kind[i] == pr.kd || (pr.kd == 72 && kind[i] == -1)) { c->layers[order[i]].dirty = true; c->layers[order[i]].zero_pending = false; }
     }
     // a flush that failed part-way may have announced side workgroups that never started: counter and target would disagree for
     // good (every later gate a silent no-op or a full timeout), so the context stops gating
@@ -1291,7 +1343,7 @@ int daam_tap_flush(DaamCtx* c, void* stream)
     c->last_grid[0] = grid_total;
     c->last_block[0] = 256;
     for (auto& pr : prepared)
-        if (pr.w8 || pr.kd == 71) c->last_block[0] = 512;
+        if (pr.w8 || pr.kd == 71 || pr.kd == 72) c->last_block[0] = 512;
     c->last_kernels[0] = launched_names;
     c->last_flush_kernels = (int)launch_order.size();
     c->last_flush_side = n_side;

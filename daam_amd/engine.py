@@ -123,6 +123,47 @@ def window_steps(time_bins: Sequence[int], layer_steps: Sequence[int]) -> List[i
     return out
 
 
+MAX_PROBES = 8
+
+
+def check_probes(probes, time_bins=None) -> Optional[Tuple[str, ...]]:
+    """``probes`` of ``trace``: ``None``, or 1 to 8 prompt strings whose keys the generation's queries are also tapped against.
+    ``time_bins`` together with probes is not supported (ValueError)."""
+    if probes is None:
+        return None
+    if isinstance(probes, (str, bytes)):
+        raise ValueError('probes must be a list of prompt strings, not one string')
+    try:
+        out = list(probes)
+    except TypeError:
+        raise ValueError('probes must be a list of prompt strings') from None
+    if not 1 <= len(out) <= MAX_PROBES:
+        raise ValueError(f'probes must hold 1 to {MAX_PROBES} prompts, got {len(out)}')
+    for p in out:
+        if not isinstance(p, str):
+            raise ValueError(f'probes entries must be strings, got {p!r}')
+    if time_bins is not None:
+        raise ValueError('probes cannot be combined with time_bins')
+    return tuple(out)
+
+
+def probe_key_groups(layout: Sequence[Tuple[int, int, int, int]], total: int, n_probes: int, n_prompts: int,
+                     factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None,
+                     layer_idx: Optional[int] = None) -> List[int]:
+    """``daam_finalize_groups``' key -> group table of the probe sums: group ``p * n_prompts + i`` is probe ``p`` seen by the
+    queries of prompt ``i``.  ``layout`` = ``(probe, generation layer, key offset of the probe's slot, kept heads)``; the keys of
+    a probe slot group by prompt exactly as the generation's keys do (``prompt_key_groups``), and the filters mean what they mean
+    there (``layer_idx`` names the generation's layer)."""
+    groups = [-1] * total
+    for p in range(n_probes):
+        part = prompt_key_groups([(layer, off, factor, heads) for q, layer, off, factor, heads in layout if q == p], total,
+                                 n_prompts, factors, head_idx, layer_idx)
+        for k, g in enumerate(part):
+            if g >= 0:
+                groups[k] = p * n_prompts + g
+    return groups
+
+
 def release_parked_contexts() -> None:
     """Destroy every parked context now (frees their sum buffers too).  Not called at interpreter exit on purpose:
     process teardown reclaims them, and no HIP call has to run while the runtime is shutting down."""
@@ -134,7 +175,8 @@ def release_parked_contexts() -> None:
 
 class HeatMapEngine:
     def __init__(self, n_layers: int, tokens: int = 77, out_side: int = 64, accumulate: str = 'exact',
-                 defer_steps: int = 0, defer_bytes: int = 32 << 30, reuse_context: bool = False, time_bins=None):
+                 defer_steps: int = 0, defer_bytes: int = 32 << 30, reuse_context: bool = False, time_bins=None,
+                 n_probes: int = 0):
         """``accumulate``: ``'exact'`` keeps the running sums in the pipeline dtype like the
         reference (fp16 sums on an fp16 pipeline, heatmap.py:156); ``'float32'`` is the
         accuracy mode.  ``defer_steps`` > 0 records Q/K pointers and taps ``defer_steps``
@@ -143,7 +185,11 @@ class HeatMapEngine:
         ``defer_bytes`` (both CFG halves count: 388 MB per SDXL-1024 step).  ``reuse_context``: ``close()`` parks
         the native context and the sum buffers for the next engine of the same geometry instead of destroying them
         (what ``trace`` asks for: one trace per generation is the normal use).  ``time_bins``: first step of each time window
-        (``check_time_bins``); every layer then keeps one running sum per window, ``[n_bins, heads, tokens, side, side]``."""
+        (``check_time_bins``); every layer then keeps one running sum per window, ``[n_bins, heads, tokens, side, side]``.
+        ``n_probes`` (0 to 8): every layer also keeps one running sum per probe, in the slot ``(1 + p) * n_layers + layer`` of the same
+        context (``probe_slot``), fed by the layer's queries against the probe's keys (``set_probe_keys``); one deferred launch taps
+        the generation and every probe.  Each probe costs one more set of sums (221 MB for SDXL-1024 with fp16 sums) and records no
+        Q / K of its own (``defer_bytes`` counts the generation's only)."""
         if accumulate not in ('exact', 'float32'):
             raise ValueError("accumulate must be 'exact' or 'float32'")
         self.lib = nat.load()
@@ -153,6 +199,13 @@ class HeatMapEngine:
         self.accumulate = accumulate
         self.time_bins = check_time_bins(time_bins)
         self.n_bins = len(self.time_bins) if self.time_bins is not None else 0
+        self.n_probes = int(n_probes)
+        if not 0 <= self.n_probes <= MAX_PROBES:
+            raise ValueError(f'n_probes must be 0 to {MAX_PROBES}, got {n_probes}')
+        if self.n_probes and self.time_bins is not None:
+            raise ValueError('probes cannot be combined with time_bins')
+        self._probe_k: Dict[int, torch.Tensor] = {}      # layer -> [n_probes, tokens, C] probe keys (to_k output)
+        self._probe_desc: Dict[bytes, 'nat.QKDesc'] = {}  # generation DaamQKDesc bytes -> the probes' descriptor (k_stride_b = 0)
         self.defer_steps = min(int(defer_steps), 64)     # the kernels stage at most 64 steps of pointers per launch
         self.defer_bytes = int(defer_bytes) if defer_bytes and defer_bytes > 0 else 1 << 62
         self.reuse_context = bool(reuse_context) and not os.environ.get('DAAM_NO_CTX_POOL')
@@ -239,7 +292,7 @@ class HeatMapEngine:
             return
         ctx = nat.c_void_p()
         with torch.cuda.device(self.device):
-            nat.check(self.lib.daam_ctx_create(self.n_layers, self.tokens, self.out_side,
+            nat.check(self.lib.daam_ctx_create(self.n_layers * (1 + self.n_probes), self.tokens, self.out_side,
                                                _DTYPE_CODE[self.acc_dtype],
                                                nat.byref(ctx)))
         if self.time_bins is not None:
@@ -252,7 +305,7 @@ class HeatMapEngine:
         self._sync_native()
 
     def _park_key(self) -> tuple:
-        return (str(self.device), self.n_layers, self.tokens, self.out_side, self.acc_dtype, self.time_bins)
+        return (str(self.device), self.n_layers, self.tokens, self.out_side, self.acc_dtype, self.time_bins, self.n_probes)
 
     def close(self) -> None:
         if self.ctx is not None:
@@ -302,11 +355,16 @@ class HeatMapEngine:
             # the reference would simply start a new key set / fail on a shape mismatch in `+`
             self.flush()
         shape = (heads, self.tokens, side, side) if self.time_bins is None else (self.n_bins, heads, self.tokens, side, side)
-        buf = torch.zeros(shape, dtype=self.acc_dtype, device=self.device)
-        nat.check(self.lib.daam_layer_configure(self.ctx, layer, heads, side, factor, buf.data_ptr()))
-        self.acc[layer] = buf
-        self.layer_info[layer] = (factor, heads, side)
+        for slot in [layer] + [self.probe_slot(p, layer) for p in range(self.n_probes)]:     # a probe's sums: the layer's geometry
+            buf = torch.zeros(shape, dtype=self.acc_dtype, device=self.device)
+            nat.check(self.lib.daam_layer_configure(self.ctx, slot, heads, side, factor, buf.data_ptr()))
+            self.acc[slot] = buf
+            self.layer_info[slot] = (factor, heads, side)
         self._mask_cache.clear()
+
+    def probe_slot(self, probe: int, layer: int) -> int:
+        """The context's layer slot that holds probe ``probe``'s sums of layer ``layer``."""
+        return (1 + probe) * self.n_layers + layer
 
     def _touch(self, layer: int) -> None:
         if not self._touched_flag[layer]:
@@ -551,6 +609,11 @@ class HeatMapEngine:
                 return False
             try:
                 stream, rec_stream = self._launch_stream()
+                if self.n_probes:
+                    arrays = [np.ctypeslib.as_array((t * n).from_address(a)) for t, a in
+                              ((ctypes.c_int32, la), (ctypes.c_uint64, qa), (ctypes.c_uint64, ka), (ctypes.c_uint64, da))]
+                    n, arrays = self._with_probes(*arrays)
+                    la, qa, ka, da = (a.ctypes.data for a in arrays)
                 nat.check(self.lib.daam_tap_qk_enqueue_many(self.ctx, n, la, qa, ka, da))
                 self._announce_then_launch(_before_launch, stream)
                 if rec_stream is not None:
@@ -578,6 +641,8 @@ class HeatMapEngine:
         dp = np.array(d_t, dtype=np.uint64)
         try:
             stream, rec_stream = self._launch_stream()
+            if self.n_probes:
+                n, (layers, qp, kp, dp) = self._with_probes(layers, qp, kp, dp)
             nat.check(self.lib.daam_tap_qk_enqueue_many(self.ctx, n, layers.ctypes.data, qp.ctypes.data, kp.ctypes.data,
                                                         dp.ctypes.data))
             self._announce_then_launch(_before_launch, stream)
@@ -609,6 +674,130 @@ class HeatMapEngine:
         self._cnt[:] = [0] * self.n_layers              # in place: tap_qk holds a reference across flush()
         if self._fast is not None:
             self._fast.drop()
+
+    # ---- probes: the generation's queries against the keys of other prompts -------------------------
+    def set_probe_keys(self, layer: int, keys: torch.Tensor) -> None:
+        """``keys`` [n_probes, tokens, heads*d]: ``to_k(norm_cross(E_p))`` of every probe for layer ``layer`` (computed once per
+        layer and trace by the processor; kept alive here until the engine closes)."""
+        if keys.dim() != 3 or keys.shape[0] != self.n_probes or keys.shape[1] != self.tokens:
+            raise ValueError(f'probe keys must be [{self.n_probes}, {self.tokens}, C], got {list(keys.shape)}')
+        if layer in self._probe_k:
+            self.flush()                                   # recorded taps still point at the old keys: launch them before those go
+        self._probe_k[layer] = keys.contiguous()
+
+    def _probe_desc_for(self, desc: 'nat.QKDesc') -> 'nat.QKDesc':
+        """The descriptor of the probes' chains for a generation call described by ``desc``: the same Q, the same key layout
+        with batch stride 0 (one probe key serves every kept batch entry)."""
+        raw = bytes(desc)
+        out = self._probe_desc.get(raw)
+        if out is None:
+            out = self._probe_desc[raw] = nat.QKDesc.from_buffer_copy(raw)
+            out.k_stride_b = 0
+        return out
+
+    def _probe_key_ptr(self, layer: int, probe: int) -> int:
+        keys = self._probe_k.get(layer)
+        if keys is None:
+            raise RuntimeError(f'daam_amd: layer {layer} was tapped before its probe keys were set')
+        return keys.data_ptr() + probe * keys.stride(0) * keys.element_size()
+
+    def _with_probes(self, layers: np.ndarray, qp: np.ndarray, kp: np.ndarray, dp: np.ndarray):
+        """The recorded generation taps followed by every probe's taps of the same calls (same Q, the probe's K, slot
+        ``probe_slot``): ``(n, [layers, q, k, desc])`` for ``daam_tap_qk_enqueue_many``."""
+        uniq, inv = np.unique(dp, return_inverse=True)
+        pdesc = np.array([ctypes.addressof(self._probe_desc_for(nat.QKDesc.from_address(int(a)))) for a in uniq], dtype=np.uint64)
+        out_l, out_q, out_k, out_d = [layers], [qp], [kp], [dp]
+        for p in range(self.n_probes):
+            ptr = np.zeros(self.n_layers, dtype=np.uint64)
+            for layer in np.unique(layers).tolist():
+                ptr[layer] = self._probe_key_ptr(layer, p)
+            out_l.append((layers + (1 + p) * self.n_layers).astype(np.int32))
+            out_q.append(qp)
+            out_k.append(ptr[layers])
+            out_d.append(pdesc[inv])
+        arrays = [np.ascontiguousarray(np.concatenate(a)) for a in (out_l, out_q, out_k, out_d)]
+        return len(arrays[0]), arrays
+
+    def tap_probes(self, layer: int, query: torch.Tensor, heads: int, scale: float, factor: int, round_logits: bool = True) -> None:
+        """Immediate probe taps of one call (``daam_tap_qk`` per probe on ``query`` [B, hw, heads*d], the raw ``to_q`` output):
+        the route of ``defer_steps=0``, ``DAAM_NO_ATTEND`` without deferral and the materialised processor.  The generation's own tap
+        of the call comes first (it configures the layer); a probe never sees the generation's attention mask."""
+        if self.defer_steps:
+            # an immediate tap needs an empty queue.  On the materialised route of a deferred trace the generation's own tap_probs of
+            # this call has just flushed it (daam_tap_probs takes no pending taps), so this adds no launch of its own
+            self.flush()
+        query = query if query.is_contiguous() else query.contiguous()
+        b, hw, c = query.shape
+        d = c // heads
+        bh = b * heads
+        self._ensure_layer(layer, bh - bh // 2, int(math.sqrt(hw)), factor)
+        desc = nat.QKDesc(in_dtype=_DTYPE_CODE[query.dtype], batch=b, heads=heads, hw=hw, tokens=self.tokens, head_dim=d,
+                          round_logits=1 if round_logits else 0, scale=float(scale),
+                          q_stride_b=hw * c, q_stride_h=d, q_stride_p=c,
+                          k_stride_b=0, k_stride_h=d, k_stride_t=c)
+        stream = self.stream
+        for p in range(self.n_probes):
+            nat.check(self.lib.daam_tap_qk(self.ctx, self.probe_slot(p, layer), query.data_ptr(), self._probe_key_ptr(layer, p),
+                                           nat.byref(desc), stream))
+
+    def probe_items(self, probe: int) -> Dict[Key, torch.Tensor]:
+        """``{(factor, layer, head): probe ``probe``'s running sum [tokens, h, w]}`` -- views of the live buffers, with the lifetime
+        rules of ``items``."""
+        if not 0 <= probe < self.n_probes:
+            raise IndexError(f'probe {probe} out of range: the trace has {self.n_probes} probe(s)')
+        self.flush()
+        self._views_out = True
+        out: Dict[Key, torch.Tensor] = {}
+        for layer in list(self.touched):
+            factor, heads, _ = self.layer_info[layer]
+            buf = self.acc[self.probe_slot(probe, layer)]
+            for h in range(heads):
+                out[(factor, layer, h)] = buf[h]
+        return out
+
+    def probe_heat_maps(self, probes: Sequence[int], n_prompts: int, n_rows: Sequence[int], factors: Optional[Sequence[int]] = None,
+                        head_idx: Optional[int] = None, layer_idx: Optional[int] = None) -> torch.Tensor:
+        """Global heat maps of the probes ``probes`` x ``n_prompts`` prompts from ONE ``daam_finalize_groups`` call (groups of 64 per
+        call beyond that): returns ``[len(probes) * n_prompts, tokens, x, x]`` fp32, group ``i * n_prompts + j`` = probe ``probes[i]``
+        seen by prompt ``j``, whose rows ``[0, n_rows[i])`` are its map."""
+        if self.ctx is None or not self.touched:
+            raise LookupError('no heat maps')
+        if len(n_rows) != len(probes):
+            raise ValueError(f'{len(n_rows)} row counts for {len(probes)} probes')
+        sel = ('probes', tuple(probes), n_prompts, None if factors is None else tuple(sorted(set(factors))), head_idx, layer_idx,
+               tuple(self.touched), len(self.layer_info))
+        cached = self._mask_cache.get(sel)
+        n_groups = len(probes) * n_prompts
+        if cached is None:
+            total = ctypes.c_int()
+            nat.check(self.lib.daam_key_offset(self.ctx, 0, None, ctypes.byref(total)))
+            layout = []
+            for i, p in enumerate(probes):
+                for layer in self.touched:
+                    factor, heads, _ = self.layer_info[layer]
+                    off = ctypes.c_int()
+                    nat.check(self.lib.daam_key_offset(self.ctx, self.probe_slot(p, layer), ctypes.byref(off), None))
+                    layout.append((i, layer, off.value, factor, heads))
+            table = probe_key_groups(layout, total.value, len(probes), n_prompts, factors, head_idx, layer_idx)
+            counts = [table.count(g) for g in range(n_groups)]
+            if len(self._mask_cache) > 64:
+                self._mask_cache.clear()
+            cached = self._mask_cache[sel] = (table, counts)
+        table, counts = cached
+        if min(counts) == 0:
+            self.flush()
+            raise LookupError('no heat maps')
+        rows = [max(1, min(int(n_rows[g // n_prompts]), self.tokens)) for g in range(n_groups)]
+        self.flush()
+        plane = self.tokens * self.out_side * self.out_side
+        out = torch.empty(n_groups, self.tokens, self.out_side, self.out_side, dtype=torch.float32, device=self.device)
+        i32 = ctypes.c_int32
+        for start in range(0, n_groups, 64):                    # the library takes at most 64 groups per call
+            n = min(64, n_groups - start)
+            part = [g - start if start <= g < start + n else -1 for g in table]
+            nat.check(self.lib.daam_finalize_groups(self.ctx, (i32 * len(part))(*part), n, (i32 * n)(*rows[start:start + n]),
+                                                    out.data_ptr() + start * plane * 4, plane, self.stream))
+        return out
 
     def tap_probs(self, layer: int, probs: torch.Tensor, factor: int) -> None:
         """``probs`` [B*H, hw, tokens] as returned by ``get_attention_scores`` (trace.py:276)."""

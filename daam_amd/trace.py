@@ -25,7 +25,7 @@ from typing import Any, List, Optional, Type, Union
 import torch
 import torch.nn.functional as F
 
-from .engine import HeatMapEngine, check_time_bins
+from .engine import HeatMapEngine, check_probes, check_time_bins
 from .heatmap import GlobalHeatMap, RawHeatMapCollection
 from .hook import AggregateHooker, ObjectHooker, UNetCrossAttentionLocator
 from .utils import cache_dir
@@ -65,10 +65,36 @@ def _default_defer_bytes(pipeline=None) -> int:
     return budget
 
 
+def _probe_embeddings(pipeline, probes, probe_embeds=None) -> torch.Tensor:
+    """``[P, 77, C]`` conditional prompt embeddings of the probes: ``probe_embeds`` as given, else each probe encoded once by the
+    pipeline's own ``encode_prompt`` (element ``[0]`` of what it returns: SD's 2-tuple and SDXL's 4-tuple both start with the
+    conditional ``prompt_embeds``, SDXL's the concatenated 2048-wide embedding that ``attn2`` sees)."""
+    if probe_embeds is not None:
+        if not torch.is_tensor(probe_embeds) or probe_embeds.dim() != 3 or probe_embeds.shape[0] != len(probes) \
+                or probe_embeds.shape[1] != 77:
+            shape = list(probe_embeds.shape) if torch.is_tensor(probe_embeds) else type(probe_embeds).__name__
+            raise ValueError(f'probe_embeds must be a [{len(probes)}, 77, C] tensor (one row set per probe), got {shape}')
+        return probe_embeds
+    encode = getattr(pipeline, 'encode_prompt', None)
+    if encode is None:
+        raise ValueError('the pipeline has no encode_prompt: pass probe_embeds')
+    device = getattr(pipeline, '_execution_device', None) or getattr(pipeline, 'device', None)
+    rows = []
+    with torch.no_grad():
+        for p in probes:
+            out = encode(p, device=device, num_images_per_prompt=1, do_classifier_free_guidance=False)
+            emb = out[0] if isinstance(out, (tuple, list)) else out
+            if not torch.is_tensor(emb) or emb.dim() != 3 or emb.shape[0] != 1 or emb.shape[1] != 77:
+                raise ValueError(f'encode_prompt({p!r}) gave no [1, 77, C] prompt embedding')
+            rows.append(emb)
+    return torch.cat(rows)
+
+
 class DiffusionHeatMapHooker(AggregateHooker):
     def __init__(self, pipeline, low_memory: bool = False, load_heads: bool = False, save_heads: bool = False,
                  data_dir: Optional[str] = None, *, accumulate: str = 'exact', tap: str = 'qk',
-                 defer_steps: Optional[int] = None, batch_prompts: bool = False, time_bins=None):
+                 defer_steps: Optional[int] = None, batch_prompts: bool = False, time_bins=None, probes=None,
+                 probe_embeds: Optional[torch.Tensor] = None):
         """Positional arguments as in the reference (trace.py:23-30).  Keyword-only extras:
         ``accumulate`` = ``'exact'`` (running sums in the pipeline dtype, like the reference) or
         ``'float32'``; ``tap`` = ``'qk'`` (fused, default) or ``'probs'`` (materialised
@@ -85,10 +111,23 @@ class DiffusionHeatMapHooker(AggregateHooker):
         call's step is the number of tapped calls of its layer since the generation began.  ``compute_global_heat_map(time_bin=)``
         then selects a window or a range of them, ``compute_time_heat_maps`` gives one map per window; ``None`` keeps one sum
         over the whole generation (the reference's running sum, which the reference's unused ``time_idx`` never splits,
-        trace.py:38,61-62)."""
+        trace.py:38,61-62).
+        ``probes`` (1 to 8 prompt strings; open-vocabulary heat maps): every tapped call's conditional-half queries are also
+        attended to the keys ``to_k(norm_cross(E_p))`` of each probe prompt -- with the generation's rounding points and sum dtype,
+        never its attention mask -- into sums of their own; the generation itself is unchanged.  ``E_p`` is
+        ``pipe.encode_prompt(p, device=..., num_images_per_prompt=1, do_classifier_free_guidance=False)[0]``, encoded once here;
+        ``probe_embeds`` ([P, 77, C]) replaces that encoding (the strings still name the tokens).  ``compute_probe_heat_map(p)`` /
+        ``compute_probe_heat_maps()`` / ``raw_probe_heat_maps(p)`` read them.  Each probe holds one more set of running sums (221 MB
+        for SDXL-1024 with fp16 sums).  Not with ``time_bins``, ``save_heads`` or ``load_heads`` (ValueError)."""
         if tap not in ('qk', 'probs'):
             raise ValueError("tap must be 'qk' or 'probs'")
+        self.probes = check_probes(probes, time_bins)
         self.time_bins = check_time_bins(time_bins)
+        if self.probes is not None and (save_heads or load_heads):
+            raise ValueError('probes cannot be combined with save_heads / load_heads')
+        self.probe_embeds = None if self.probes is None else _probe_embeddings(pipeline, self.probes, probe_embeds)
+        if self.probes is None and probe_embeds is not None:
+            raise ValueError('probe_embeds needs probes (the strings that name its tokens)')
         h = pipeline.unet.config.sample_size * pipeline.vae_scale_factor
         self.latent_hw = 4096 if h == 512 or h == 1024 else 9216          # trace.py:32-33
         locate_middle = load_heads or save_heads
@@ -98,7 +137,8 @@ class DiffusionHeatMapHooker(AggregateHooker):
         self.engine = HeatMapEngine(max(1, len(modules_found)), tokens=77, out_side=int(math.sqrt(self.latent_hw)),
                                     accumulate=accumulate,
                                     defer_steps=_default_defer() if defer_steps is None else defer_steps,
-                                    defer_bytes=_default_defer_bytes(pipeline), reuse_context=True, time_bins=self.time_bins)
+                                    defer_bytes=_default_defer_bytes(pipeline), reuse_context=True, time_bins=self.time_bins,
+                                    n_probes=len(self.probes) if self.probes is not None else 0)
         self.all_heat_maps = RawHeatMapCollection(self.engine)
         self.last_prompt: str = ''
         self.last_prompts: List[str] = []
@@ -359,6 +399,67 @@ class DiffusionHeatMapHooker(AggregateHooker):
             maps = self.engine.normalize_(maps)
         return GlobalHeatMap(self.pipe.tokenizer, prompt, maps)
 
+    # -- probes (open-vocabulary heat maps) ----------------------------------------------------------
+    def _check_probe(self, probe) -> int:
+        n = len(self.probes) if self.probes is not None else 0
+        if n == 0:
+            raise ValueError('the trace has no probes: pass probes=[...] to trace()')
+        if isinstance(probe, bool) or not isinstance(probe, numbers.Integral) or not -n <= int(probe) < n:
+            raise ValueError(f'probe {probe!r} out of range: the trace has {n} probe(s)')
+        return int(probe) % n
+
+    def raw_probe_heat_maps(self, probe: int) -> dict:
+        """``{(factor, layer, head): running sum [77, h, w]}`` of probe ``probe`` -- the layout of ``raw_heat_maps`` / ``all_heat_maps``,
+        zero-copy views of the live sums."""
+        return self.engine.probe_items(self._check_probe(probe))
+
+    def _probe_maps(self, probes: List[int], factors, head_idx, layer_idx, normalize, prompt_idx):
+        """``[probe][prompt] -> GlobalHeatMap`` for ``probes``, from one grouped finalize (groups = probes x prompts)."""
+        n = max(1, len(self.last_prompts))
+        if prompt_idx is not None:
+            prompt_idx = self._check_prompt_idx(prompt_idx)
+        texts = [self.probes[p] for p in probes]
+        n_rows = [len(self.pipe.tokenizer.tokenize(t)) + 2 for t in texts]
+        try:
+            maps = self.engine.probe_heat_maps(probes, n, n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx)
+        except LookupError:
+            if head_idx is not None or layer_idx is not None:
+                raise RuntimeError('No heat maps found for the given parameters.') from None
+            raise RuntimeError('No heat maps found. Did you forget to call `with trace(...)` during generation?') from None
+        out = []
+        for i, (text, rows) in enumerate(zip(texts, n_rows)):
+            row = []
+            for j in range(n):
+                if prompt_idx is not None and j != prompt_idx:
+                    continue
+                m = maps[i * n + j, :rows]
+                if normalize:
+                    m = self.engine.normalize_(m)
+                row.append(GlobalHeatMap(self.pipe.tokenizer, text, m))
+            out.append(row)
+        return out
+
+    def compute_probe_heat_map(self, probe: int, factors=None, head_idx=None, layer_idx=None, normalize=False,
+                               prompt_idx: Optional[int] = None) -> GlobalHeatMap:
+        """The global heat map of probe ``probe`` over its own ``len(tokenize(probe)) + 2`` token rows: the generation's queries
+        attended to the probe's keys, then the finalize of ``compute_global_heat_map`` (bicubic, clamp, mean over the selected keys;
+        ``factors`` / ``head_idx`` / ``layer_idx`` / ``normalize`` as there).  After a batched generation of N > 1 prompts,
+        ``prompt_idx`` picks the prompt whose queries are used."""
+        p = self._check_probe(probe)
+        if len(self.last_prompts) > 1 and prompt_idx is None:
+            raise ValueError(f'the last generation traced {len(self.last_prompts)} prompts: pass prompt_idx')
+        return self._probe_maps([p], factors, head_idx, layer_idx, normalize, prompt_idx)[0][0]
+
+    def compute_probe_heat_maps(self, factors=None, head_idx=None, layer_idx=None, normalize=False,
+                                prompt_idx: Optional[int] = None) -> list:
+        """One ``GlobalHeatMap`` per probe from ONE grouped finalize (``daam_finalize_groups``, groups = probes x prompts).  After a
+        batched generation of N > 1 prompts without ``prompt_idx``, each entry is the list of the N prompts' maps."""
+        self._check_probe(0)
+        maps = self._probe_maps(list(range(len(self.probes))), factors, head_idx, layer_idx, normalize, prompt_idx)
+        if len(self.last_prompts) > 1 and prompt_idx is None:
+            return maps
+        return [row[0] for row in maps]
+
 
 class _CallInterceptor(ObjectHooker):
     """Wraps methods of one pipeline-side object.  ``WRAPS`` lists ``(attribute, handler name, strict)``;
@@ -473,10 +574,57 @@ class UNetCrossAttentionHooker(ObjectHooker):
         # attention itself on the library's kernel (fp16, 77 keys, head_dim a multiple of 8 up to 160), with the tap fused in on an immediate
         # trace; DAAM_NO_ATTEND=1 keeps the framework's fused SDPA for the model's output
         self._attend = None if os.environ.get('DAAM_NO_ATTEND') else self.trace.engine.attend
+        # probes: the fused route gets its probe-tapping form here, once; without probes every call runs exactly as before
+        self._probe_embeds = self.trace.probe_embeds
+        self._probe_key_dtype = None
+        if self._probe_embeds is not None:
+            self._fused = self._fused_probes
         attn.set_processor(self)
 
     def _unhook_impl(self):
         self.module.set_processor(self.original_processor)
+        self.__dict__.pop('_fused', None)
+
+    def _ensure_probe_keys(self, attn, like: torch.Tensor) -> None:
+        """The probes' keys of this layer, ``to_k(norm_cross(E_p))`` (batch = the probes), computed on the layer's first tapped call
+        of the trace (again only if the pipeline's dtype changes)."""
+        if self._probe_key_dtype is like.dtype:
+            return
+        emb = self._probe_embeds.to(device=like.device, dtype=like.dtype)
+        with torch.no_grad():
+            ctx = emb if attn.norm_cross is None else attn.norm_cross(emb)
+            keys = attn.to_k(ctx)
+        self.trace.engine.set_probe_keys(self.layer_idx, keys)
+        self._probe_key_dtype = like.dtype
+
+    def _fused_probes(self, attn, hidden_states, context):
+        """``_fused`` on a trace with probes: the probe keys exist before the call is recorded; a deferred launch adds each probe's
+        chain of the recorded calls itself, an immediate trace taps the probes right after the generation."""
+        query, key, value = attn.to_q(hidden_states), attn.to_k(context), attn.to_v(context)
+        self.trace._gen_idx += 1
+        batch, positions, channels = query.shape
+        factor = self._factor(positions)
+        tapped = factor != 8 and key.shape[1] == self.context_size          # trace.py:289
+        if tapped:
+            if self.trace._batch_unchecked:
+                self.trace._check_batch(batch)
+            self._ensure_probe_keys(attn, key)
+        engine = self.trace.engine
+        out = None
+        if self._attend is not None and key.shape[1] == self.context_size:
+            out = self._attend(self.layer_idx, query, key, value, self._heads, self._scale, factor, self._round_logits, tapped)
+        if out is None and tapped:
+            self._tap_qk(self.layer_idx, query, key, self._heads, self._scale, factor, self._round_logits)
+        if tapped and not engine.defer_steps:
+            engine.tap_probes(self.layer_idx, query, self._heads, self._scale, factor, self._round_logits)
+        if out is not None:
+            return out
+        heads = self._heads
+        head_dim = channels // heads
+        out = F.scaled_dot_product_attention(query.view(batch, -1, heads, head_dim).transpose(1, 2),
+                                             key.view(batch, -1, heads, head_dim).transpose(1, 2),
+                                             value.view(batch, -1, heads, head_dim).transpose(1, 2), scale=self._scale)
+        return out.transpose(1, 2).reshape(batch, -1, channels)
 
     @property
     def num_heat_maps(self):
@@ -526,8 +674,8 @@ class UNetCrossAttentionHooker(ObjectHooker):
         return out.transpose(1, 2).reshape(batch, -1, channels)
 
     def _materialised(self, attn, hidden_states, context, attention_mask):
-        query, key, value = (attn.head_to_batch_dim(t)
-                             for t in (attn.to_q(hidden_states), attn.to_k(context), attn.to_v(context)))
+        raw_query = attn.to_q(hidden_states)
+        query, key, value = (attn.head_to_batch_dim(t) for t in (raw_query, attn.to_k(context), attn.to_v(context)))
         probs = attn.get_attention_scores(query, key, attention_mask)
         if self.save_heads:
             self._save_attn(probs)
@@ -539,6 +687,10 @@ class UNetCrossAttentionHooker(ObjectHooker):
             if self.trace._batch_unchecked:
                 self.trace._check_batch(probs.shape[0] // attn.heads)
             self.trace.engine.tap_probs(self.layer_idx, probs, factor)
+            if self._probe_embeds is not None:                             # the probes: daam_tap_qk on the same Q, no mask
+                self._ensure_probe_keys(attn, raw_query)
+                self.trace.engine.tap_probes(self.layer_idx, raw_query, attn.heads, attn.scale, factor,
+                                             not getattr(attn, 'upcast_attention', False))
         return attn.batch_to_head_dim(torch.bmm(probs, value))
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, **_ignored):
