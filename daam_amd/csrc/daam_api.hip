@@ -1,9 +1,7 @@
 // Host side of libdaam_hip.so: the C ABI declared in include/daam_hip.h.
 // Owns no activations; owns (optionally) the running sums, the bicubic tap tables and a
 // small pinned upload ring for the per-launch device tables.
-#include "daam_types.h"
-#include "daam_fin_bins.h"
-#include "../../include/daam_hip.h"
+#include "daam_ctx.h"
 
 #include <algorithm>
 #include <cmath>
@@ -11,72 +9,12 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <string>
 #include <vector>
 
-namespace daam {
-hipError_t launch_tap_generic(const TapLaunch&, int, int, int, hipStream_t, int*, int*);
-hipError_t launch_tap_mfma(const TapLaunch&, int acc_dtype, int max_d, int fast_exp, hipStream_t, int*, int*);
-bool tap_mfma_supported(int in_dtype, int head_dim, int tokens, int hw, int64_t q_sp, int64_t k_st,
-                        int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh);
-int tap_mfma_tile_pixels();
-int tap_mfma_ksteps(int head_dim);
-int tap_mfma_max_steps();
-hipError_t launch_tap_d64(const TapLaunch&, int in_dtype, int acc_dtype, int fast_exp, int full64, int waves8, hipStream_t, int*, int*);
-int tap_d64_tile_pixels(int in_dtype, int acc_dtype, int full64);
-bool tap_wide_supported(int in_dtype, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
-                        const void* q, const void* k);
-hipError_t launch_tap_wide(const TapLaunch&, int acc_dtype, int max_head_dim, int fast_exp, hipStream_t, int*, int*);
-bool tap_d64_supported(int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
-                       const void* q, const void* k);
-bool tap_chunk_supported(int in_dtype, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
-                         int64_t q_extent, const void* q, const void* k);
-hipError_t launch_tap_chunk(const TapLaunch&, int in_dtype, int acc_dtype, int fast_exp, int interleave, hipStream_t, int*, int*);
-bool tap_slab_supported(int in_dtype, int batch, int heads, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb,
-                        int64_t k_sh, int64_t q_extent, const void* q, const void* k);
-int tap_slab_heads(int head_dim);
-int tap_slab_tile_pixels();
-hipError_t launch_tap_slab(const TapLaunch&, int acc_dtype, int fast_exp, hipStream_t, int*, int*);
-int tap_pair_tile_pixels();
-hipError_t launch_tap_pair(const TapLaunch&, int fast_exp, hipStream_t, int*, int*);
-
-hipError_t launch_tap_probs(const ProbsLaunch&, int, int, hipStream_t, int*, int*);
-hipError_t launch_finalize(const FinLaunch&, int, hipStream_t, int*, int*);
-hipError_t launch_upload(void* dst, const void* src_host_mapped, size_t bytes, void* zero, size_t zero_bytes, hipStream_t);
-hipError_t launch_finalize_up32_same(const FinLaunch& up, const FinLaunch& same, hipStream_t, int*);
-hipError_t launch_finalize_up32_pipe(const FinPipeLaunch&, int acc_dtype, hipStream_t, int*);
-int finalize_pipe_ring(int acc_dtype);
-hipError_t launch_finalize_same(const FinLaunch&, int, hipStream_t, int*);
-hipError_t launch_finalize_up(const FinLaunch&, int side, int, int mfma_ok, hipStream_t, int*);
-bool finalize_up_supported(int side, int out_side);
-bool finalize_down2_supported(int side, int out_side);
-hipError_t launch_finalize_down2(const FinLaunch&, int, hipStream_t, int*);
-hipError_t launch_zero_groups(float* out, size_t stride, int plane, const int* rows, int n_groups, hipStream_t);
-hipError_t launch_finalize_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*, int*);
-hipError_t launch_finalize_same_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
-hipError_t launch_finalize_up_grouped(const FinGroupLaunch&, int n_groups, int side, int acc_dtype, hipStream_t, int*);
-hipError_t launch_finalize_down2_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
-hipError_t launch_finalize_up32_pipe_grouped(const FinPipeGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
-hipError_t launch_normalize(float*, int, int, hipStream_t);
-hipError_t launch_mask_overlap(const float*, int, int, const float*, int, int, int, float*, hipStream_t);
-bool attend_d64_supported(int in_dtype, int head_dim, int tokens, const int64_t* strides, int n_strides, const void* const* ptrs, int n_ptrs);
-hipError_t launch_attend_d64(const AttendLaunch&, int in_dtype, int acc_dtype, int fast_exp, hipStream_t, int*, int*);
-hipError_t launch_clock_monitor(unsigned long long* samples, int n_samples, int period_us, hipStream_t);
-hipError_t launch_start_gate(const unsigned* counter, unsigned target, int timeout_us, unsigned* timeouts, hipStream_t);
-constexpr int kClockMaxSamples = 4096;
-hipError_t launch_word(const float*, int, const int32_t*, int, float*, float*, int, int, int, float, float*,
-                       hipStream_t);
-hipError_t launch_finalize_bin_sum(const BinSumLaunch&, int acc_dtype, hipStream_t);
-int bin_sum_elems_per_tile(int acc_dtype);
-}  // namespace daam
-
-using namespace daam;
-
 static thread_local std::string g_err;
 
-static int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-static int fail(int code, const char* fmt, ...)
+int fail(int code, const char* fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -86,235 +24,6 @@ static int fail(int code, const char* fmt, ...)
     g_err = buf;
     return code;
 }
-
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess) return fail((int)_e, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
-namespace {
-
-// ---- pinned upload ring -----------------------------------------------------------------
-// alloc() hands out a pinned host region and its device twin; commit() copies it H2D on the
-// stream with a tiny copy KERNEL that reads the (device-mapped) pinned buffer - hipMemcpyAsync put a
-// ~0.2 ms cross-queue bubble between the copy and the consuming kernel - and, after the consuming
-// kernel has been enqueued, release() records an event so the region is only reused once that
-// kernel has run.  Wrap-around waits (hipEventSynchronize)
-// only if the GPU is more than one ring behind the host.
-struct Ring {
-    static constexpr size_t kBytes = 8u << 20;
-    char* host = nullptr;
-    char* host_dev = nullptr;         // device-side address of the pinned buffer
-    char* dev = nullptr;
-    size_t head = 0;                  // next free byte
-    struct Busy { size_t begin, end; hipEvent_t ev; };
-    std::deque<Busy> busy;
-    std::vector<hipEvent_t> pool;
-
-    hipError_t init() {
-        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), kBytes, hipHostMallocMapped);
-        if (e != hipSuccess) return e;
-        e = hipHostGetDevicePointer(reinterpret_cast<void**>(&host_dev), host, 0);
-        if (e != hipSuccess) return e;
-        return hipMalloc(reinterpret_cast<void**>(&dev), kBytes);
-    }
-    void destroy() {
-        for (auto& b : busy) { (void)hipEventSynchronize(b.ev); (void)hipEventDestroy(b.ev); }
-        for (auto ev : pool) (void)hipEventDestroy(ev);
-        busy.clear(); pool.clear();
-        if (host) (void)hipHostFree(host);
-        if (dev) (void)hipFree(dev);
-        host = dev = nullptr;
-    }
-    bool overlaps(size_t b, size_t e) const {
-        for (auto& x : busy) if (b < x.end && x.begin < e) return true;
-        return false;
-    }
-    hipError_t alloc(size_t bytes, size_t* off) {
-        bytes = (bytes + 255) & ~size_t(255);
-        if (bytes > kBytes) return hipErrorOutOfMemory;
-        if (head + bytes > kBytes) head = 0;
-        // retire finished regions; block on the oldest ones still overlapping the request
-        while (!busy.empty() && (hipEventQuery(busy.front().ev) == hipSuccess)) {
-            pool.push_back(busy.front().ev);
-            busy.pop_front();
-        }
-        while (overlaps(head, head + bytes)) {
-            hipError_t e = hipEventSynchronize(busy.front().ev);
-            if (e != hipSuccess) return e;
-            pool.push_back(busy.front().ev);
-            busy.pop_front();
-        }
-        *off = head;
-        head += bytes;
-        cur_begin = *off;
-        cur_end = head;
-        return hipSuccess;
-    }
-    size_t cur_begin = 0, cur_end = 0;
-    hipError_t commit(size_t off, size_t bytes, hipStream_t s, void* zero = nullptr, size_t zero_bytes = 0) {
-        return launch_upload(dev + off, host_dev + off, bytes, zero, zero_bytes, s);
-    }
-    hipError_t release_range(size_t begin, size_t end, hipStream_t s) {
-        cur_begin = begin;
-        cur_end = end;
-        return release(s);
-    }
-    hipError_t release(hipStream_t s) {
-        hipEvent_t ev;
-        if (!pool.empty()) { ev = pool.back(); pool.pop_back(); }
-        else {
-            hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e != hipSuccess) return e;
-        }
-        hipError_t e = hipEventRecord(ev, s);
-        if (e != hipSuccess) return e;
-        busy.push_back({cur_begin, cur_end, ev});
-        return hipSuccess;
-    }
-};
-
-struct Layer {
-    bool configured = false;
-    int heads = 0, side = 0, hw = 0, factor = 0;
-    void* acc = nullptr;
-    bool owned = false;
-    size_t bytes = 0;
-    int tab = -1;
-    bool dirty = false;      // tapped since the last reset (else the sums are known to be zero)
-    bool zero_pending = false;  // reset() was called but the buffer has not been cleared yet: the next
-                                // MFMA tap overwrites it (fresh), anything else clears it first
-};
-
-struct Pending {
-    int layer;
-    const void* q;
-    const void* k;
-    DaamQKDesc d;
-};
-
-constexpr int kMaxTabs = 16;
-constexpr int kMaxBins = 64;         // time windows of a binned context (daam_ctx_set_time_bins)
-
-}  // namespace
-
-struct DaamCtx {
-    int device = 0;                    // HIP device the context was created on; every entry point runs there
-    int max_layers, tokens, out_side, acc_dtype;
-    // Layer slots.  Un-binned: slot = layer.  Time-binned (daam_ctx_set_time_bins): slot = window * max_layers + layer, an
-    // ordinary Layer over the window's slice of the layer's sums [n_bins][heads, tokens, side, side]; every tap entry point maps
-    // (layer, step) to its slot, so the deferred launch chains the steps of one window per table entry (TapLayer) as it
-    // chains the steps of a layer without windows.
-    std::vector<Layer> layers;
-    int n_bins = 0;                    // 0: no windows (daam_ctx_set_time_bins never called)
-    int bin_first[kMaxBins] = {0};     // first step of each window
-    std::vector<int> tap_steps;        // per layer: taps since daam_reset (the step index of the next tap)
-    void* bin_scratch = nullptr;       // daam_finalize_bins: f32 planes of the window-range reduction (grows, never shrinks)
-    size_t bin_scratch_bytes = 0;
-    int slot_of(int layer) const {
-        if (n_bins <= 1) return layer;
-        const int step = tap_steps[layer];
-        int b = n_bins - 1;
-        while (b > 0 && bin_first[b] > step) --b;
-        return b * max_layers + layer;
-    }
-    Ring ring;
-    int16_t* d_tab_idx = nullptr;
-    float* d_tab_w = nullptr;
-    std::vector<int> tab_sides;
-    std::vector<int> tab_fp16_exact;   // every (border-merged) tap weight is an fp16 number
-    void* d_up32_ops = nullptr;        // finalize_up32_mfma_kernel operands of the 32 -> 64 table (see build_up32_ops)
-    void* d_up32_ops_bf16 = nullptr;   // the same for bf16 planes on the pipelined kernel: pass-1 pieces as bf16 bit patterns, W = W' + E (NULL: no such split)
-    int up32_tab = -1;
-    int no_mfma_finalize = 0;
-    int no_fold_same = 0;             // debugging / A-B: the same-size class as its own kernel beside the pipelined one
-    int no_pipe_finalize = 0;         // debugging / A-B: the round-2 x2 MFMA kernel instead of the software-pipelined one
-    void* d_zero_planes = nullptr;    // [tokens][32 x 32] zeros (sized for f32 planes): padding keys of the pipelined x2 finalize
-    int no_paired_finalize = 0;       // debugging / A-B: same-size and x2 class as two launches
-    // finalize tables kept on the device between calls: a generation's compute_global_heat_map() selects the same keys at the same
-    // addresses as the previous one, so the key / pointer tables are uploaded once and compared on the host afterwards
-    static constexpr size_t kFinTabCap = 1u << 20;
-    char* d_fin_tab = nullptr;
-    std::vector<char> fin_tab_host;   // the bytes d_fin_tab holds (when fin_tab_valid)
-    bool fin_tab_valid = false;
-    hipStream_t fin_tab_stream = nullptr;   // the stream its upload and its readers were enqueued on
-    int no_w8 = 0;                    // debugging / A-B: DAAM_TAP_W8=0 (head_dim-64 launches on 4-wave workgroups of 128 pixels instead of 8-wave / 256)
-    int no_fin_cache = 0;             // debugging / A-B: DAAM_NO_FIN_CACHE=1 (tables through the ring + zeroing in every call)
-    // daam_finalize_prepare: the output buffer the next daam_finalize accumulates into has been zeroed already (prep_*), or is to
-    // be zeroed by the table-upload kernel of the next tap launch (fold_*)
-    float* prep_out = nullptr;
-    hipStream_t prep_stream = nullptr;
-    int prep_rows = 0;                 // token rows the announced call covers (= the rows that were / will be cleared)
-    float* fold_out = nullptr;
-    size_t fold_bytes = 0;
-    hipStream_t fold_stream = nullptr;
-    std::vector<Pending> pending;
-    std::vector<int> pending_count;   // per layer: recorded steps
-    std::vector<int> pending_last;    // per layer: index of its newest entry in `pending`
-    void drop_pending() { pending.clear(); pending_count.clear(); pending_last.clear(); }
-    int last_grid[2] = {0, 0}, last_block[2] = {0, 0}, last_lds[2] = {0, 0};
-    std::string last_kernels[2];       // daam_last_kernels: what the last tap launch / finalize call launched, '+'-separated
-    int last_fin_side = 0;             // finalize class kernels of the last call that ran on auxiliary streams
-    int last_flush_kernels = 0, last_flush_side = 0, last_flush_steps = 0;   // daam_last_flush: kernels / of them on side streams / longest step chain
-    long long n_flushes = 0;           // tap launches (flushes that launched something) since the context was created
-    int profile = 0;
-    hipEvent_t prof_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    // daam_profile_enable(ctx, 2): every launch of a kind (0 tap, 1 finalize) gets its own event pair out of a ring, so that a caller
-    // can time the launches of a whole timed region WITHOUT synchronising inside it (daam_profile_history afterwards)
-    static constexpr int kProfHist = 256;
-    std::vector<hipEvent_t> hist_ev[2][2];
-    long long hist_count[2] = {0, 0};
-    hipEvent_t prof_event(int which, int end) {
-        if (profile == 2 && !hist_ev[which][end].empty()) return hist_ev[which][end][(size_t)(hist_count[which] % kProfHist)];
-        return prof_ev[which][end];
-    }
-    // shader-clock monitor (daam_clock_monitor_*): one wave on its own stream samples the shader-cycle counter and the
-    // 100 MHz reference counter into pinned memory while the kernels under test run
-    unsigned long long* clk_host = nullptr;
-    unsigned long long* clk_dev = nullptr;
-    int clk_samples = 0;
-    hipStream_t clk_stream = nullptr;
-    static constexpr int kAux = 3;     // side streams of multi-kind tap flushes (see daam_tap_flush)
-    hipStream_t aux_stream[kAux] = {nullptr, nullptr, nullptr};
-    hipEvent_t aux_fork = nullptr, aux_join[kAux] = {nullptr, nullptr, nullptr};
-    unsigned* d_started = nullptr;     // start gate of multi-kernel flushes: workgroups of side kernels started so far (wraps)
-    unsigned started_target = 0;       // ... and how many the host has launched
-    unsigned* gate_timeouts = nullptr; // pinned, device-mapped: gates that gave up after their 200 us (the side kernels were NOT running beside them)
-    unsigned* gate_timeouts_dev = nullptr;
-    int no_start_gate = 0;             // DAAM_NO_START_GATE=1 (debugging / A-B), or a failed flush left counter and target in disagreement
-    unsigned gate_timeouts_seen = 0;   // value of *gate_timeouts when the gate was last armed
-    unsigned long long gate_enqueued = 0;   // gated flushes enqueued since then
-    long long gate_off_until = 0;      // n_flushes at which a gate that was dropped for timing out is tried again (0 = in use)
-    bool gate_said = false;
-    int no_side_stream = 0;
-
-    int force_generic = 0;
-    int fast_exp = 0;
-    int no_d64 = 0;
-    int no_tap_pair = 0;
-    int slab_tail_pct = 25;           // DAAM_SLAB_TAIL: percent of a head_dim-40 layer's pixels the slab kernel takes in 16-pixel tiles at the end of the launch
-                                      // (SD-v1.5, alternating on one box: 0 -> 2390, 25 -> 2415, 50 -> 2316, 100 -> 2204 maps/s: half-size units cost K traffic)
-    int tap_slab = 1;                 // tap_slab_kernel (daam_tap_slab.hip): deferred fp16 layers of head_dim 40 / 80 / 160 in 640-byte slabs of adjacent heads
-                                      // (whole 128-byte lines of Q: SD-v1.x); DAAM_TAP_SLAB=0 leaves them to the kernels below
-    int tap_chunked = 2;              // tap_chunk_kernel (fp16 layers of any head_dim, one kind of workgroup): 2 = for deferred launches that
-                                      // mix head dims (default), 1 = for every fp16 layer (DAAM_TAP_CHUNKED=1), 0 = never (DAAM_TAP_CHUNKED=0)
-};
-
-// Entry points may be called with another device current (a pipeline on cuda:1 while the process default is
-// cuda:0): streams, events and launches must go to the context's device.  Restores the caller's device on exit.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceGuard(const DaamCtx* c) {
-        if (c && hipGetDevice(&prev) == hipSuccess && prev != c->device) switched = hipSetDevice(c->device) == hipSuccess;
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
-static size_t acc_elem(int dtype) { return dtype == DAAM_F32 ? 4 : 2; }
 
 // which running-sum dtypes a pipeline dtype may feed: its own (the reference's behaviour) or f32
 static bool dtypes_compatible(int in_dtype, int acc_dtype) { return acc_dtype == DAAM_F32 || acc_dtype == in_dtype; }
@@ -342,15 +51,6 @@ static void bicubic_table(int in_size, int out_size, int16_t* idx, float* w)
             idx[j * 4 + a] = (int16_t)v;
         }
     }
-}
-
-static int ensure_zeroed(Layer& l, hipStream_t s)
-{
-    if (l.zero_pending) {
-        HIP_TRY(hipMemsetAsync(l.acc, 0, l.bytes, s));
-        l.zero_pending = false;
-    }
-    return 0;
 }
 
 // MFMA operand pieces of finalize_up32_mfma_kernel (32 -> 64, fp16-exact banded tap matrix W[o][src]),
@@ -410,20 +110,8 @@ static std::vector<_Float16> build_up32_ops(const int16_t* idx, const float* w, 
     return ops;
 }
 
-// Key ranges of the chunks of the x2 MFMA finalize: equal shares (even boundaries; the two key lanes of a workgroup take the
-// keys of its range alternately).  Shares shrinking with the dispatch round of a chunk's workgroups (the SIMD arbitrates by
-// age: the first 256 workgroups finish their loop in 23 us, the last 256 in 40 us) were tried and changed nothing -- the kernel
-// is throughput-bound from its first to its last microsecond, the age order only decides who waits.
-static void finalize_chunk_ranges(int n_keys, int n_chunks, FinLaunch* L)
-{
-    const int pairs = (n_keys + 1) / 2;
-    for (int c = 0; c <= n_chunks; ++c)
-        L->chunk_begin[c] = (int16_t)std::min(n_keys, 2 * (int)(((int64_t)pairs * c + n_chunks - 1) / n_chunks));
-    L->chunk_begin[n_chunks] = (int16_t)n_keys;
-}
-
 // auxiliary non-blocking streams + fork / join events of a context (multi-kernel tap flushes, multi-class finalize)
-static hipError_t ensure_aux(DaamCtx* c)
+hipError_t ensure_aux(DaamCtx* c)
 {
     if (c->aux_fork) return hipSuccess;
     hipError_t ae = hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming);
@@ -454,7 +142,6 @@ static const char* tap_kernel_name(int kd)
     return (kd == 65 || kd == 66) ? "tap_d64_kernel" : (kd == 67 || kd == 69) ? "tap_wide_kernel" : kd == 70 ? "tap_chunk_kernel"
            : kd == 71 ? "tap_slab_kernel" : kd == 72 ? "tap_pair_kernel" : kd ? "tap_mfma_kernel" : "tap_generic_kernel";
 }
-static const char* dtype_name(int dt) { return dt == DAAM_F32 ? "f32" : dt == DAAM_BF16 ? "bf16" : "f16"; }
 
 extern "C" {
 
@@ -1407,830 +1094,6 @@ int daam_key_offset(DaamCtx* c, int layer, int* offset, int* total)
     return 0;
 }
 
-// ---- finalize: host-side plan (which keys, in which class, chunking of the pipelined x2 kernel) and the device tables it needs
-namespace {
-constexpr int kFinClasses = 5;       // 0 = same size (clamp + mean), 1 = x2 (32 -> 64), 2 = x4 (16 -> 64), 3 = general kernel, 4 = x0.5 (128 -> 64)
-struct FinPlan {
-    std::vector<FinKey> keys[kFinClasses];
-    std::vector<int> pos[kFinClasses];  // layer-major index of every key (daam_finalize_groups: its group)
-    int total = 0, max_side = 0;
-    bool mfma_up = false, pipe_up = false, fold_same = false;
-    int pipe_chunks = 0, pipe_nk = 0, pipe_stride = 0, same_per = 0;
-    size_t key_bytes = 0, ptr_bytes = 0;
-    std::vector<char> tab;           // FinKey array (class order) | pointer table of the pipelined x2 kernel | folded same-size pointers
-};
-int fin_env(const char* name)
-{
-    const char* v = getenv(name);
-    return v ? atoi(v) : 0;
-}
-}  // namespace
-
-// token rows a finalize call covers (ABI v6: the caller may pass the prompt's n_tokens + 2, daam/trace.py:127)
-static int fin_rows(const DaamCtx* c, int n_rows) { return (n_rows <= 0 || n_rows > c->tokens) ? c->tokens : n_rows; }
-
-// the plan over `n_layers` entries of `layers` whose planes are of `dtype` (the context's sums: c->layers / max_layers / acc_dtype;
-// daam_finalize_bins also plans over the window slots of a binned context and over f32 scratch planes)
-static int fin_plan_on(DaamCtx* c, const Layer* layers, int n_layers, int dtype, const uint8_t* key_mask, int rows, FinPlan& P)
-{
-    static const int env_chunks = fin_env("DAAM_FIN_CHUNKS"), env_pipe_chunks = fin_env("DAAM_FIN_PIPE_CHUNKS");   // pipelined x2 kernel only (A/B)
-    auto& keys = P.keys;
-    int pos = 0;
-    for (int i = 0; i < n_layers; ++i) {
-        const Layer& l = layers[i];
-        if (!l.configured) continue;
-        for (int h = 0; h < l.heads; ++h, ++pos) {
-            if (key_mask && !key_mask[pos]) continue;
-            FinKey k;
-            k.base = static_cast<const char*>(l.acc) + (size_t)h * c->tokens * l.hw * acc_elem(dtype);
-            k.side = l.side;
-            k.tab = l.tab;
-            int cls = 3;
-            if (!c->force_generic) {
-                if (l.tab < 0 && (l.hw % 8) == 0) cls = 0;
-                else if (l.tab >= 0 && finalize_up_supported(l.side, c->out_side)) cls = l.side == 32 ? 1 : 2;
-                else if (l.tab >= 0 && finalize_down2_supported(l.side, c->out_side)) cls = 4;
-            }
-            if (cls == 3 && l.tab >= 0) P.max_side = std::max(P.max_side, l.side);
-            keys[cls].push_back(k);
-            P.pos[cls].push_back(pos);
-            ++P.total;
-        }
-    }
-    if (P.total == 0) return fail(DAAM_E_NOMAPS, "no heat maps selected");
-    if (P.max_side > 128) return fail(DAAM_E_UNSUPPORTED, "map side %d > 128 not supported by finalize", P.max_side);
-    // x2 class on the matrix cores (fp16 planes, fp16-exact tap matrix)?
-    P.mfma_up = !keys[1].empty() && keys[1][0].tab == c->up32_tab && c->d_up32_ops &&
-                c->tab_fp16_exact[keys[1][0].tab] && !c->no_mfma_finalize;
-    // ... on the software-pipelined kernel (daam_finalize_pipe.hip): workgroup = (token, key chunk), every wave walks ALL keys
-    // of its chunk from a pointer table padded with the all-zero plane to one even length >= 4 (+ what the ring prefetches
-    // past the end).  ~1000 workgroups of 2 waves = one resident round at 2 waves per SIMD.
-    P.pipe_up = P.mfma_up && !c->no_pipe_finalize && c->d_zero_planes;
-    // bf16 / f32 sums (round 6): the pipelined kernel only (bf16: the tap matrix must split into two bf16 MFMA operands); the round-2 MFMA
-    // kernels behind DAAM_NO_PIPE_FINALIZE take fp16 planes
-    if (dtype == DAAM_BF16) P.pipe_up = P.pipe_up && c->d_up32_ops_bf16;
-    if (dtype != DAAM_F16) P.mfma_up = P.pipe_up;
-    if (P.pipe_up) {
-        const int n = (int)keys[1].size();
-        const int want = env_pipe_chunks ? env_pipe_chunks : env_chunks ? env_chunks : std::max(1, (1024 + rows / 2) / rows);
-        P.pipe_chunks = std::max(1, std::min(want, (n + 7) / 8));
-        const int per = (n + P.pipe_chunks - 1) / P.pipe_chunks;
-        P.pipe_nk = std::max(4, (per + 1) & ~1);
-        P.pipe_stride = (P.pipe_nk + finalize_pipe_ring(dtype) + 2) & ~1;
-    }
-    // The same-size (64 x 64) keys ride along in the pipelined kernel (every wave adds its share of them to its accumulators
-    // before the x2 loop) unless they outnumber the x2 keys 2 : 1 -- then they keep their own streaming kernel.
-    P.fold_same = P.pipe_up && !keys[0].empty() && c->out_side == 64 && keys[0].size() <= 2 * keys[1].size() && !c->no_fold_same;
-    P.same_per = P.fold_same ? ((int)keys[0].size() + P.pipe_chunks - 1) / P.pipe_chunks : 0;
-    P.key_bytes = ((size_t)P.total * sizeof(FinKey) + 63) & ~size_t(63);
-    P.ptr_bytes = (size_t)P.pipe_chunks * P.pipe_stride * sizeof(unsigned long long);
-    P.tab.assign(P.key_bytes + P.ptr_bytes + (size_t)P.pipe_chunks * P.same_per * sizeof(unsigned long long), 0);
-    FinKey* dst = reinterpret_cast<FinKey*>(P.tab.data());
-    for (auto& v : keys) {
-        if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(FinKey));
-        dst += v.size();
-    }
-    if (P.pipe_up) {
-        unsigned long long* pt = reinterpret_cast<unsigned long long*>(P.tab.data() + P.key_bytes);
-        const unsigned long long zero = reinterpret_cast<unsigned long long>(c->d_zero_planes);
-        const int n = (int)keys[1].size(), per = (n + P.pipe_chunks - 1) / P.pipe_chunks;
-        for (int ch = 0; ch < P.pipe_chunks; ++ch)
-            for (int j = 0; j < P.pipe_stride; ++j) {
-                const int k = ch * per + j;
-                pt[(size_t)ch * P.pipe_stride + j] = (j < per && k < n) ? reinterpret_cast<unsigned long long>(keys[1][k].base) : zero;
-            }
-        unsigned long long* st = pt + (size_t)P.pipe_chunks * P.pipe_stride;
-        for (int ch = 0; ch < P.pipe_chunks; ++ch)
-            for (int j = 0; j < P.same_per; ++j) {
-                const size_t k = (size_t)ch * P.same_per + j;
-                st[(size_t)ch * P.same_per + j] = k < keys[0].size() ? reinterpret_cast<unsigned long long>(keys[0][k].base) : 0ull;
-            }
-    }
-    return 0;
-}
-
-static int fin_plan(DaamCtx* c, const uint8_t* key_mask, int rows, FinPlan& P)
-{
-    return fin_plan_on(c, c->layers.data(), c->max_layers, c->acc_dtype, key_mask, rows, P);
-}
-
-// the device copy of the tables is the one these bytes were uploaded to, on this stream?
-static bool fin_cache_hit(const DaamCtx* c, const FinPlan& P, hipStream_t s)
-{
-    return !c->no_fin_cache && c->fin_tab_valid && c->fin_tab_stream == s && P.tab.size() == c->fin_tab_host.size() &&
-           memcmp(P.tab.data(), c->fin_tab_host.data(), P.tab.size()) == 0;
-}
-
-// may this call's tables replace the cached ones?  (not while kernels enqueued on ANOTHER stream may still be reading them)
-static bool fin_cacheable(const DaamCtx* c, const FinPlan& P, hipStream_t s)
-{
-    return !c->no_fin_cache && c->d_fin_tab && P.tab.size() <= DaamCtx::kFinTabCap && (!c->fin_tab_valid || c->fin_tab_stream == s);
-}
-
-// tables -> pinned ring -> d_fin_tab by the upload kernel (which also clears `zero`), in stream order
-static int fin_cache_upload(DaamCtx* c, const FinPlan& P, hipStream_t s, void* zero, size_t zero_bytes)
-{
-    size_t off = 0;
-    HIP_TRY(c->ring.alloc(P.tab.size(), &off));
-    memcpy(c->ring.host + off, P.tab.data(), P.tab.size());
-    c->fin_tab_valid = false;
-    hipError_t e = launch_upload(c->d_fin_tab, c->ring.host_dev + off, P.tab.size(), zero, zero_bytes, s);
-    (void)c->ring.release(s);                                  // the staging region is free once the upload kernel has run
-    if (e != hipSuccess) return fail((int)e, "table upload: %s", hipGetErrorString(e));
-    c->fin_tab_host = P.tab;
-    c->fin_tab_valid = true;
-    c->fin_tab_stream = s;
-    return 0;
-}
-
-static bool fin_out_zeroable(const DaamCtx* c, const float* out, int rows)
-{
-    const size_t out_bytes = sizeof(float) * rows * (size_t)c->out_side * c->out_side;
-    return out_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-}
-
-int daam_finalize_prepare(DaamCtx* c, const uint8_t* key_mask, int n_rows, float* out, void* stream)
-{
-    if (!c || !out) return fail(DAAM_E_INVALID, "NULL argument");
-    if (c->n_bins > 1) return fail(DAAM_E_UNSUPPORTED, "daam_finalize_prepare: not on a time-binned context (daam_finalize_bins)");
-    DeviceGuard on_device(c);
-    hipStream_t s = (hipStream_t)stream;
-    const int rows = fin_rows(c, n_rows);
-    c->prep_out = c->fold_out = nullptr;
-    c->prep_rows = rows;
-    if (c->no_fin_cache || !fin_out_zeroable(c, out, rows)) return 0;  // daam_finalize does everything itself
-    FinPlan P;
-    if (fin_plan(c, key_mask, rows, P)) return 0;                // nothing selected / unsupported: daam_finalize reports it
-    const size_t out_bytes = sizeof(float) * rows * (size_t)c->out_side * c->out_side;
-    if (!fin_cache_hit(c, P, s)) {
-        if (!fin_cacheable(c, P, s)) return 0;
-        int rc = fin_cache_upload(c, P, s, out, out_bytes);      // first call of a geometry / selection: tables + zeroing now
-        if (rc) return rc;
-        c->prep_out = out;
-        c->prep_stream = s;
-        return 0;
-    }
-    if (!c->pending.empty()) {                                   // the table-upload kernel of the coming tap launch clears `out`
-        c->fold_out = out;
-        c->fold_bytes = out_bytes;
-        c->fold_stream = s;
-        return 0;
-    }
-    hipError_t e = launch_upload(nullptr, nullptr, 0, out, out_bytes, s);
-    if (e != hipSuccess) return fail((int)e, "output zeroing: %s", hipGetErrorString(e));
-    c->prep_out = out;
-    c->prep_stream = s;
-    return 0;
-}
-
-int daam_finalize(DaamCtx* c, const uint8_t* key_mask, int n_rows, float* out, void* stream)
-{
-    if (!c || !out) return fail(DAAM_E_INVALID, "NULL argument");
-    if (!c->pending.empty()) return fail(DAAM_E_STATE, "finalize with deferred taps pending: flush first");
-    if (c->n_bins > 1) {                                       // a binned context: the whole generation = windows [0, n_bins)
-        int total = 0;
-        daam_key_offset(c, 0, nullptr, &total);
-        std::vector<int32_t> kg(total > 0 ? total : 1, -1);
-        for (int i = 0; i < total; ++i) kg[i] = (!key_mask || key_mask[i]) ? 0 : -1;
-        const int32_t b0 = 0, b1 = c->n_bins, r = n_rows;
-        return daam_finalize_bins(c, kg.data(), 1, nullptr, &b0, &b1, &r, out, 0, stream);
-    }
-    DeviceGuard on_device(c);
-    hipStream_t s = (hipStream_t)stream;
-    const int rows = fin_rows(c, n_rows);
-    // zeroed ahead of this call (daam_finalize_prepare, same buffer, same rows, same stream)?  One-shot.
-    const bool prepared = c->prep_out == out && c->prep_stream == s && c->prep_rows == rows;
-    c->prep_out = c->fold_out = nullptr;
-    for (auto& l : c->layers)
-        if (l.configured) {
-            int zrc = ensure_zeroed(l, s);
-            if (zrc) return zrc;
-        }
-    constexpr int kClasses = kFinClasses;
-    FinPlan P;
-    {
-        int prc = fin_plan(c, key_mask, rows, P);
-        if (prc) return prc;
-    }
-    auto& keys = P.keys;
-    const int total = P.total, max_side = P.max_side;
-    const bool mfma_up = P.mfma_up, pipe_up = P.pipe_up, fold_same = P.fold_same;
-    const int pipe_chunks = P.pipe_chunks, pipe_nk = P.pipe_nk, pipe_stride = P.pipe_stride, same_per = P.same_per;
-    const size_t key_bytes = P.key_bytes, ptr_bytes = P.ptr_bytes, bytes = P.tab.size();
-    const size_t plane = (size_t)c->out_side * c->out_side;
-    const size_t out_bytes = sizeof(float) * rows * plane;
-    static const int env_chunks = fin_env("DAAM_FIN_CHUNKS");
-    static const int env_up_chunks = fin_env("DAAM_FIN_UP_CHUNKS");       // LDS up kernels only (A/B)
-    // the output is accumulated with atomics: it is zeroed by the table-upload launch unless daam_finalize_prepare had it done
-    const bool zero_in_upload = fin_out_zeroable(c, out, rows);
-    if (!zero_in_upload && !prepared) {
-        hipError_t ze = hipMemsetAsync(out, 0, out_bytes, s);
-        if (ze != hipSuccess) return fail((int)ze, "output memset: %s", hipGetErrorString(ze));
-    }
-    if (c->profile) (void)hipEventRecord(c->prof_event(1, 0), s);    // timed: what this call launches (table upload + zeroing if needed, class kernels)
-    void* zero_ptr = (zero_in_upload && !prepared) ? out : nullptr;
-    const size_t zero_n = zero_ptr ? out_bytes : 0;
-    const char* tab_dev = nullptr;
-    bool ring_held = false;                                     // the tables sit in a ring region the class kernels read
-    if (fin_cache_hit(c, P, s)) {
-        tab_dev = c->d_fin_tab;
-        if (zero_ptr) {
-            hipError_t e = launch_upload(nullptr, nullptr, 0, zero_ptr, zero_n, s);
-            if (e != hipSuccess) return fail((int)e, "output zeroing: %s", hipGetErrorString(e));
-        }
-    } else if (fin_cacheable(c, P, s)) {
-        int rc = fin_cache_upload(c, P, s, zero_ptr, zero_n);
-        if (rc) return rc;
-        tab_dev = c->d_fin_tab;
-    } else {
-        size_t off = 0;
-        HIP_TRY(c->ring.alloc(bytes, &off));
-        memcpy(c->ring.host + off, P.tab.data(), bytes);
-        hipError_t ce = c->ring.commit(off, bytes, s, zero_ptr, zero_n);
-        if (ce != hipSuccess) {
-            (void)c->ring.release(s);
-            return fail((int)ce, "table upload: %s", hipGetErrorString(ce));
-        }
-        tab_dev = c->ring.dev + off;
-        ring_held = true;
-    }
-    auto release_tab = [&]() { if (ring_held) (void)c->ring.release(s); ring_held = false; };
-    const FinKey* dev = reinterpret_cast<const FinKey*>(tab_dev);
-    c->last_block[1] = 256;
-    c->last_grid[1] = 0;
-    c->last_lds[1] = 0;
-    // The round-2 MFMA kernel (DAAM_NO_PIPE_FINALIZE=1) walks a host-built chunk table of at most kFinMaxChunks chunks x 2 key
-    // lanes x 64 keys, so a larger class goes out as several launches over key sub-ranges (kFinMfmaKeysPerLaunch each) -- the
-    // pipelined kernel, the LDS kernel and the other classes take any key count.
-    constexpr int kFinMfmaKeysPerLaunch = kFinMaxChunks * 128;
-    // x2 class chunking: ~1000 workgroups (one full round at 4 workgroups per CU) measured best -- fewer leaves a ragged
-    // tail, more pays the per-workgroup reduction + atomics too often; every key lane of a chunk takes at most 64 keys
-    const int want_up = env_up_chunks ? env_up_chunks : env_chunks ? env_chunks : std::max(1, (1024 + rows / 2) / rows);
-    // (few keys: at least 4 per wave -- a workgroup ends in a four-wave LDS reduction + 4096 atomics, which one key per wave does
-    // not pay for: SD-v1.5's 48 x4 keys in 3 chunks instead of 12 take 10 us less)
-    auto up_chunks = [&](int n) { return std::max(std::max(1, std::min((n + 15) / 16, want_up)), (n + 127) / 128); };
-    // build the launch descriptor of every non-empty class first
-    FinLaunch launches[kClasses];
-    bool have[kClasses] = {false, false, false, false, false};
-    for (int cls = 0; cls < kClasses; ++cls) {
-        const int n = (int)keys[cls].size();
-        if (n == 0) continue;
-        FinLaunch& L = launches[cls];
-        L.keys = dev;
-        dev += n;
-        L.tab_idx = c->d_tab_idx;
-        L.tab_w = c->d_tab_w;
-        L.out = out;
-        L.n_keys = n;
-        L.tokens = rows;                                       // grid dimension / bound of every class kernel; a key's planes keep their [tokens] stride
-        L.out_side = c->out_side;
-        L.inv_n = 1.0f / (float)total;
-        L.max_side = max_side;
-        L.mfma_ops = (cls == 1 && mfma_up) ? c->d_up32_ops : nullptr;
-        if (cls == 0) {
-            // 154 workgroups per chunk: 4 chunks for the 100 same-size keys of SDXL-1024, up to 9 (1386 workgroups) for the 1000 of
-            // SDXL-2048.  Round 2 had 16 there; round 4's sweep (tools/exp/fin_chunks_sweep.sh: 4 ... 64 chunks) has its optimum at
-            // 8 - 10 -- the x0.5 class now streams beside this one on a side stream, and every chunk ends in 315 k atomics per
-            // token plane: 0.186 -> 0.159 ms for the SDXL-2048 call (0.59 -> 0.69 of the HBM peak)
-            L.n_chunks = std::max(1, std::min(n, env_chunks ? env_chunks : std::min(9, std::max(4, n / 32))));
-        } else if (cls == 3) {
-            L.n_chunks = std::max(1, std::min(n, 32));
-        } else {
-            // each wave takes keys first, first + 4*n_chunks, ...: at most 64 per wave (4 key lanes per workgroup; the MFMA
-            // kernel of class 1 has 2 and is chunked per launch below)
-            L.n_chunks = up_chunks(n);
-        }
-        memset(L.chunk_begin, 0, sizeof L.chunk_begin);
-        have[cls] = true;
-    }
-    // the MFMA kernel's launches: key sub-ranges of at most kFinMfmaKeysPerLaunch keys, each with its own chunk table
-    std::vector<FinLaunch> up_parts;
-    if (mfma_up && !pipe_up) {
-        const FinLaunch& U = launches[1];
-        for (int begin = 0; begin < U.n_keys; begin += kFinMfmaKeysPerLaunch) {
-            FinLaunch P = U;
-            P.keys = U.keys + begin;
-            P.n_keys = std::min(kFinMfmaKeysPerLaunch, U.n_keys - begin);
-            P.n_chunks = std::min(up_chunks(P.n_keys), kFinMaxChunks);
-            finalize_chunk_ranges(P.n_keys, P.n_chunks, &P);
-            up_parts.push_back(P);
-        }
-        launches[1] = up_parts[0];                             // what the paired launch takes (single part)
-    }
-    // SDXL-1024 in fp16: the same-size and the x2 class side by side in ONE launch
-    const bool paired = mfma_up && !pipe_up && up_parts.size() == 1 && have[0] && !c->no_paired_finalize;
-    // Several classes: the issue-bound x2 kernel keeps the caller's stream; every other class (HBM streams with few
-    // registers: their waves fit beside the two heavy waves of a SIMD) goes to an auxiliary stream forked from / joined to the
-    // caller's by events, launched FIRST -- SDXL-1024: 63 MB of same-size planes stream under 158 MB of x2 planes; SD-v1.5:
-    // three classes side by side instead of three serial launches.
-    if (fold_same) have[0] = false;                            // done inside the pipelined kernel
-    int n_classes = 0;
-    for (int cls = 0; cls < kClasses; ++cls) n_classes += have[cls] ? 1 : 0;
-    // (an event fork / join costs ~15 us of queue latency per finalize call: only worth it for a side class of tens of MB --
-    // SD-v1.5's 1.6 MB x4 class runs 10 us faster serially behind the pipelined kernel)
-    size_t side_bytes = 0;
-    for (int cls = 0; cls < kClasses; ++cls)
-        if (have[cls] && cls != 1)
-            for (auto& k : keys[cls]) side_bytes += (size_t)c->tokens * k.side * k.side * acc_elem(c->acc_dtype);
-    bool fork = pipe_up && n_classes > 1 && n_classes <= DaamCtx::kAux + 1 && !c->no_side_stream && side_bytes >= ((size_t)16 << 20);
-    if (fork) {
-        hipError_t ae = ensure_aux(c);
-        if (ae != hipSuccess || hipEventRecord(c->aux_fork, s) != hipSuccess) fork = false;    // serial launches still correct
-    }
-    int n_side = 0;
-    std::string launched_names;
-    auto names = [&](const char* kernel, const char* what) {
-        launched_names += (launched_names.empty() ? "" : "+") + std::string(kernel) + "<" + what + ">";
-    };
-    auto launch_class = [&](int cls, hipStream_t ks, int* grid, int* lds) -> hipError_t {
-        const FinLaunch& L = launches[cls];
-        if (cls == 1 && pipe_up) {
-            FinPipeLaunch PL;
-            PL.key_ptrs = reinterpret_cast<const unsigned long long*>(tab_dev + key_bytes);
-            PL.same_ptrs = fold_same ? reinterpret_cast<const unsigned long long*>(tab_dev + key_bytes + ptr_bytes) : nullptr;
-            PL.same_per = same_per;
-            PL.mfma_ops = c->acc_dtype == DAAM_BF16 ? c->d_up32_ops_bf16 : c->d_up32_ops;
-            PL.out = out;
-            PL.n_chunks = pipe_chunks;
-            PL.nk_pad = pipe_nk;
-            PL.ptr_stride = pipe_stride;
-            PL.tokens = rows;
-            PL.inv_n = L.inv_n;
-            names("finalize_up32_pipe_kernel", (std::string(dtype_name(c->acc_dtype)) + (fold_same ? " + same-size keys" : "")).c_str());
-            return launch_finalize_up32_pipe(PL, c->acc_dtype, ks, grid);
-        }
-        if (cls == 1 && paired) { names("finalize_up32_same_kernel", "f16"); return launch_finalize_up32_same(L, launches[0], ks, grid); }
-        if (cls == 1 && mfma_up) {
-            names("finalize_up32_mfma_kernel", "f16");
-            hipError_t e = hipSuccess;
-            for (size_t part = 0; part < up_parts.size() && e == hipSuccess; ++part) {
-                int g = 0;
-                e = launch_finalize_up(up_parts[part], 32, c->acc_dtype, 1, ks, &g);
-                *grid += g;
-            }
-            return e;
-        }
-        if (cls == 0) { names("finalize_same_kernel", dtype_name(c->acc_dtype)); return launch_finalize_same(L, c->acc_dtype, ks, grid); }
-        if (cls == 3) { names("finalize_kernel", dtype_name(c->acc_dtype)); return launch_finalize(L, c->acc_dtype, ks, grid, lds); }
-        if (cls == 4) { names("finalize_down2_kernel", dtype_name(c->acc_dtype)); return launch_finalize_down2(L, c->acc_dtype, ks, grid); }
-        names(keys[cls][0].side == 32 ? "finalize_up_kernel<32>" : "finalize_up_kernel<16>", dtype_name(c->acc_dtype));
-        return launch_finalize_up(L, keys[cls][0].side, c->acc_dtype, 0, ks, grid);
-    };
-    const int order[kClasses] = {0, 2, 3, 4, 1};                       // the x2 class last: side kernels are resident when it fills the chip
-    for (int oi = 0; oi < kClasses; ++oi) {
-        const int cls = order[oi];
-        if (!have[cls] || (paired && cls == 0)) continue;
-        hipStream_t ks = s;
-        const bool on_side = fork && cls != 1;
-        if (on_side) {
-            ks = c->aux_stream[n_side];
-            if (hipStreamWaitEvent(ks, c->aux_fork, 0) != hipSuccess) ks = s;
-        }
-        int grid = 0, lds = 0;
-        hipError_t e = launch_class(cls, ks, &grid, &lds);
-        if (e == hipSuccess && ks != s) {
-            e = hipEventRecord(c->aux_join[n_side], ks);
-            ++n_side;
-        }
-        if (e != hipSuccess) {
-            for (int i = 0; i < n_side; ++i) (void)hipStreamWaitEvent(s, c->aux_join[i], 0);
-            release_tab();                                 // the table region is reusable once whatever did launch has run
-            return fail((int)e, "finalize launch (class %d): %s", cls, hipGetErrorString(e));
-        }
-        c->last_grid[1] += grid;
-        c->last_lds[1] = std::max(c->last_lds[1], lds);
-    }
-    for (int i = 0; i < n_side; ++i)
-        if (hipStreamWaitEvent(s, c->aux_join[i], 0) != hipSuccess) { release_tab(); return fail(DAAM_E_STATE, "stream join failed"); }
-    c->last_fin_side = n_side;
-    c->last_kernels[1] = launched_names;
-    if (c->profile) { (void)hipEventRecord(c->prof_event(1, 1), s); ++c->hist_count[1]; }
-    release_tab();
-    return 0;
-}
-
-// daam_finalize_groups: N global heat maps, one launch per class.  The keys of every class are laid out group by group (a
-// group's keys are contiguous in the FinKey array and in the pointer tables of the pipelined x2 kernel, so no chunk straddles
-// two groups); the per-group part of a launch (key range, rows, 1/N, output base, pointer-table offsets) travels in the kernel
-// arguments and blockIdx.z selects it.
-// The grouped finalize over the planes of `layers[0, n_layers)` (plane dtype `dtype`): key i of that table (layer-major, heads
-// inside) belongs to group key_group[i].  Arguments validated by the caller; `mask` = key_group[i] >= 0; `n_of` = keys per group.
-// per_group_fallback: the round-2 MFMA x2 kernel (DAAM_NO_PIPE_FINALIZE) may serve the call as one daam_finalize per group (only
-// over the context's own sums); otherwise such keys take the grouped LDS kernel.  timed_start: this call opens the profiled span.
-static int fin_groups_core(DaamCtx* c, Layer* layers, int n_layers, int dtype, const int32_t* key_group, int total_keys,
-                           int n_groups, const int32_t* n_rows, const std::vector<int>& rows, const std::vector<int>& n_of,
-                           std::vector<uint8_t>& mask, float* out, size_t group_stride, hipStream_t s, bool per_group_fallback,
-                           bool timed_start)
-{
-    const size_t plane = (size_t)c->out_side * c->out_side;
-    for (int i = 0; i < n_layers; ++i)
-        if (layers[i].configured) {
-            int zrc = ensure_zeroed(layers[i], s);
-            if (zrc) return zrc;
-        }
-    FinPlan P;
-    {
-        int prc = fin_plan_on(c, layers, n_layers, dtype, mask.data(), c->tokens, P);
-        if (prc) return prc;
-    }
-    if (P.mfma_up && !P.pipe_up && per_group_fallback) {
-        // the round-2 MFMA x2 kernel (DAAM_NO_PIPE_FINALIZE): one daam_finalize per group
-        for (int g = 0; g < n_groups; ++g) {
-            for (int i = 0; i < total_keys; ++i) mask[i] = key_group[i] == g;
-            int rc = daam_finalize(c, mask.data(), n_rows[g], out + (size_t)g * group_stride, s);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    static const int env_chunks = fin_env("DAAM_FIN_CHUNKS"), env_pipe_chunks = fin_env("DAAM_FIN_PIPE_CHUNKS");
-    static const int env_up_chunks = fin_env("DAAM_FIN_UP_CHUNKS");
-    int max_rows = 0, sum_rows = 0;
-    for (int g = 0; g < n_groups; ++g) { max_rows = std::max(max_rows, rows[g]); sum_rows += rows[g]; }
-    // every class's keys group by group (stable: layer-major order inside a group)
-    std::vector<FinKey> gk[kFinClasses];
-    std::vector<int> begin[kFinClasses], count[kFinClasses];
-    int max_n[kFinClasses] = {0, 0, 0, 0, 0};
-    for (int cls = 0; cls < kFinClasses; ++cls) {
-        begin[cls].assign(n_groups, 0);
-        count[cls].assign(n_groups, 0);
-        for (int g = 0; g < n_groups; ++g) {
-            begin[cls][g] = (int)gk[cls].size();
-            for (size_t j = 0; j < P.keys[cls].size(); ++j)
-                if (key_group[P.pos[cls][j]] == g) gk[cls].push_back(P.keys[cls][j]);
-            count[cls][g] = (int)gk[cls].size() - begin[cls][g];
-            if (!count[cls][g]) begin[cls][g] = 0;             // (a kernel reads keys[0].tab: stay inside the class)
-            max_n[cls] = std::max(max_n[cls], count[cls][g]);
-        }
-    }
-    // pipelined x2 kernel: ~1000 workgroups over the whole launch (every group's rows), one chunk length for every group
-    const bool pipe_up = P.pipe_up, fold_same = P.fold_same;
-    int pipe_chunks = 0, pipe_nk = 0, pipe_stride = 0, pipe_per = 0, same_per = 0;
-    if (pipe_up) {
-        const int want = env_pipe_chunks ? env_pipe_chunks : env_chunks ? env_chunks : std::max(1, (1024 + sum_rows / 2) / sum_rows);
-        pipe_chunks = std::max(1, std::min(want, (max_n[1] + 7) / 8));
-        pipe_per = (max_n[1] + pipe_chunks - 1) / pipe_chunks;
-        pipe_nk = std::max(4, (pipe_per + 1) & ~1);
-        pipe_stride = (pipe_nk + finalize_pipe_ring(dtype) + 2) & ~1;
-        same_per = fold_same ? (max_n[0] + pipe_chunks - 1) / pipe_chunks : 0;
-    }
-    const size_t key_bytes = ((size_t)P.total * sizeof(FinKey) + 63) & ~size_t(63);
-    const size_t ptr_per_group = (size_t)pipe_chunks * pipe_stride, same_per_group = (size_t)pipe_chunks * same_per;
-    const size_t ptr_bytes = ptr_per_group * n_groups * sizeof(unsigned long long);
-    std::vector<char> tab(key_bytes + ptr_bytes + same_per_group * n_groups * sizeof(unsigned long long), 0);
-    {
-        FinKey* dst = reinterpret_cast<FinKey*>(tab.data());
-        for (auto& v : gk) {
-            if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(FinKey));
-            dst += v.size();
-        }
-    }
-    if (pipe_up) {
-        unsigned long long* pt = reinterpret_cast<unsigned long long*>(tab.data() + key_bytes);
-        unsigned long long* st = pt + ptr_per_group * n_groups;
-        const unsigned long long zero = reinterpret_cast<unsigned long long>(c->d_zero_planes);
-        for (int g = 0; g < n_groups; ++g) {
-            const FinKey* k1 = gk[1].data() + begin[1][g];
-            const FinKey* k0 = gk[0].data() + begin[0][g];
-            for (int ch = 0; ch < pipe_chunks; ++ch) {
-                for (int j = 0; j < pipe_stride; ++j) {
-                    const int k = ch * pipe_per + j;
-                    pt[g * ptr_per_group + (size_t)ch * pipe_stride + j] =
-                        (j < pipe_per && k < count[1][g]) ? reinterpret_cast<unsigned long long>(k1[k].base) : zero;
-                }
-                for (int j = 0; j < same_per; ++j) {
-                    const int k = ch * same_per + j;
-                    st[g * same_per_group + (size_t)ch * same_per + j] =
-                        k < count[0][g] ? reinterpret_cast<unsigned long long>(k0[k].base) : 0ull;
-                }
-            }
-        }
-    }
-    P.tab.swap(tab);
-    // the output is accumulated with atomics: rows [0, rows[g]) of every group are cleared first
-    if (c->profile && timed_start) (void)hipEventRecord(c->prof_event(1, 0), s);
-    const char* tab_dev = nullptr;
-    bool ring_held = false;
-    if (fin_cache_hit(c, P, s)) {
-        tab_dev = c->d_fin_tab;
-    } else if (fin_cacheable(c, P, s)) {
-        int rc = fin_cache_upload(c, P, s, nullptr, 0);
-        if (rc) return rc;
-        tab_dev = c->d_fin_tab;
-    } else {
-        size_t off = 0;
-        HIP_TRY(c->ring.alloc(P.tab.size(), &off));
-        memcpy(c->ring.host + off, P.tab.data(), P.tab.size());
-        hipError_t ce = c->ring.commit(off, P.tab.size(), s, nullptr, 0);
-        if (ce != hipSuccess) {
-            (void)c->ring.release(s);
-            return fail((int)ce, "table upload: %s", hipGetErrorString(ce));
-        }
-        tab_dev = c->ring.dev + off;
-        ring_held = true;
-    }
-    auto release_tab = [&]() { if (ring_held) (void)c->ring.release(s); ring_held = false; };
-    {
-        hipError_t ze = launch_zero_groups(out, group_stride, (int)plane, rows.data(), n_groups, s);
-        if (ze != hipSuccess) { release_tab(); return fail((int)ze, "output zeroing: %s", hipGetErrorString(ze)); }
-    }
-    FinGroupLaunch GL[kFinClasses];
-    bool have[kFinClasses] = {false, false, false, false, false};
-    const FinKey* dev = reinterpret_cast<const FinKey*>(tab_dev);
-    const int want_up = env_up_chunks ? env_up_chunks : env_chunks ? env_chunks : std::max(1, (1024 + sum_rows / 2) / sum_rows);
-    auto up_chunks = [&](int n) { return std::max(std::max(1, std::min((n + 15) / 16, want_up)), (n + 127) / 128); };
-    for (int cls = 0; cls < kFinClasses; ++cls) {
-        const int n = (int)gk[cls].size();
-        if (n == 0) continue;
-        FinGroupLaunch& G = GL[cls];
-        memset(&G, 0, sizeof G);
-        FinLaunch& L = G.L;
-        L.keys = dev;
-        dev += n;
-        L.tab_idx = c->d_tab_idx;
-        L.tab_w = c->d_tab_w;
-        L.out = out;
-        L.n_keys = max_n[cls];
-        L.tokens = max_rows;
-        L.out_side = c->out_side;
-        L.inv_n = 0.f;
-        L.max_side = P.max_side;
-        L.mfma_ops = nullptr;
-        const int m = max_n[cls];
-        if (cls == 0) L.n_chunks = std::max(1, std::min(m, env_chunks ? env_chunks : std::min(9, std::max(4, m / 32))));
-        else if (cls == 3) L.n_chunks = std::max(1, std::min(m, 32));
-        else L.n_chunks = up_chunks(m);
-        for (int g = 0; g < n_groups; ++g) {
-            FinGroup& q = G.g[g];
-            q.key_begin = begin[cls][g];
-            q.n_keys = count[cls][g];
-            q.rows = rows[g];
-            q.inv_n = 1.0f / (float)n_of[g];
-            q.out_off = (int64_t)((size_t)g * group_stride);
-            q.ptr_off = (int32_t)(g * ptr_per_group);
-            q.same_off = (int32_t)(g * same_per_group);
-        }
-        have[cls] = true;
-    }
-    if (fold_same) have[0] = false;                            // done inside the pipelined kernel
-    int n_classes = 0;
-    size_t side_bytes = 0;
-    for (int cls = 0; cls < kFinClasses; ++cls) {
-        n_classes += have[cls] ? 1 : 0;
-        if (have[cls] && cls != 1)
-            for (auto& k : gk[cls]) side_bytes += (size_t)c->tokens * k.side * k.side * acc_elem(dtype);
-    }
-    bool fork = pipe_up && n_classes > 1 && n_classes <= DaamCtx::kAux + 1 && !c->no_side_stream && side_bytes >= ((size_t)16 << 20);
-    if (fork) {
-        hipError_t ae = ensure_aux(c);
-        if (ae != hipSuccess || hipEventRecord(c->aux_fork, s) != hipSuccess) fork = false;
-    }
-    c->last_block[1] = 256;
-    c->last_grid[1] = 0;
-    c->last_lds[1] = 0;
-    std::string launched_names;
-    auto names = [&](const char* kernel, const std::string& what) {
-        launched_names += (launched_names.empty() ? "" : "+") + std::string(kernel) + "<" + what + ">";
-    };
-    const std::string dt = dtype_name(dtype);
-    auto launch_class = [&](int cls, hipStream_t ks, int* grid, int* lds) -> hipError_t {
-        const FinGroupLaunch& G = GL[cls];
-        if (cls == 1 && pipe_up) {
-            FinPipeGroupLaunch PG;
-            memset(&PG, 0, sizeof PG);
-            FinPipeLaunch& PL = PG.L;
-            PL.key_ptrs = reinterpret_cast<const unsigned long long*>(tab_dev + key_bytes);
-            PL.same_ptrs = fold_same ? reinterpret_cast<const unsigned long long*>(tab_dev + key_bytes + ptr_bytes) : nullptr;
-            PL.same_per = same_per;
-            PL.mfma_ops = dtype == DAAM_BF16 ? c->d_up32_ops_bf16 : c->d_up32_ops;
-            PL.out = out;
-            PL.n_chunks = pipe_chunks;
-            PL.nk_pad = pipe_nk;
-            PL.ptr_stride = pipe_stride;
-            PL.tokens = max_rows;
-            PL.inv_n = 0.f;
-            memcpy(PG.g, G.g, sizeof PG.g);
-            names("finalize_up32_pipe_grouped_kernel", dt + (fold_same ? " + same-size keys" : ""));
-            return launch_finalize_up32_pipe_grouped(PG, n_groups, dtype, ks, grid);
-        }
-        if (cls == 0) { names("finalize_same_grouped_kernel", dt); return launch_finalize_same_grouped(G, n_groups, dtype, ks, grid); }
-        if (cls == 3) { names("finalize_grouped_kernel", dt); return launch_finalize_grouped(G, n_groups, dtype, ks, grid, lds); }
-        if (cls == 4) { names("finalize_down2_grouped_kernel", dt); return launch_finalize_down2_grouped(G, n_groups, dtype, ks, grid); }
-        names(gk[cls][0].side == 32 ? "finalize_up_grouped_kernel<32>" : "finalize_up_grouped_kernel<16>", dt);
-        return launch_finalize_up_grouped(G, n_groups, gk[cls][0].side, dtype, ks, grid);
-    };
-    int n_side = 0;
-    const int order[kFinClasses] = {0, 2, 3, 4, 1};
-    for (int oi = 0; oi < kFinClasses; ++oi) {
-        const int cls = order[oi];
-        if (!have[cls]) continue;
-        hipStream_t ks = s;
-        if (fork && cls != 1) {
-            ks = c->aux_stream[n_side];
-            if (hipStreamWaitEvent(ks, c->aux_fork, 0) != hipSuccess) ks = s;
-        }
-        int grid = 0, lds = 0;
-        hipError_t e = launch_class(cls, ks, &grid, &lds);
-        if (e == hipSuccess && ks != s) {
-            e = hipEventRecord(c->aux_join[n_side], ks);
-            ++n_side;
-        }
-        if (e != hipSuccess) {
-            for (int i = 0; i < n_side; ++i) (void)hipStreamWaitEvent(s, c->aux_join[i], 0);
-            release_tab();
-            return fail((int)e, "grouped finalize launch (class %d): %s", cls, hipGetErrorString(e));
-        }
-        c->last_grid[1] += grid;
-        c->last_lds[1] = std::max(c->last_lds[1], lds);
-    }
-    for (int i = 0; i < n_side; ++i)
-        if (hipStreamWaitEvent(s, c->aux_join[i], 0) != hipSuccess) { release_tab(); return fail(DAAM_E_STATE, "stream join failed"); }
-    c->last_fin_side = n_side;
-    c->last_kernels[1] = launched_names;
-    if (c->profile) { (void)hipEventRecord(c->prof_event(1, 1), s); ++c->hist_count[1]; }
-    release_tab();
-    return 0;
-}
-
-int daam_finalize_groups(DaamCtx* c, const int32_t* key_group, int n_groups, const int32_t* n_rows, float* out,
-                         size_t group_stride, void* stream)
-{
-    if (!c || !out || !key_group || !n_rows) return fail(DAAM_E_INVALID, "NULL argument");
-    if (n_groups < 1 || n_groups > kFinMaxGroups) return fail(DAAM_E_INVALID, "n_groups %d not in 1..%d", n_groups, kFinMaxGroups);
-    if (!c->pending.empty()) return fail(DAAM_E_STATE, "finalize with deferred taps pending: flush first");
-    if (c->n_bins > 1) {                                       // a binned context: every group over the whole generation
-        std::vector<int32_t> b0(n_groups, 0), b1(n_groups, c->n_bins);
-        return daam_finalize_bins(c, key_group, n_groups, nullptr, b0.data(), b1.data(), n_rows, out, group_stride, stream);
-    }
-    int total_keys = 0;
-    daam_key_offset(c, 0, nullptr, &total_keys);
-    std::vector<int> rows(n_groups);
-    for (int g = 0; g < n_groups; ++g) rows[g] = fin_rows(c, n_rows[g]);
-    const size_t plane = (size_t)c->out_side * c->out_side;
-    for (int g = 0; g + 1 < n_groups; ++g)
-        if (group_stride < (size_t)rows[g] * plane)
-            return fail(DAAM_E_INVALID, "group_stride %zu < %d rows of %zu floats: groups would overlap", group_stride, rows[g], plane);
-    std::vector<uint8_t> mask(total_keys > 0 ? total_keys : 1);
-    std::vector<int> n_of(n_groups, 0);
-    for (int i = 0; i < total_keys; ++i) {
-        const int g = key_group[i];
-        if (g < -1 || g >= n_groups) return fail(DAAM_E_INVALID, "key_group[%d] = %d not in -1..%d", i, g, n_groups - 1);
-        mask[i] = g >= 0;
-        if (g >= 0) ++n_of[g];
-    }
-    for (int g = 0; g < n_groups; ++g)
-        if (!n_of[g]) return fail(DAAM_E_NOMAPS, "no heat maps selected for group %d", g);
-    if (n_groups == 1) return daam_finalize(c, mask.data(), n_rows[0], out, stream);
-    DeviceGuard on_device(c);
-    hipStream_t s = (hipStream_t)stream;
-    c->prep_out = c->fold_out = nullptr;
-    return fin_groups_core(c, c->layers.data(), c->max_layers, c->acc_dtype, key_group, total_keys, n_groups, n_rows, rows, n_of, mask,
-                           out, group_stride, s, true, true);
-}
-
-// daam_finalize_bins: daam_finalize_groups with a window range per group.  Groups that each take ONE window (and no two of them
-// the same key of the same window) run the grouped class kernels straight on the windows' planes: the key space of the call is
-// the window slots' (window-major), and the per-group key table points at window bin_begin[g].  Otherwise one launch of
-// finalize_bin_sum_kernel adds every selected key's windows [bin_begin[g], bin_end[g]) into f32 scratch planes (rows
-// [0, n_rows[g]) only) and the grouped class kernels run on those, dispatched on THEIR dtype (f32).
-int daam_finalize_bins(DaamCtx* c, const int32_t* key_group, int n_groups, const int32_t* group_set, const int32_t* bin_begin,
-                       const int32_t* bin_end, const int32_t* n_rows, float* out, size_t group_stride, void* stream)
-{
-    if (!c || !out || !key_group || !bin_begin || !bin_end || !n_rows) return fail(DAAM_E_INVALID, "NULL argument");
-    if (n_groups < 1 || n_groups > kFinMaxGroups) return fail(DAAM_E_INVALID, "n_groups %d not in 1..%d", n_groups, kFinMaxGroups);
-    if (!c->pending.empty()) return fail(DAAM_E_STATE, "finalize with deferred taps pending: flush first");
-    const int nb = std::max(1, c->n_bins);
-    int n_sets = group_set ? 0 : n_groups;
-    for (int g = 0; g < n_groups; ++g) {
-        if (bin_begin[g] < 0 || bin_end[g] > nb || bin_begin[g] >= bin_end[g])
-            return fail(DAAM_E_INVALID, "group %d: window range [%d, %d) not a non-empty part of [0, %d)", g, bin_begin[g], bin_end[g], nb);
-        if (group_set) {
-            if (group_set[g] < 0) return fail(DAAM_E_INVALID, "group_set[%d] = %d < 0", g, group_set[g]);
-            n_sets = std::max(n_sets, group_set[g] + 1);
-        }
-    }
-    auto set_of = [&](int g) { return group_set ? group_set[g] : g; };
-    int total_keys = 0;
-    daam_key_offset(c, 0, nullptr, &total_keys);
-    std::vector<int> rows(n_groups);
-    for (int g = 0; g < n_groups; ++g) rows[g] = fin_rows(c, n_rows[g]);
-    const size_t plane = (size_t)c->out_side * c->out_side;
-    for (int g = 0; g + 1 < n_groups; ++g)
-        if (group_stride < (size_t)rows[g] * plane)
-            return fail(DAAM_E_INVALID, "group_stride %zu < %d rows of %zu floats: groups would overlap", group_stride, rows[g], plane);
-    std::vector<int> per_set(n_sets, 0);
-    for (int i = 0; i < total_keys; ++i) {
-        const int k = key_group[i];
-        // (with group_set: keys of a set no group takes are simply not selected)
-        if (k < -1 || (!group_set && k >= n_sets)) return fail(DAAM_E_INVALID, "key_group[%d] = %d not in -1..%d", i, k, n_sets - 1);
-        if (k >= 0 && k < n_sets) ++per_set[k];
-    }
-    std::vector<int> n_of(n_groups, 0);
-    for (int g = 0; g < n_groups; ++g)
-        if (!(n_of[g] = per_set[set_of(g)])) return fail(DAAM_E_NOMAPS, "no heat maps selected for group %d", g);
-    bool direct = true;
-    for (int g = 0; g < n_groups && direct; ++g) {
-        direct = bin_end[g] - bin_begin[g] == 1;
-        for (int h = 0; h < g && direct; ++h) direct = !(bin_begin[h] == bin_begin[g] && set_of(h) == set_of(g));
-    }
-    if (direct && nb == 1 && !group_set) return daam_finalize_groups(c, key_group, n_groups, n_rows, out, group_stride, stream);
-    DeviceGuard on_device(c);
-    hipStream_t s = (hipStream_t)stream;
-    c->prep_out = c->fold_out = nullptr;
-    if (direct) {
-        // key (window b, key i) of the slots' key space = b * total_keys + i
-        const size_t ext = (size_t)nb * total_keys;
-        std::vector<int32_t> kg(ext > 0 ? ext : 1, -1);
-        std::vector<uint8_t> mask(ext > 0 ? ext : 1, 0);
-        for (int g = 0; g < n_groups; ++g)
-            for (int i = 0; i < total_keys; ++i)
-                if (key_group[i] == set_of(g)) {
-                    kg[(size_t)bin_begin[g] * total_keys + i] = g;
-                    mask[(size_t)bin_begin[g] * total_keys + i] = 1;
-                }
-        return fin_groups_core(c, c->layers.data(), nb * c->max_layers, c->acc_dtype, kg.data(), (int)ext, n_groups, n_rows, rows, n_of,
-                               mask, out, group_stride, s, false, true);
-    }
-    // ---- window-range reduction: one task per (group, selected key)
-    std::vector<std::pair<int, int>> key_at;                  // key i -> (layer, head)
-    for (int l = 0; l < c->max_layers; ++l)
-        if (c->layers[l].configured)
-            for (int h = 0; h < c->layers[l].heads; ++h) key_at.push_back({l, h});
-    const size_t elem = acc_elem(c->acc_dtype);
-    const int per_tile = bin_sum_elems_per_tile(c->acc_dtype);
-    std::vector<BinSumTask> tasks;
-    std::vector<Layer> vl;                                     // the scratch planes as one-head layers
-    std::vector<int32_t> vg;
-    size_t scratch = 0;
-    int tiles = 0;
-    for (int g = 0; g < n_groups; ++g)
-        for (int i = 0; i < total_keys; ++i) {
-            if (key_group[i] != set_of(g)) continue;
-            const Layer& l = c->layers[(size_t)bin_begin[g] * c->max_layers + key_at[i].first];
-            BinSumTask t;
-            memset(&t, 0, sizeof t);
-            t.src = static_cast<const char*>(l.acc) + (size_t)key_at[i].second * c->tokens * l.hw * elem;
-            t.dst = reinterpret_cast<float*>(scratch);             // offset for now
-            t.win_stride = (int64_t)(l.bytes / elem);
-            t.n_elem = (int64_t)rows[g] * l.hw;
-            t.n_win = bin_end[g] - bin_begin[g];
-            t.tile_begin = tiles;
-            t.vec = ((reinterpret_cast<uintptr_t>(t.src) | l.bytes) & 15) == 0;
-            tiles += (int)((t.n_elem + per_tile - 1) / per_tile);
-            tasks.push_back(t);
-            Layer v;
-            v.configured = true;
-            v.heads = 1;
-            v.side = l.side;
-            v.hw = l.hw;
-            v.factor = l.factor;
-            v.tab = l.tab;
-            v.bytes = (size_t)t.n_elem * sizeof(float);
-            vl.push_back(v);
-            vg.push_back(g);
-            scratch += (v.bytes + 255) & ~size_t(255);
-        }
-    if (scratch > c->bin_scratch_bytes) {
-        if (c->bin_scratch) {
-            HIP_TRY(hipDeviceSynchronize());                   // earlier finalize calls may still read the old scratch
-            HIP_TRY(hipFree(c->bin_scratch));
-            c->bin_scratch = nullptr;
-            c->bin_scratch_bytes = 0;
-        }
-        HIP_TRY(hipMalloc(&c->bin_scratch, scratch));
-        c->bin_scratch_bytes = scratch;
-    }
-    for (size_t j = 0; j < tasks.size(); ++j) {
-        tasks[j].dst = reinterpret_cast<float*>(static_cast<char*>(c->bin_scratch) + reinterpret_cast<size_t>(tasks[j].dst));
-        tasks[j].vec = tasks[j].vec && (reinterpret_cast<uintptr_t>(tasks[j].dst) & 15) == 0;
-        vl[j].acc = tasks[j].dst;
-    }
-    // the windows' sums must hold what they should: a zeroing still owed since daam_reset comes first
-    for (int g = 0; g < n_groups; ++g)
-        for (int b = bin_begin[g]; b < bin_end[g]; ++b)
-            for (int l = 0; l < c->max_layers; ++l) {
-                int zrc = ensure_zeroed(c->layers[(size_t)b * c->max_layers + l], s);
-                if (zrc) return zrc;
-            }
-    const size_t tab_bytes = tasks.size() * sizeof(BinSumTask);
-    if (tab_bytes > Ring::kBytes) return fail(DAAM_E_UNSUPPORTED, "%zu window-range tasks in one call", tasks.size());
-    if (c->profile) (void)hipEventRecord(c->prof_event(1, 0), s);   // timed: the reduction and the class kernels
-    size_t off = 0;
-    HIP_TRY(c->ring.alloc(tab_bytes, &off));
-    memcpy(c->ring.host + off, tasks.data(), tab_bytes);
-    hipError_t e = c->ring.commit(off, tab_bytes, s);
-    BinSumLaunch BL;
-    BL.tasks = reinterpret_cast<const BinSumTask*>(c->ring.dev + off);
-    BL.n_tasks = (int32_t)tasks.size();
-    BL.n_tiles = tiles;
-    if (e == hipSuccess) e = launch_finalize_bin_sum(BL, c->acc_dtype, s);
-    (void)c->ring.release(s);
-    if (e != hipSuccess) return fail((int)e, "window-range reduction: %s", hipGetErrorString(e));
-    std::vector<uint8_t> mask(vg.size(), 1);
-    int rc = fin_groups_core(c, vl.data(), (int)vl.size(), DAAM_F32, vg.data(), (int)vg.size(), n_groups, n_rows, rows, n_of, mask, out,
-                             group_stride, s, false, false);
-    if (!rc) c->last_kernels[1] = std::string("finalize_bin_sum_kernel<") + dtype_name(c->acc_dtype) + ">+" + c->last_kernels[1];
-    return rc;
-}
 
 int daam_epilogue_normalize(float* maps, int n_rows, int side, void* stream)
 {

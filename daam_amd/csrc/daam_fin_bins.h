@@ -1,5 +1,5 @@
 // Window-range reduction of a time-binned context (daam_finalize_bins, include/daam_hip.h): the host side
-// (daam_api.hip) and the kernel (daam_fin_bins.hip) share this table.  Kept out of daam_types.h so that no existing
+// (daam_finalize_api.hip) and the kernel (daam_fin_bins.hip) share this table.  Kept out of daam_types.h so that no existing
 // kernel's translation unit changes.
 #pragma once
 #include "daam_types.h"

@@ -1,4 +1,4 @@
-// Device-visible tables shared by the host API (daam_api.hip) and the kernels.
+// Device-visible tables shared by the host API (daam_api.hip, daam_finalize_api.hip) and the kernels.
 // gfx950 only; no other architecture is targeted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,7 +116,7 @@ struct FinLaunch {
     int32_t max_side;       // largest non-identity side among the keys (LDS carve-up)
     const void* mfma_ops;   // x2 MFMA finalize: [2 nt][64 lanes][6] 16-byte operand pieces (host-built), or NULL
     // x2 MFMA finalize: chunk c covers the keys [chunk_begin[c], chunk_begin[c + 1]) (even boundaries; its two key lanes take
-    // them alternately); see finalize_chunk_ranges() in daam_api.hip.
+    // them alternately); see finalize_chunk_ranges() in daam_finalize_api.hip.
     int16_t chunk_begin[kFinMaxChunks + 1];
 };
 
