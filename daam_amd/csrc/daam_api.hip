@@ -2,6 +2,7 @@
 // Owns no activations; owns (optionally) the running sums, the bicubic tap tables and a
 // small pinned upload ring for the per-launch device tables.
 #include "daam_ctx.h"
+#include "daam_tap_walk.h"
 
 #include <algorithm>
 #include <cmath>
@@ -140,7 +141,7 @@ hipError_t ensure_aux(DaamCtx* c)
 static const char* tap_kernel_name(int kd)
 {
     return (kd == 65 || kd == 66) ? "tap_d64_kernel" : (kd == 67 || kd == 69) ? "tap_wide_kernel" : kd == 70 ? "tap_chunk_kernel"
-           : kd == 71 ? "tap_slab_kernel" : kd == 72 ? "tap_pair_kernel" : kd ? "tap_mfma_kernel" : "tap_generic_kernel";
+           : kd == 71 ? "tap_slab_kernel" : kd == 72 ? "tap_pair_kernel" : kd == 73 ? "tap_walk_kernel" : kd ? "tap_mfma_kernel" : "tap_generic_kernel";
 }
 
 extern "C" {
@@ -203,6 +204,8 @@ int daam_ctx_create(int max_layers, int tokens, int out_side, int acc_dtype, Daa
     c->tap_chunked = !tck || !tck[0] ? 2 : tck[0] == '1' ? 1 : tck[0] == '0' ? 0 : 2;
     const char* ntp = getenv("DAAM_TAP_PAIR");              // 1: chains that share Q pair up on tap_pair_kernel; default: separate chains
     c->no_tap_pair = !(ntp && ntp[0] == '1');
+    const char* twk = getenv("DAAM_TAP_WALK");              // 1: a layer's time windows walk through one workgroup chain (tap_walk_kernel)
+    c->tap_walk = twk && twk[0] == '1';
 
     // softmax flavour of the MFMA tap: fast (default; exponent by one mixed-precision FMA, ~1e-6 relative,
     // same deviation class as the f32 summation order of q.k -- DESIGN.md section 3.1) or compensated
@@ -803,19 +806,37 @@ int daam_tap_flush(DaamCtx* c, void* stream)
             }
         }
     }
+    // Time windows, only with DAAM_TAP_WALK=1: when the launch of the head_dim-64 chains would take the eight-wave FULL64
+    // tap_d64_kernel and some layer has recorded steps in two or more of its window slots, every such chain goes to tap_walk_kernel
+    // (kind 73): one table entry per LAYER that walks the layer's windows in recorded order -- a layer with one window in this flush as a
+    // walk of length one, rather than a second kernel beside it.  Bit-identical sums (tests/test_gpu_tap_walk.py).
+    if (c->tap_walk && c->n_bins > 1 && !c->no_w8) {
+        const int kd = in_dtype == DAAM_BF16 ? 66 : 65;
+        bool full64 = true, multi = false;
+        std::vector<char> seen(c->max_layers, 0);
+        for (size_t i = 0; i < order.size(); ++i) {
+            if (kind[i] != kd) continue;
+            full64 = full64 && per[i][0]->d.head_dim == 64;
+            multi = multi || seen[order[i] % c->max_layers]++;
+        }
+        if (multi && full64 && tap_walk_has(in_dtype, c->acc_dtype) && tap_d64_tile_pixels(in_dtype, c->acc_dtype, 1) == tap_walk_tile_pixels())
+            for (int& k2 : kind)
+                if (k2 == kd) k2 = 73;
+    }
     std::vector<int> kinds;
     for (int kd : kind)
         if (kd >= 0 && std::find(kinds.begin(), kinds.end(), kd) == kinds.end()) kinds.push_back(kd);
     int rc = 0;
     int grid_total = 0;
     // pass 1: the tables of every kernel kind -> ring -> device (all on the caller's stream)
-    struct Prepared { int kd; TapLaunch L; int max_d; int min_d; int all_round; size_t ring_begin, ring_end; bool w8; };
+    struct Prepared { int kd; TapLaunch L; int max_d; int min_d; int all_round; size_t ring_begin, ring_end; bool w8;
+                      const WalkEntry* walk_entries; const WalkWin* walk_wins; };
     std::vector<Prepared> prepared;
     for (int kd : kinds) {
         size_t n_layers = 0, n_ptrs = 0;
         for (size_t i = 0; i < order.size(); ++i)
             if (kind[i] == kd) { ++n_layers; n_ptrs += per[i].size() * (kd == 72 ? 2 : 1); }
-        int tile = kd == 72 ? tap_pair_tile_pixels() : kd == 71 ? tap_slab_tile_pixels() : kd ? tap_mfma_tile_pixels() : kTapPixels;
+        int tile = kd == 73 ? tap_walk_tile_pixels() : kd == 72 ? tap_pair_tile_pixels() : kd == 71 ? tap_slab_tile_pixels() : kd ? tap_mfma_tile_pixels() : kTapPixels;
         bool w8 = false;
         if ((kd == 65 || kd == 66) && !c->no_w8) {
             // head_dim-64 launches with fp16 Q / K and fp16 sums: 256-pixel tiles on eight-wave workgroups (one K tile for twice the pixels)
@@ -835,6 +856,33 @@ int daam_tap_flush(DaamCtx* c, void* stream)
         // entry with 16-pixel tiles (see below)
         struct Ent { size_t i; int rank, px_begin, px_end, tile; };
         std::vector<Ent> ents;
+        // walk kernel (73): entry = the window chains (indices into `order`) of one layer, in recorded order.  An entry ends where its
+        // steps would pass the launch's step limit (the pointer table in LDS holds the ENTRY's steps) or where a window's shape or
+        // strides differ from the entry's: the layer then has another entry for its later windows -- never a window in two entries.
+        std::vector<std::vector<size_t>> walk;
+        size_t n_walk_wins = 0;
+        if (kd == 73) {
+            std::vector<int> open(c->max_layers, -1), steps_in;
+            auto same_shape = [](const DaamQKDesc& o, const DaamQKDesc& d) {
+                return o.batch == d.batch && o.heads == d.heads && o.head_dim == d.head_dim && o.hw == d.hw && o.round_logits == d.round_logits &&
+                       o.scale == d.scale && o.q_stride_b == d.q_stride_b && o.q_stride_h == d.q_stride_h && o.q_stride_p == d.q_stride_p &&
+                       o.k_stride_b == d.k_stride_b && o.k_stride_h == d.k_stride_h && o.k_stride_t == d.k_stride_t;
+            };
+            for (size_t i = 0; i < order.size(); ++i) {
+                if (kind[i] != kd) continue;
+                const int layer = order[i] % c->max_layers;
+                int e = open[layer];
+                if (e < 0 || steps_in[e] + (int)per[i].size() > tap_mfma_max_steps() || !same_shape(per[walk[e][0]][0]->d, per[i][0]->d)) {
+                    e = open[layer] = (int)walk.size();
+                    walk.emplace_back();
+                    steps_in.push_back(0);
+                }
+                walk[e].push_back(i);
+                steps_in[e] += (int)per[i].size();
+                ++n_walk_wins;
+            }
+            for (auto& g : walk) ents.push_back({g[0], 0, 0, per[g[0]][0]->d.hw, tile});
+        }
         // slab kernel: the layers segment by segment (one cost per workgroup each): head_dim 160 first (few, light workgroups with the longest
         // step chains), 40 (the bulk), 80 (short chains), and last the TAIL of the head_dim-40 layers in half-size workgroups: 2.2 rounds of
         // indivisible 50-step chains leave a third of the chip idle for the last 100 us of the launch; half-length units empty it more evenly
@@ -844,7 +892,7 @@ int daam_tap_flush(DaamCtx* c, void* stream)
         // every tail share (LABNOTES R6.2) -- a chain's speed depends on what shares its CU, which the model does not know.
         auto seg_rank = [](int d) { return d == 160 ? 0 : d == 40 ? 1 : 2; };
         for (size_t i = 0; i < order.size(); ++i) {
-            if (kind[i] != kd) continue;
+            if (kind[i] != kd || kd == 73) continue;
             const DaamQKDesc& d0 = per[i][0]->d;
             if (kd != 71) { ents.push_back({i, 0, 0, d0.hw, tile}); continue; }
             const int r = seg_rank(d0.head_dim);
@@ -855,16 +903,33 @@ int daam_tap_flush(DaamCtx* c, void* stream)
         if (kd == 71) std::stable_sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.rank < b.rank; });
         n_layers = ents.size();
         // tap_pair_kernel: the chain-B entries follow the chain-A entries, one per pair, in the same order
-        const size_t bytes_layers = n_layers * (kd == 72 ? 2 : 1) * sizeof(TapLayer), bytes = bytes_layers + n_ptrs * sizeof(TapPtr);
+        // tap_walk_kernel: its window table and per-entry window ranges follow the step pointers
+        const size_t bytes_layers = n_layers * (kd == 72 ? 2 : 1) * sizeof(TapLayer), bytes_tap = bytes_layers + n_ptrs * sizeof(TapPtr);
+        const size_t bytes = bytes_tap + n_walk_wins * sizeof(WalkWin) + walk.size() * sizeof(WalkEntry);
         size_t off = 0;
         hipError_t e = c->ring.alloc(bytes, &off);
         if (e != hipSuccess) { rc = fail((int)e, "upload ring: %s", hipGetErrorString(e)); break; }
         TapLayer* hl = reinterpret_cast<TapLayer*>(c->ring.host + off);
         TapPtr* hp = reinterpret_cast<TapPtr*>(c->ring.host + off + bytes_layers);
+        WalkWin* hw_wins = reinterpret_cast<WalkWin*>(c->ring.host + off + bytes_tap);
+        WalkEntry* hw_ents = reinterpret_cast<WalkEntry*>(c->ring.host + off + bytes_tap + n_walk_wins * sizeof(WalkWin));
         int wg = 0, ptr = 0, max_d = 0, min_d = 1 << 30, all_round = 1;
         std::vector<int> ptr_of(order.size(), -1);             // a layer's step pointers are written once, both of its entries point at them
+        for (size_t e = 0, win = 0; e < walk.size(); ++e) {     // (73) a window's step pointers follow the previous window's
+            hw_ents[e].win_begin = (int32_t)win;
+            hw_ents[e].n_win = (int32_t)walk[e].size();
+            for (size_t i : walk[e]) {
+                const Layer& wl = c->layers[order[i]];
+                hw_wins[win].acc = wl.acc;
+                hw_wins[win].n_steps = (int32_t)per[i].size();
+                hw_wins[win].fresh = wl.dirty ? 0 : 1;
+                ++win;
+                ptr_of[i] = ptr;
+                for (auto* p : per[i]) { hp[ptr].q = p->q; hp[ptr].k = p->k; ++ptr; }
+            }
+        }
         for (size_t i = 0; i < order.size(); ++i) {
-            if (kind[i] != kd) continue;
+            if (kind[i] != kd || kd == 73) continue;
             for (size_t m = 0; m < (kd == 72 ? 2u : 1u); ++m) {
                 const size_t ci = m ? (size_t)partner[i] : i;
                 ptr_of[ci] = ptr;
@@ -879,6 +944,10 @@ int daam_tap_flush(DaamCtx* c, void* stream)
             fill_layer(c, c->layers[order[en.i]], v[0]->d, en.tile, &hl[j]);
             hl[j].wg_begin = wg;
             hl[j].n_steps = (int)v.size();
+            if (kd == 73) {                                  // the entry's steps: every window's
+                hl[j].n_steps = 0;
+                for (size_t i : walk[j]) hl[j].n_steps += (int)per[i].size();
+            }
             hl[j].ptr_begin = ptr_of[en.i];
             hl[j].px_begin = en.px_begin;
             hl[j].px_end = en.px_end;
@@ -928,7 +997,9 @@ int daam_tap_flush(DaamCtx* c, void* stream)
         pr.max_d = max_d;
         pr.min_d = min_d;
         pr.all_round = all_round;
-        pr.w8 = w8;
+        pr.w8 = w8 || kd == 73;
+        pr.walk_entries = reinterpret_cast<const WalkEntry*>(c->ring.dev + off + bytes_tap + n_walk_wins * sizeof(WalkWin));
+        pr.walk_wins = reinterpret_cast<const WalkWin*>(c->ring.dev + off + bytes_tap);
         pr.ring_begin = c->ring.cur_begin;
         pr.ring_end = c->ring.cur_end;
         prepared.push_back(pr);
@@ -1000,7 +1071,10 @@ int daam_tap_flush(DaamCtx* c, void* stream)
             if (ge != hipSuccess) { rc = fail((int)ge, "start gate: %s", hipGetErrorString(ge)); break; }
         }
         int grid = 0;
-        hipError_t e = (pr.kd == 65 || pr.kd == 66) ? launch_tap_d64(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d == 64 && pr.max_d == 64, pr.w8 ? 1 : 0, ks, &grid, &c->last_lds[0])
+        WalkLaunch WL;
+        if (pr.kd == 73) { WL.L = pr.L; WL.entries = pr.walk_entries; WL.wins = pr.walk_wins; }
+        hipError_t e = pr.kd == 73 ? launch_tap_walk(WL, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
+                     : (pr.kd == 65 || pr.kd == 66) ? launch_tap_d64(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d == 64 && pr.max_d == 64, pr.w8 ? 1 : 0, ks, &grid, &c->last_lds[0])
                      : (pr.kd == 67 || pr.kd == 69) ? launch_tap_wide(pr.L, c->acc_dtype, pr.max_d, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
                      : pr.kd == 70 ? launch_tap_chunk(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d != pr.max_d, ks, &grid, &c->last_lds[0])
                      : pr.kd == 71 ? launch_tap_slab(pr.L, c->acc_dtype, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])

@@ -276,6 +276,8 @@ struct DaamCtx {
     int fast_exp = 0;
     int no_d64 = 0;
     int no_tap_pair = 0;
+    int tap_walk = 0;                 // DAAM_TAP_WALK=1: a binned context's eight-wave head_dim-64 launches walk each layer's windows in one
+                                      // workgroup chain (tap_walk_kernel, daam_tap_walk.hip) instead of one chain per window
     int slab_tail_pct = 25;           // DAAM_SLAB_TAIL: percent of a head_dim-40 layer's pixels the slab kernel takes in 16-pixel tiles at the end of the launch
                                       // (SD-v1.5, alternating on one box: 0 -> 2390, 25 -> 2415, 50 -> 2316, 100 -> 2204 maps/s: half-size units cost K traffic)
     int tap_slab = 1;                 // tap_slab_kernel (daam_tap_slab.hip): deferred fp16 layers of head_dim 40 / 80 / 160 in 640-byte slabs of adjacent heads

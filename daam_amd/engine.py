@@ -305,7 +305,9 @@ class HeatMapEngine:
         self._sync_native()
 
     def _park_key(self) -> tuple:
-        return (str(self.device), self.n_layers, self.tokens, self.out_side, self.acc_dtype, self.time_bins, self.n_probes)
+        # DAAM_TAP_WALK is read when a native context is created: a context parked without the switch is not adopted with it
+        walk = os.environ.get('DAAM_TAP_WALK', '')[:1] == '1'
+        return (str(self.device), self.n_layers, self.tokens, self.out_side, self.acc_dtype, walk, self.time_bins, self.n_probes)
 
     def close(self) -> None:
         if self.ctx is not None:
