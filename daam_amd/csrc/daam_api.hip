@@ -190,6 +190,8 @@ int daam_ctx_create(int max_layers, int tokens, int out_side, int acc_dtype, Daa
     c->no_paired_finalize = npf && npf[0] == '1';
     const char* w8 = getenv("DAAM_TAP_W8");
     c->no_w8 = w8 && w8[0] == '0';
+    const char* tsy = getenv("DAAM_TAP_SYNC");              // 0: the head_dim-64 tap's step protocol before the counted waits
+    c->tap_sync = !(tsy && tsy[0] == '0');
     const char* nfc = getenv("DAAM_NO_FIN_CACHE");
     c->no_fin_cache = nfc && nfc[0] == '1';
     const char* n16 = getenv("DAAM_NO_D64");            // debugging: 32x32-tile kernel also for head_dim 64
@@ -565,7 +567,7 @@ int daam_tap_qk(DaamCtx* c, int layer, const void* q, const void* k, const DaamQ
     L.wgs_per_xcd = (L.total_wgs + 7) / 8;
     c->last_block[0] = 256;
     const int kd1 = mfma ? mfma_kind(c, *d, q, k) : 0;
-    hipError_t e = (kd1 == 65 || kd1 == 66) ? launch_tap_d64(L, d->in_dtype, c->acc_dtype, c->fast_exp && d->round_logits, d->head_dim == 64, 0, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
+    hipError_t e = (kd1 == 65 || kd1 == 66) ? launch_tap_d64(L, d->in_dtype, c->acc_dtype, c->fast_exp && d->round_logits, d->head_dim == 64, 0, c->tap_sync, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
                    : (kd1 == 67 || kd1 == 69) ? launch_tap_wide(L, c->acc_dtype, d->head_dim, c->fast_exp && d->round_logits, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
                    : kd1 == 70 ? launch_tap_chunk(L, d->in_dtype, c->acc_dtype, c->fast_exp && d->round_logits, 0, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
                    : mfma ? launch_tap_mfma(L, c->acc_dtype, d->head_dim, c->fast_exp && d->round_logits, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
@@ -1074,7 +1076,7 @@ int daam_tap_flush(DaamCtx* c, void* stream)
         WalkLaunch WL;
         if (pr.kd == 73) { WL.L = pr.L; WL.entries = pr.walk_entries; WL.wins = pr.walk_wins; }
         hipError_t e = pr.kd == 73 ? launch_tap_walk(WL, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
-                     : (pr.kd == 65 || pr.kd == 66) ? launch_tap_d64(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d == 64 && pr.max_d == 64, pr.w8 ? 1 : 0, ks, &grid, &c->last_lds[0])
+                     : (pr.kd == 65 || pr.kd == 66) ? launch_tap_d64(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d == 64 && pr.max_d == 64, pr.w8 ? 1 : 0, c->tap_sync, ks, &grid, &c->last_lds[0])
                      : (pr.kd == 67 || pr.kd == 69) ? launch_tap_wide(pr.L, c->acc_dtype, pr.max_d, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
                      : pr.kd == 70 ? launch_tap_chunk(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d != pr.max_d, ks, &grid, &c->last_lds[0])
                      : pr.kd == 71 ? launch_tap_slab(pr.L, c->acc_dtype, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])

@@ -17,7 +17,7 @@ bool tap_mfma_supported(int in_dtype, int head_dim, int tokens, int hw, int64_t 
 int tap_mfma_tile_pixels();
 int tap_mfma_ksteps(int head_dim);
 int tap_mfma_max_steps();
-hipError_t launch_tap_d64(const TapLaunch&, int in_dtype, int acc_dtype, int fast_exp, int full64, int waves8, hipStream_t, int*, int*);
+hipError_t launch_tap_d64(const TapLaunch&, int in_dtype, int acc_dtype, int fast_exp, int full64, int waves8, int counted, hipStream_t, int*, int*);
 int tap_d64_tile_pixels(int in_dtype, int acc_dtype, int full64);
 bool tap_wide_supported(int in_dtype, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
                         const void* q, const void* k);
@@ -223,6 +223,7 @@ struct DaamCtx {
     bool fin_tab_valid = false;
     hipStream_t fin_tab_stream = nullptr;   // the stream its upload and its readers were enqueued on
     int no_w8 = 0;                    // debugging / A-B: DAAM_TAP_W8=0 (head_dim-64 launches on 4-wave workgroups of 128 pixels instead of 8-wave / 256)
+    int tap_sync = 1;                 // A-B: DAAM_TAP_SYNC=0 (head_dim-64 DMA launches: vmcnt(0) + __syncthreads() per step instead of counted waits + one raw barrier)
     int no_fin_cache = 0;             // debugging / A-B: DAAM_NO_FIN_CACHE=1 (tables through the ring + zeroing in every call)
     // daam_finalize_prepare: the output buffer the next daam_finalize accumulates into has been zeroed already (prep_*), or is to
     // be zeroed by the table-upload kernel of the next tap launch (fold_*)
