@@ -785,3 +785,45 @@ def test_header_is_plain_c_and_links_from_c(tmp_path):
                     '-L' + libdir, '-l:' + os.path.basename(_native.LIB_PATH), '-Wl,-rpath,' + libdir], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split(None, 2)
     assert int(out[0]) == _native.ABI_VERSION and int(out[1]) == -1 and 'tokens' in out[2]
+
+
+def test_attend_supported_accept_decline_table():
+    """``daam_attend_supported`` is a pure function of the descriptor and four pointer values (no device call): what it accepts
+    and declines, one condition at a time around a contiguous fp16 head_dim-64 call."""
+    import __graft_entry__
+    __graft_entry__.build()
+    from daam_amd import _native as nat
+    lib = nat.load()
+    heads, d, hw = 2, 64, 256
+    c = heads * d
+    ptrs = dict(q=0x10000, k=0x20000, v=0x30000, out=0x40000)
+
+    def supported(ptr=None, **change):
+        fields = dict(in_dtype=nat.DAAM_F16, batch=2, heads=heads, hw=hw, tokens=77, head_dim=d, round_logits=1, scale=d ** -0.5,
+                      q_stride_b=hw * c, q_stride_h=d, q_stride_p=c, k_stride_b=77 * c, k_stride_h=d, k_stride_t=c,
+                      v_stride_b=77 * c, v_stride_h=d, v_stride_t=c, o_stride_b=hw * c, o_stride_h=d, o_stride_p=c)
+        fields.update(change)
+        outer = {key: fields.pop(key) for key in list(fields) if key[:2] in ('v_', 'o_')}
+        desc = nat.AttendDesc(qk=nat.QKDesc(**fields), **outer)
+        p = dict(ptrs, **(ptr or {}))
+        return lib.daam_attend_supported(ctypes.byref(desc), p['q'], p['k'], p['v'], p['out'])
+
+    assert supported() == 1
+    assert supported(in_dtype=nat.DAAM_BF16) == 1
+    assert supported(in_dtype=nat.DAAM_F32) == 0
+    assert supported(head_dim=160) == 1 and supported(head_dim=168) == 0 and supported(head_dim=60) == 0
+    assert supported(tokens=76) == 0
+    assert supported(hw=252) == 0
+    strides = ('q_stride_b', 'q_stride_h', 'q_stride_p', 'k_stride_b', 'k_stride_h', 'k_stride_t', 'v_stride_b', 'v_stride_h',
+               'v_stride_t', 'o_stride_b', 'o_stride_h', 'o_stride_p')
+    for name in strides:
+        assert supported(**{name: c + 8}) == 1, name                             # any multiple of 8 elements
+        assert supported(**{name: 0}) == 1, name                                 # (a broadcast tensor)
+        assert supported(**{name: c + 4}) == 0, name                             # rows not 16-byte aligned
+        assert supported(**{name: -c}) == 0, name
+        assert supported(**{name: (1 << 40) - 8}) == 1 and supported(**{name: 1 << 40}) == 0, name
+    for name, value in ptrs.items():
+        assert supported(ptr={name: value + 16}) == 1, name
+        for off in (2, 4, 8):
+            assert supported(ptr={name: value + off}) == 0, (name, off)
+        assert supported(ptr={name: None}) == 0, name                            # NULL
