@@ -126,8 +126,11 @@ __global__ __launch_bounds__(256) void finalize_up_grouped_kernel(const FinGroup
 //   k-step ks2, slot (g, i)  <->  y = 16 ks2 + 8 (i >> 2) + 4g + (i & 3) = the row held in register
 //   8 ks2 + i.  The constant Wy pieces are built once per wave with the same permutation: no lane
 //   exchange, no LDS.  T is fed as an fp16 pair hi + lo (hi = fp16(T), lo = fp16(T - hi)): 22
-//   significant bits, |error| <= 2^-22 |T| -- below the f32 rounding noise of the four-tap sums it
-//   feeds, far inside the tolerance of the bicubic parity tests; Wy is exact in fp16 (host check).
+//   significant bits, |error| <= 2^-22 |T|, while lo is a normal fp16 number, i.e. for |T| >= 2^-3 -- below the f32 rounding
+//   noise of the four-tap sums it feeds.  For smaller |T| lo is an fp16 subnormal and the error is ABSOLUTE, half a subnormal
+//   ulp = 2^-25 (2^-17 of a token row at level 2^-8, all of a row at 2^-25); |T| > 65504 makes hi inf.  Hence the documented
+//   domain of the MFMA x2 kernels (include/daam_hip.h, finalize): plane values |v| <= 2^15, per map element
+//   err <= 2^-19 * (row maximum) + 2^-23 (tests/test_gpu_finalize_domain.py).  Wy is exact in fp16 (host check).
 //   VALU work per plane: the hi/lo split + clamp / accumulate of the outputs (~165 instructions per 64x64
 //   plane, against ~300 for a register y pass with lane exchanges); the MFMA pipe does 4 + 16 instructions.
 //   Measured (SDXL-1024, 1000 planes x 77 tokens): ~68 us either way -- the kernel is bound by its

@@ -28,7 +28,8 @@
 //     at [0][0] and [63][31]) and pass 1 has a third MFMA whose A operand -- plane columns 0..7 | 24..31 -- is selected from the two pieces
 //     the lane holds anyway (4 v_cndmask): 11 MFMAs per plane.  T, pass 2, clamp and the folded same-size keys (identity MFMA in bf16) as above;
 //   * f32 planes (accumulate='float32'): 4 KiB per plane, ring of 8; a lane reads its A pieces as 16 floats and splits them into an
-//     fp16 hi + lo pair exactly like pass 2 splits T (2^-22 relative, the same error pass 2 already has): 4 pass-1 MFMAs and 32 more
+//     fp16 hi + lo pair exactly like pass 2 splits T (2^-22 relative for |v| >= 2^-3, an absolute 2^-25 below that, where lo is an fp16
+//     subnormal, inf above 65504 -- the same error and the same domain pass 2 already has, see daam_finalize.hip): 4 pass-1 MFMAs and 32 more
 //     VALU instructions per plane.  The 16-byte pieces of a 128-byte plane row sit XOR-swizzled in the ring (piece ^ ((row >> 1) & 7), done
 //     on the DMA's per-lane SOURCE address): the four ds_read_b128 of an A operand are conflict-free.  The folded same-size keys take the
 //     VALU (every lane loads the elements it owns in the C/D layout, acc += max(P, 0)).

@@ -802,7 +802,14 @@ class HeatMapEngine:
         return out
 
     def tap_probs(self, layer: int, probs: torch.Tensor, factor: int) -> None:
-        """``probs`` [B*H, hw, tokens] as returned by ``get_attention_scores`` (trace.py:276)."""
+        """``probs`` [B*H, hw, tokens] as returned by ``get_attention_scores`` (trace.py:276).
+
+        Arbitrary planes (not probabilities) may be fed this way, but the default finalize of 32 x 32 layers onto a 64 x 64 map runs on
+        the matrix cores and has a value domain (include/daam_hip.h, finalize): the running sums must stay within ``|v| <= 2^15`` (no
+        check; beyond it the map turns inf / NaN), and every map element carries an absolute error floor of 2^-23 on top of 2^-19 of its
+        token row's maximum -- token rows summed far below 2^-10 lose their low bits.  ``DAAM_NO_PIPE_FINALIZE=1`` (bf16 / f32 sums) or
+        ``DAAM_NO_MFMA_FINALIZE=1`` (fp16 sums), set before the trace starts, select the exact f32 kernels, which take any finite
+        planes."""
         self._require_device(probs)
         self._ensure_ctx(probs.dtype)
         self.flush()
@@ -816,7 +823,9 @@ class HeatMapEngine:
 
     def add_map(self, factor: int, layer: int, head: int, heat_map: torch.Tensor) -> None:
         """``RawHeatMapCollection.update`` called by hand (heatmap.py:153-156): rare, done with a
-        torch add on the layer's buffer."""
+        torch add on the layer's buffer.  The value domain of ``tap_probs`` applies to what the sums hold afterwards: 32 x 32 layers
+        finalized onto a 64 x 64 map need ``|v| <= 2^15`` and carry an absolute error floor of 2^-23 per map element unless the exact
+        route is selected (``DAAM_NO_PIPE_FINALIZE=1`` for bf16 / f32 sums, ``DAAM_NO_MFMA_FINALIZE=1`` for fp16 sums)."""
         if self.time_bins is not None:
             raise RuntimeError('daam_amd: update() is not supported on a trace with time_bins (which window would it add to?)')
         self._require_device(heat_map)

@@ -178,7 +178,23 @@ DAAM_API int daam_attend(DaamCtx* ctx, int layer, const void* q, const void* k, 
  * (trace.py:127), so a caller that knows the prompt passes that count and the planes of the
  * other tokens are neither read nor written: the rows [0, n_rows) of `out` are overwritten, the
  * rows [n_rows, tokens) -- if `out` has them at all -- are left untouched.  n_rows <= 0 or
- * > tokens means all `tokens` rows. */
+ * > tokens means all `tokens` rows.
+ *
+ * Value domain and accuracy (daam_finalize, daam_finalize_groups, daam_finalize_bins), per token row t against the exact result,
+ * err_t = max over pixels of |out - exact|, rowmax_t = max over pixels of |exact| (tests/test_gpu_finalize_domain.py):
+ *   - every class but 32 -> 64, and the 32 -> 64 class on the LDS kernel: f32 arithmetic on any finite planes,
+ *     err_t <= 2^-19 * rowmax_t at any magnitude (measured: 2^-21.7).
+ *   - the 32 -> 64 class on the matrix cores (the default for a 64 x 64 output: finalize_up32_pipe_kernel for all three dtypes of
+ *     the sums, finalize_up32_mfma_kernel / finalize_up32_same_kernel for fp16 sums under DAAM_NO_PIPE_FINALIZE=1) passes f32 numbers
+ *     -- the intermediate of the two bicubic passes, and the planes themselves when the sums are f32 -- to the fp16 matrix pipe as
+ *     hi = fp16(v), lo = fp16(v - hi).  Two consequences.  DOMAIN: plane values must satisfy |v| <= 2^15 (beyond 65504 / 1.28, hi
+ *     is inf and the map NaN; nothing checks this).  FLOOR: lo is an fp16 subnormal whenever |v| < 2^-3, so the split's error
+ *     is an absolute 2^-25 rather than relative: err_t <= 2^-19 * rowmax_t + 2^-23 per map element (measured: 2^-20.2 and 2^-23.9),
+ *     whatever the planes' magnitude.  Running sums of probabilities (<= steps x batch, start-of-text row of order steps) sit inside
+ *     the domain and a content token whose row maximum is 1e-3 keeps 13 bits; planes fed through daam_tap_probs or summed far below
+ *     2^-10 do not.  fp16 subnormal plane elements pass through the matrix pipe exactly (not flushed on gfx950).
+ *   - the exact routes: DAAM_NO_PIPE_FINALIZE=1 for bf16 and f32 sums (LDS kernel), DAAM_NO_MFMA_FINALIZE=1 for fp16 sums (and
+ *     every dtype); both are read when the context is created. */
 DAAM_API int daam_key_offset(DaamCtx* ctx, int layer, int* offset, int* total);
 DAAM_API int daam_finalize(DaamCtx* ctx, const uint8_t* key_mask, int n_rows, float* out, void* stream);
 /* Optional, ABI v5 (`n_rows`: v6): announce the `key_mask` / `n_rows` / `out` / `stream` of the daam_finalize call that follows, BEFORE the deferred taps are
