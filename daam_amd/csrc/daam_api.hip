@@ -1,8 +1,8 @@
-// Host side of libdaam_hip.so: the C ABI declared in include/daam_hip.h.
+// Host side of libdaam_hip.so: the C ABI declared in include/daam_hip.h -- context, layers, time bins, attend, probs tap, epilogue,
+// profiling and the clock monitor (the tap entry points: daam_tap_api.hip; the finalize ones: daam_finalize_api.hip).
 // Owns no activations; owns (optionally) the running sums, the bicubic tap tables and a
 // small pinned upload ring for the per-launch device tables.
 #include "daam_ctx.h"
-#include "daam_tap_walk.h"
 
 #include <algorithm>
 #include <cmath>
@@ -25,9 +25,6 @@ int fail(int code, const char* fmt, ...)
     g_err = buf;
     return code;
 }
-
-// which running-sum dtypes a pipeline dtype may feed: its own (the reference's behaviour) or f32
-static bool dtypes_compatible(int in_dtype, int acc_dtype) { return acc_dtype == DAAM_F32 || acc_dtype == in_dtype; }
 
 // torch upsample_bicubic2d, align_corners=False, antialias=False:
 // scale = in / out in f32; src = scale * (dst + 0.5) - 0.5 (NOT clamped for cubic);
@@ -138,12 +135,6 @@ hipError_t ensure_aux(DaamCtx* c)
     return ae;
 }
 
-static const char* tap_kernel_name(int kd)
-{
-    return (kd == 65 || kd == 66) ? "tap_d64_kernel" : (kd == 67 || kd == 69) ? "tap_wide_kernel" : kd == 70 ? "tap_chunk_kernel"
-           : kd == 71 ? "tap_slab_kernel" : kd == 72 ? "tap_pair_kernel" : kd == 73 ? "tap_walk_kernel" : kd ? "tap_mfma_kernel" : "tap_generic_kernel";
-}
-
 extern "C" {
 
 int daam_abi_version(void) { return DAAM_ABI_VERSION; }
@@ -176,44 +167,35 @@ int daam_ctx_create(int max_layers, int tokens, int out_side, int acc_dtype, Daa
         daam_ctx_destroy(c);
         return fail((int)e, "context allocation: %s", hipGetErrorString(e));
     }
-    const char* fg = getenv("DAAM_FORCE_GENERIC");
-    c->force_generic = fg && fg[0] == '1';
-    const char* nm = getenv("DAAM_NO_MFMA_FINALIZE");
-    c->no_mfma_finalize = nm && nm[0] == '1';
-    const char* nfs = getenv("DAAM_NO_FOLD_SAME");
-    c->no_fold_same = nfs && nfs[0] == '1';
-    const char* nsg = getenv("DAAM_NO_START_GATE");
-    c->no_start_gate = nsg && nsg[0] == '1';
-    const char* npp = getenv("DAAM_NO_PIPE_FINALIZE");
-    c->no_pipe_finalize = npp && npp[0] == '1';
-    const char* npf = getenv("DAAM_NO_PAIRED_FINALIZE");
-    c->no_paired_finalize = npf && npf[0] == '1';
-    const char* w8 = getenv("DAAM_TAP_W8");
-    c->no_w8 = w8 && w8[0] == '0';
-    const char* tsy = getenv("DAAM_TAP_SYNC");              // 0: the head_dim-64 tap's step protocol before the counted waits
-    c->tap_sync = !(tsy && tsy[0] == '0');
-    const char* nfc = getenv("DAAM_NO_FIN_CACHE");
-    c->no_fin_cache = nfc && nfc[0] == '1';
-    const char* n16 = getenv("DAAM_NO_D64");            // debugging: 32x32-tile kernel also for head_dim 64
-    c->no_d64 = n16 && n16[0] == '1';
-    const char* nss = getenv("DAAM_NO_SIDE_STREAM");        // debugging / A-B: every tap kernel of a flush on the caller's stream
-    c->no_side_stream = nss && nss[0] == '1';
+    // A/B and debugging switches, read once per context: `field` = `value` when the variable's first character is `match`, else !value
+    static const struct { const char* name; int DaamCtx::*field; char match; int value; } kSwitches[] = {
+        {"DAAM_FORCE_GENERIC", &DaamCtx::force_generic, '1', 1},
+        {"DAAM_NO_MFMA_FINALIZE", &DaamCtx::no_mfma_finalize, '1', 1},
+        {"DAAM_NO_FOLD_SAME", &DaamCtx::no_fold_same, '1', 1},
+        {"DAAM_NO_START_GATE", &DaamCtx::no_start_gate, '1', 1},
+        {"DAAM_NO_PIPE_FINALIZE", &DaamCtx::no_pipe_finalize, '1', 1},
+        {"DAAM_NO_PAIRED_FINALIZE", &DaamCtx::no_paired_finalize, '1', 1},
+        {"DAAM_TAP_W8", &DaamCtx::no_w8, '0', 1},
+        {"DAAM_TAP_SYNC", &DaamCtx::tap_sync, '0', 0},            // 0: the head_dim-64 tap's step protocol before the counted waits
+        {"DAAM_NO_FIN_CACHE", &DaamCtx::no_fin_cache, '1', 1},
+        {"DAAM_NO_D64", &DaamCtx::no_d64, '1', 1},                // debugging: 32x32-tile kernel also for head_dim 64
+        {"DAAM_NO_SIDE_STREAM", &DaamCtx::no_side_stream, '1', 1},   // debugging / A-B: every tap kernel of a flush on the caller's stream
+        {"DAAM_TAP_SLAB", &DaamCtx::tap_slab, '0', 0},
+        {"DAAM_TAP_PAIR", &DaamCtx::no_tap_pair, '1', 0},         // 1: chains that share Q pair up on tap_pair_kernel; default: separate chains
+        {"DAAM_TAP_WALK", &DaamCtx::tap_walk, '1', 1},            // 1: a layer's time windows walk through one workgroup chain (tap_walk_kernel)
+        // softmax flavour of the MFMA tap: fast (default; exponent by one mixed-precision FMA, ~1e-6 relative,
+        // same deviation class as the f32 summation order of q.k -- DESIGN.md section 3.1) or compensated
+        // (DAAM_STRICT_EXP=1: ~1 ulp f32 like the reference's expf)
+        {"DAAM_STRICT_EXP", &DaamCtx::fast_exp, '1', 0},
+    };
+    for (const auto& sw : kSwitches) {
+        const char* v = getenv(sw.name);
+        c->*sw.field = (v && v[0] == sw.match) ? sw.value : !sw.value;
+    }
     const char* stl = getenv("DAAM_SLAB_TAIL");
     if (stl && stl[0]) c->slab_tail_pct = std::max(0, std::min(100, atoi(stl)));
-    const char* tsl = getenv("DAAM_TAP_SLAB");
-    c->tap_slab = !(tsl && tsl[0] == '0');
     const char* tck = getenv("DAAM_TAP_CHUNKED");           // daam_tap_chunk.hip: unset = launches that mix head dims, 1 = always, 0 = never
-    c->tap_chunked = !tck || !tck[0] ? 2 : tck[0] == '1' ? 1 : tck[0] == '0' ? 0 : 2;
-    const char* ntp = getenv("DAAM_TAP_PAIR");              // 1: chains that share Q pair up on tap_pair_kernel; default: separate chains
-    c->no_tap_pair = !(ntp && ntp[0] == '1');
-    const char* twk = getenv("DAAM_TAP_WALK");              // 1: a layer's time windows walk through one workgroup chain (tap_walk_kernel)
-    c->tap_walk = twk && twk[0] == '1';
-
-    // softmax flavour of the MFMA tap: fast (default; exponent by one mixed-precision FMA, ~1e-6 relative,
-    // same deviation class as the f32 summation order of q.k -- DESIGN.md section 3.1) or compensated
-    // (DAAM_STRICT_EXP=1: ~1 ulp f32 like the reference's expf)
-    const char* se = getenv("DAAM_STRICT_EXP");
-    c->fast_exp = !(se && se[0] == '1');
+    c->tap_chunked = !tck ? 2 : tck[0] == '1' ? 1 : tck[0] == '0' ? 0 : 2;
     *out = c;
     return 0;
 }
@@ -410,177 +392,6 @@ int daam_reset(DaamCtx* c, void* stream)
     return 0;
 }
 
-static int check_qk(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d)
-{
-    if (!c || !d || !q || !k) return fail(DAAM_E_INVALID, "NULL argument");
-    if (layer < 0 || layer >= c->max_layers || !c->layers[layer].configured)
-        return fail(DAAM_E_STATE, "layer %d not configured", layer);
-    const Layer& l = c->layers[layer];
-    if (d->in_dtype != DAAM_F16 && d->in_dtype != DAAM_F32 && d->in_dtype != DAAM_BF16) return fail(DAAM_E_INVALID, "in_dtype %d", d->in_dtype);
-    if (!dtypes_compatible(d->in_dtype, c->acc_dtype))
-        return fail(DAAM_E_INVALID, "activations of dtype %d cannot feed running sums of dtype %d (own dtype or f32)", d->in_dtype, c->acc_dtype);
-    if (d->tokens != c->tokens) return fail(DAAM_E_INVALID, "tokens %d != context size %d (reference gate, trace.py:289)", d->tokens, c->tokens);
-    if (d->batch <= 0 || d->heads <= 0 || d->head_dim <= 0 || d->head_dim > 1024)
-        return fail(DAAM_E_INVALID, "batch %d heads %d head_dim %d", d->batch, d->heads, d->head_dim);
-    const int bh = d->batch * d->heads;
-    if (bh - bh / 2 != l.heads) return fail(DAAM_E_INVALID, "layer %d holds %d heads, call keeps %d", layer, l.heads, bh - bh / 2);
-    if (d->hw != l.hw) return fail(DAAM_E_INVALID, "layer %d holds %d positions, call has %d", layer, l.hw, d->hw);
-    return 0;
-}
-
-static void fill_layer(const DaamCtx* c, const Layer& l, const DaamQKDesc& d, int tile_pixels, TapLayer* t)
-{
-    const int bh = d.batch * d.heads;
-    t->acc = l.acc;
-    t->heads_kept = l.heads;
-    t->bh_first = bh / 2;
-    t->heads = d.heads;
-    t->hw = d.hw;
-    t->head_dim = d.head_dim;
-    t->tiles_per_head = (d.hw + tile_pixels - 1) / tile_pixels;
-    t->wg_begin = 0;
-    t->n_steps = 1;
-    t->ptr_begin = 0;
-    t->round_logits = d.round_logits;
-    t->scale = d.scale;
-    t->fresh = l.dirty ? 0 : 1;
-    t->px_begin = 0;
-    t->px_end = d.hw;
-    t->tile_px = tile_pixels;
-    t->q_sb = d.q_stride_b; t->q_sh = d.q_stride_h; t->q_sp = d.q_stride_p;
-    t->k_sb = d.k_stride_b; t->k_sh = d.k_stride_h; t->k_st = d.k_stride_t;
-    (void)c;
-}
-
-static bool use_d64_bf16(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k);
-static bool use_chunk(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k);
-
-static bool use_mfma(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k)
-{
-    if (c->force_generic) return false;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) return false;
-    if (d.in_dtype == DAAM_BF16) return use_d64_bf16(c, d, q, k) || use_chunk(c, d, q, k);
-    return tap_mfma_supported(d.in_dtype, d.head_dim, d.tokens, d.hw, d.q_stride_p, d.k_stride_t, d.q_stride_b,
-                              d.q_stride_h, d.k_stride_b, d.k_stride_h);
-}
-
-// kernel choice for an MFMA-capable call: 65 = 16x16-tile head_dim-64 kernel (default for d = 64),
-// else the k-step count of the generic 32x32-tile MFMA kernel
-static int mfma_kind(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k);
-
-// The specialised tap kernels address Q and K with 32-bit BYTE offsets from the tensor pointers: every element a call can
-// address -- (batch - 1) * stride_b + (heads - 1) * stride_h + (rows - 1) * row stride + head_dim -- must stay below 2^30 elements
-// (views into a large fused buffer with unusual strides fall back to the any-shape kernel instead of wrapping).
-static bool offsets_fit_32(const DaamQKDesc& d)
-{
-    const int64_t lim = (int64_t)1 << 30;
-    const int64_t s[] = {d.q_stride_b, d.q_stride_h, d.q_stride_p, d.k_stride_b, d.k_stride_h, d.k_stride_t};
-    for (int64_t v : s)
-        if (v < 0 || v >= lim) return false;
-    const int64_t q_max = (int64_t)(d.batch - 1) * d.q_stride_b + (int64_t)(d.heads - 1) * d.q_stride_h + (int64_t)(d.hw - 1) * d.q_stride_p + d.head_dim;
-    const int64_t k_max = (int64_t)(d.batch - 1) * d.k_stride_b + (int64_t)(d.heads - 1) * d.k_stride_h + (int64_t)(d.tokens - 1) * d.k_stride_t + d.head_dim;
-    return q_max < lim && k_max < lim;
-}
-
-static bool use_d64(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k)
-{
-    return !c->no_d64 && offsets_fit_32(d) && tap_d64_supported(d.head_dim, d.hw, d.q_stride_p, d.k_stride_t, d.q_stride_b, d.q_stride_h,
-                                           d.k_stride_b, d.k_stride_h, q, k);
-}
-
-// bf16 pipelines: only the 16x16-tile kernel has a bf16 variant (head_dim <= 64, 77 tokens, bf16-rounded logits);
-// everything else of a bf16 pipeline runs on the any-shape kernel
-static bool use_d64_bf16(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k)
-{
-    return d.in_dtype == DAAM_BF16 && !c->no_d64 && c->fast_exp && d.round_logits && d.tokens == 77 && d.hw % 8 == 0 && offsets_fit_32(d) &&
-           tap_d64_supported(d.head_dim, d.hw, d.q_stride_p, d.k_stride_t, d.q_stride_b, d.q_stride_h, d.k_stride_b,
-                             d.k_stride_h, q, k);
-}
-
-// 64 < head_dim <= 160 on fp16 pipelines (SD-v1.5's 80 / 160): the 16x16-tile kernel with 3 or 5 k-steps (daam_tap_wide.hip)
-static bool use_wide(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k)
-{
-    return !c->no_d64 && (c->acc_dtype == DAAM_F16 || c->acc_dtype == DAAM_F32) && offsets_fit_32(d) &&
-           (int64_t)d.batch * d.q_stride_b < ((int64_t)1 << 30) &&
-           tap_wide_supported(d.in_dtype, d.head_dim, d.hw, d.q_stride_p, d.k_stride_t, d.q_stride_b, d.q_stride_h, d.k_stride_b,
-                              d.k_stride_h, q, k);
-}
-
-// the chunked kernel (daam_tap_chunk.hip) can take this call: fp16 layers of any head_dim (multiple of 8, <= 256), and bf16 layers (bf16
-// or f32 sums, bf16-rounded logits, the fast softmax -- what the bf16 head_dim-64 kernel asks for; validated on the chip in round 4)
-static bool chunk_ok(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k)
-{
-    if (!c->tap_chunked || c->no_d64 || c->force_generic || d.tokens != 77 || !offsets_fit_32(d)) return false;
-    if (d.in_dtype == DAAM_BF16) {
-        if (!c->fast_exp || !d.round_logits || !(c->acc_dtype == DAAM_BF16 || c->acc_dtype == DAAM_F32)) return false;
-    } else if (!(c->acc_dtype == DAAM_F16 || c->acc_dtype == DAAM_F32)) {
-        return false;
-    }
-    return tap_chunk_supported(d.in_dtype, d.head_dim, d.hw, d.q_stride_p, d.k_stride_t, d.q_stride_b, d.q_stride_h, d.k_stride_b,
-                               d.k_stride_h, (int64_t)d.batch * d.q_stride_b, q, k);
-}
-
-// the slab kernel (daam_tap_slab.hip) can take this deferred call: fp16 Q / K, fp16 or f32 sums, head_dim 40 / 80 / 160 with the heads
-// adjacent in the rows
-static bool slab_ok(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k)
-{
-    if (!c->tap_slab || c->no_d64 || c->force_generic || d.tokens != 77 || d.in_dtype != DAAM_F16 || !offsets_fit_32(d)) return false;
-    if (!(c->acc_dtype == DAAM_F16 || c->acc_dtype == DAAM_F32)) return false;
-    return tap_slab_supported(d.in_dtype, d.batch, d.heads, d.head_dim, d.hw, d.q_stride_p, d.k_stride_t, d.q_stride_b, d.q_stride_h, d.k_stride_b,
-                              d.k_stride_h, (int64_t)d.batch * d.q_stride_b, q, k);
-}
-
-// DAAM_TAP_CHUNKED=1: every such call.  Default (2): the deferred launches that mix head dims (daam_tap_flush), and bf16 layers with
-// head_dim > 64 -- no other MFMA kernel has a bf16 form for them (the any-shape kernel is ~45x slower per step).
-static bool use_chunk(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k)
-{
-    if (c->tap_chunked == 1) return chunk_ok(c, d, q, k);
-    return c->tap_chunked == 2 && d.in_dtype == DAAM_BF16 && d.head_dim > 64 && chunk_ok(c, d, q, k);
-}
-
-static int mfma_kind(const DaamCtx* c, const DaamQKDesc& d, const void* q, const void* k)
-{
-    if (use_chunk(c, d, q, k)) return 70;
-    if (d.in_dtype == DAAM_BF16) return 66;                   // only reached when use_d64_bf16() holds
-    if (use_d64(c, d, q, k)) return 65;
-    if (use_wide(c, d, q, k)) return d.head_dim <= 96 ? 67 : 69;
-    return tap_mfma_ksteps(d.head_dim);
-}
-
-int daam_tap_qk(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d, void* stream)
-{
-    int rc = check_qk(c, layer, q, k, d);
-    if (rc) return rc;
-    if (!c->pending.empty()) return fail(DAAM_E_STATE, "immediate tap with deferred taps pending: flush first");
-    DeviceGuard on_device(c);
-    const int slot = c->slot_of(layer);                        // the window of this step (= layer without windows)
-    const bool mfma = use_mfma(c, *d, q, k);
-    if (!mfma && (rc = ensure_zeroed(c->layers[slot], (hipStream_t)stream))) return rc;
-    TapLaunch L;
-    memset(&L, 0, sizeof L);
-    fill_layer(c, c->layers[slot], *d, mfma ? tap_mfma_tile_pixels() : kTapPixels, &L.one);
-    L.one_ptr.q = q;
-    L.one_ptr.k = k;
-    L.n_layers = 1;
-    L.tokens = c->tokens;
-    L.total_wgs = L.one.heads_kept * L.one.tiles_per_head;
-    L.wgs_per_xcd = (L.total_wgs + 7) / 8;
-    c->last_block[0] = 256;
-    const int kd1 = mfma ? mfma_kind(c, *d, q, k) : 0;
-    hipError_t e = (kd1 == 65 || kd1 == 66) ? launch_tap_d64(L, d->in_dtype, c->acc_dtype, c->fast_exp && d->round_logits, d->head_dim == 64, 0, c->tap_sync, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
-                   : (kd1 == 67 || kd1 == 69) ? launch_tap_wide(L, c->acc_dtype, d->head_dim, c->fast_exp && d->round_logits, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
-                   : kd1 == 70 ? launch_tap_chunk(L, d->in_dtype, c->acc_dtype, c->fast_exp && d->round_logits, 0, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
-                   : mfma ? launch_tap_mfma(L, c->acc_dtype, d->head_dim, c->fast_exp && d->round_logits, (hipStream_t)stream, &c->last_grid[0], &c->last_lds[0])
-                        : launch_tap_generic(L, d->in_dtype, c->acc_dtype, d->head_dim, (hipStream_t)stream,
-                                             &c->last_grid[0], &c->last_lds[0]);
-    if (e != hipSuccess) return fail((int)e, "tap launch: %s", hipGetErrorString(e));
-    c->last_kernels[0] = tap_kernel_name(kd1);
-    c->layers[slot].dirty = true;
-    c->layers[slot].zero_pending = false;
-    ++c->tap_steps[layer];
-    return 0;
-}
-
 int daam_attend_supported(const DaamAttendDesc* d, const void* q, const void* k, const void* v, const void* out)
 {
     if (!d || !q || !k || !v || !out) return 0;
@@ -641,481 +452,6 @@ int daam_attend(DaamCtx* c, int layer, const void* q, const void* k, const void*
         ++c->tap_steps[layer];
     }
     return 0;
-}
-
-// record one validated call for `slot` (a layer, or a (window, layer) slot of a binned context)
-static int enqueue_slot(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d)
-{
-    if (!c->pending.empty() && c->pending.front().d.in_dtype != d->in_dtype)
-        return fail(DAAM_E_STATE, "mixed activation dtypes in one deferred batch: flush first");
-    if (c->pending_count.size() != c->layers.size()) {
-        c->pending_count.assign(c->layers.size(), 0);
-        c->pending_last.assign(c->layers.size(), -1);
-    }
-    if (c->pending_count[layer] > 0) {
-        // every recorded step of a layer must share shape and strides
-        const DaamQKDesc& o = c->pending[c->pending_last[layer]].d;
-        if (o.batch != d->batch || o.heads != d->heads || o.head_dim != d->head_dim ||
-            o.round_logits != d->round_logits || o.scale != d->scale || o.q_stride_b != d->q_stride_b ||
-            o.q_stride_h != d->q_stride_h || o.q_stride_p != d->q_stride_p || o.k_stride_b != d->k_stride_b ||
-            o.k_stride_h != d->k_stride_h || o.k_stride_t != d->k_stride_t)
-            return fail(DAAM_E_STATE, "layer %d changed shape inside a deferred batch: flush first", layer);
-        if (c->pending_count[layer] >= tap_mfma_max_steps())
-            return fail(DAAM_E_STATE, "layer %d already has %d un-flushed steps: flush first", layer,
-                        c->pending_count[layer]);
-    }
-    c->pending_last[layer] = (int)c->pending.size();
-    ++c->pending_count[layer];
-    c->pending.push_back({layer, q, k, *d});
-    return 0;
-}
-
-int daam_tap_qk_enqueue(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d)
-{
-    int rc = check_qk(c, layer, q, k, d);
-    if (rc) return rc;
-    rc = enqueue_slot(c, c->slot_of(layer), q, k, d);
-    if (!rc) ++c->tap_steps[layer];
-    return rc;
-}
-
-int daam_tap_qk_enqueue_many(DaamCtx* c, int n, const int32_t* layers, const void* const* q, const void* const* k,
-                             const DaamQKDesc* const* descs)
-{
-    if (!c || n < 0 || (n > 0 && (!layers || !q || !k || !descs))) return fail(DAAM_E_INVALID, "NULL argument");
-    const size_t before = c->pending.size();
-    const std::vector<int> steps_before = c->tap_steps;
-    for (int i = 0; i < n; ++i) {
-        int rc = daam_tap_qk_enqueue(c, layers[i], q[i], k[i], descs[i]);
-        if (rc) {
-            // all or nothing: rebuild the per-slot bookkeeping for the surviving prefix, and the step counts
-            std::vector<Pending> keep(c->pending.begin(), c->pending.begin() + before);
-            c->drop_pending();
-            c->tap_steps = steps_before;
-            for (auto& p : keep) (void)enqueue_slot(c, p.layer, p.q, p.k, &p.d);
-            return rc;
-        }
-    }
-    return 0;
-}
-
-int daam_tap_pending(DaamCtx* c, int* n_calls, int* max_steps)
-{
-    if (!c) return fail(DAAM_E_INVALID, "ctx is NULL");
-    std::vector<int> cnt(c->layers.size(), 0);
-    int mx = 0;
-    for (auto& p : c->pending) mx = std::max(mx, ++cnt[p.layer]);
-    if (n_calls) *n_calls = (int)c->pending.size();
-    if (max_steps) *max_steps = mx;
-    return 0;
-}
-
-int daam_tap_flush(DaamCtx* c, void* stream)
-{
-    if (!c) return fail(DAAM_E_INVALID, "ctx is NULL");
-    if (c->pending.empty()) return 0;
-    DeviceGuard on_device(c);
-    hipStream_t s = (hipStream_t)stream;
-    const int in_dtype = c->pending.front().d.in_dtype;
-    // group the recorded calls by layer (first-seen order, steps in recorded order), and the
-    // layers by kernel: MFMA k-step count ceil(d/16), or 0 = generic kernel.
-    std::vector<int> order;
-    std::vector<int> slot(c->layers.size(), -1);              // (a binned context: per (window, layer) slot)
-    std::vector<std::vector<const Pending*>> per;
-    std::vector<int> kind;
-    for (auto& p : c->pending) {
-        if (slot[p.layer] < 0) {
-            slot[p.layer] = (int)order.size();
-            order.push_back(p.layer);
-            per.emplace_back();
-            kind.push_back(tap_mfma_ksteps(p.d.head_dim));
-        }
-        const int i = slot[p.layer];
-        if (!use_mfma(c, p.d, p.q, p.k)) kind[i] = 0;
-        else if (kind[i] != 0) {
-            // every step of the layer must qualify for the specialised kernel, else the generic MFMA one
-            const int want = mfma_kind(c, p.d, p.q, p.k);
-            if (per[i].empty()) kind[i] = want;
-            else if (kind[i] != want) kind[i] = p.d.in_dtype == DAAM_BF16 ? 0 : tap_mfma_ksteps(p.d.head_dim);
-        }
-        per[i].push_back(&p);
-    }
-    // A launch that mixes head dims (SD-v1.5: 40 / 80 / 160 = the head_dim-64 kernel and the two wide ones side by side, whose LDS
-    // footprints keep them from sharing CUs): every such layer on the chunked kernel instead -- ONE kind of workgroup, one launch,
-    // no side streams, bit-identical sums (tests/test_gpu_chunked.py; +11 ... 13 % heat maps / s on the SD-v1.5 workload).
-    if (c->tap_chunked == 2) {
-        bool k65 = false, k67 = false, k69 = false;
-        for (int kd : kind) {
-            k65 = k65 || kd == 65;
-            k67 = k67 || kd == 67;
-            k69 = k69 || kd == 69;
-        }
-        bool k66 = false, k70 = false;                         // bf16 pipelines: head_dim <= 64 -> 66, wider heads -> 70 (use_chunk)
-        for (int kd : kind) {
-            k66 = k66 || kd == 66;
-            k70 = k70 || kd == 70;
-        }
-        if ((int)k65 + (int)k67 + (int)k69 >= 2 || (k66 && k70)) {   // (an SDXL launch -- one kind -- never gets here: no per-call checks)
-            bool all_ok = true;
-            for (size_t i = 0; i < kind.size() && all_ok; ++i)
-                if (kind[i] == 65 || kind[i] == 66 || kind[i] == 67 || kind[i] == 69)
-                    for (const Pending* p : per[i]) all_ok = all_ok && chunk_ok(c, p->d, p->q, p->k);
-            if (all_ok)
-                for (int& kd : kind)
-                    if (kd == 65 || kd == 66 || kd == 67 || kd == 69) kd = 70;
-        }
-    }
-    // fp16 layers of head_dim 40 / 80 / 160 (SD-v1.x) whose every recorded step qualifies: the slab kernel -- whole 128-byte lines of Q,
-    // ONE launch for the three head dims (bit-identical sums: tests/test_gpu_slab.py).  DAAM_TAP_CHUNKED=0 / 1 pin the older kernels.
-    if (c->tap_slab && c->tap_chunked == 2 && in_dtype == DAAM_F16) {
-        for (size_t i = 0; i < kind.size(); ++i) {
-            if (!(kind[i] == 65 || kind[i] == 67 || kind[i] == 69 || kind[i] == 70) || !tap_slab_heads(per[i][0]->d.head_dim)) continue;
-            bool ok = true;
-            for (const Pending* p : per[i]) ok = ok && slab_ok(c, p->d, p->q, p->k);
-            if (ok) kind[i] = 71;
-        }
-    }
-    // Chains that read the same recorded Q (probes): head_dim-64 fp16 chains with fp16 sums pair up on tap_pair_kernel -- chain A
-    // any such chain, chain B one whose K is the same pointer at every step (a probe); in recorded order: generation + probe 0, probe 1 +
-    // probe 2, ...  The partner's kind becomes -1 (it rides with its chain A).  Unpaired chains keep their kernel.  Only with DAAM_TAP_PAIR=1:
-    // measured slower than separate chains for one and two probes, 4 % faster for four, so separate chains are the default.
-    std::vector<int> partner(order.size(), -1);
-    if (!c->no_tap_pair && !c->no_w8 && in_dtype == DAAM_F16 && c->acc_dtype == DAAM_F16) {
-        auto fixed_k = [&](size_t i) {
-            for (const Pending* p : per[i]) if (p->k != per[i][0]->k) return false;
-            return true;
-        };
-        auto same_q = [&](size_t a, size_t b) {
-            if (per[a].size() != per[b].size()) return false;
-            const DaamQKDesc &x = per[a][0]->d, &y = per[b][0]->d;
-            if (x.head_dim != 64 || y.head_dim != 64 || x.hw != y.hw || x.heads != y.heads || x.batch != y.batch ||
-                x.q_stride_b != y.q_stride_b || x.q_stride_h != y.q_stride_h || x.q_stride_p != y.q_stride_p ||
-                x.k_stride_h != y.k_stride_h || x.k_stride_t != y.k_stride_t || x.scale != y.scale || x.round_logits != y.round_logits ||
-                c->layers[order[a]].heads != c->layers[order[b]].heads)
-                return false;
-            for (size_t st = 0; st < per[a].size(); ++st) if (per[a][st]->q != per[b][st]->q) return false;
-            return true;
-        };
-        for (size_t a = 0; a < order.size(); ++a) {
-            if (kind[a] != 65 || partner[a] >= 0) continue;
-            for (size_t b = a + 1; b < order.size(); ++b) {
-                if (kind[b] != 65 || partner[b] >= 0 || !fixed_k(b) || !same_q(a, b)) continue;
-                partner[a] = (int)b;
-                partner[b] = (int)a;
-                kind[a] = 72;
-                kind[b] = -1;
-                break;
-            }
-        }
-    }
-    // Time windows, only with DAAM_TAP_WALK=1: when the launch of the head_dim-64 chains would take the eight-wave FULL64
-    // tap_d64_kernel and some layer has recorded steps in two or more of its window slots, every such chain goes to tap_walk_kernel
-    // (kind 73): one table entry per LAYER that walks the layer's windows in recorded order -- a layer with one window in this flush as a
-    // walk of length one, rather than a second kernel beside it.  Bit-identical sums (tests/test_gpu_tap_walk.py).
-    if (c->tap_walk && c->n_bins > 1 && !c->no_w8) {
-        const int kd = in_dtype == DAAM_BF16 ? 66 : 65;
-        bool full64 = true, multi = false;
-        std::vector<char> seen(c->max_layers, 0);
-        for (size_t i = 0; i < order.size(); ++i) {
-            if (kind[i] != kd) continue;
-            full64 = full64 && per[i][0]->d.head_dim == 64;
-            multi = multi || seen[order[i] % c->max_layers]++;
-        }
-        if (multi && full64 && tap_walk_has(in_dtype, c->acc_dtype) && tap_d64_tile_pixels(in_dtype, c->acc_dtype, 1) == tap_walk_tile_pixels())
-            for (int& k2 : kind)
-                if (k2 == kd) k2 = 73;
-    }
-    std::vector<int> kinds;
-    for (int kd : kind)
-        if (kd >= 0 && std::find(kinds.begin(), kinds.end(), kd) == kinds.end()) kinds.push_back(kd);
-    int rc = 0;
-    int grid_total = 0;
-    // pass 1: the tables of every kernel kind -> ring -> device (all on the caller's stream)
-    struct Prepared { int kd; TapLaunch L; int max_d; int min_d; int all_round; size_t ring_begin, ring_end; bool w8;
-                      const WalkEntry* walk_entries; const WalkWin* walk_wins; };
-    std::vector<Prepared> prepared;
-    for (int kd : kinds) {
-        size_t n_layers = 0, n_ptrs = 0;
-        for (size_t i = 0; i < order.size(); ++i)
-            if (kind[i] == kd) { ++n_layers; n_ptrs += per[i].size() * (kd == 72 ? 2 : 1); }
-        int tile = kd == 73 ? tap_walk_tile_pixels() : kd == 72 ? tap_pair_tile_pixels() : kd == 71 ? tap_slab_tile_pixels() : kd ? tap_mfma_tile_pixels() : kTapPixels;
-        bool w8 = false;
-        if ((kd == 65 || kd == 66) && !c->no_w8) {
-            // head_dim-64 launches with fp16 Q / K and fp16 sums: 256-pixel tiles on eight-wave workgroups (one K tile for twice the pixels)
-            bool full64 = true;
-            for (size_t i = 0; i < order.size(); ++i)
-                if (kind[i] == kd) full64 = full64 && per[i][0]->d.head_dim == 64;
-            const int t8 = tap_d64_tile_pixels(in_dtype, c->acc_dtype, full64 ? 1 : 0);
-            w8 = t8 != tile;
-            tile = t8;
-        }
-        if (!kd) {                                           // the generic kernel reads the sums first
-            for (size_t i = 0; i < order.size() && !rc; ++i)
-                if (kind[i] == kd) rc = ensure_zeroed(c->layers[order[i]], s);
-            if (rc) break;
-        }
-        // table entries of this kind: one per layer -- except that the slab kernel (71) may take the LAST pixels of a head_dim-40 layer as a second
-        // entry with 16-pixel tiles (see below)
-        struct Ent { size_t i; int rank, px_begin, px_end, tile; };
-        std::vector<Ent> ents;
-        // walk kernel (73): entry = the window chains (indices into `order`) of one layer, in recorded order.  An entry ends where its
-        // steps would pass the launch's step limit (the pointer table in LDS holds the ENTRY's steps) or where a window's shape or
-        // strides differ from the entry's: the layer then has another entry for its later windows -- never a window in two entries.
-        std::vector<std::vector<size_t>> walk;
-        size_t n_walk_wins = 0;
-        if (kd == 73) {
-            std::vector<int> open(c->max_layers, -1), steps_in;
-            auto same_shape = [](const DaamQKDesc& o, const DaamQKDesc& d) {
-                return o.batch == d.batch && o.heads == d.heads && o.head_dim == d.head_dim && o.hw == d.hw && o.round_logits == d.round_logits &&
-                       o.scale == d.scale && o.q_stride_b == d.q_stride_b && o.q_stride_h == d.q_stride_h && o.q_stride_p == d.q_stride_p &&
-                       o.k_stride_b == d.k_stride_b && o.k_stride_h == d.k_stride_h && o.k_stride_t == d.k_stride_t;
-            };
-            for (size_t i = 0; i < order.size(); ++i) {
-                if (kind[i] != kd) continue;
-                const int layer = order[i] % c->max_layers;
-                int e = open[layer];
-                if (e < 0 || steps_in[e] + (int)per[i].size() > tap_mfma_max_steps() || !same_shape(per[walk[e][0]][0]->d, per[i][0]->d)) {
-                    e = open[layer] = (int)walk.size();
-                    walk.emplace_back();
-                    steps_in.push_back(0);
-                }
-                walk[e].push_back(i);
-                steps_in[e] += (int)per[i].size();
-                ++n_walk_wins;
-            }
-            for (auto& g : walk) ents.push_back({g[0], 0, 0, per[g[0]][0]->d.hw, tile});
-        }
-        // slab kernel: the layers segment by segment (one cost per workgroup each): head_dim 160 first (few, light workgroups with the longest
-        // step chains), 40 (the bulk), 80 (short chains), and last the TAIL of the head_dim-40 layers in half-size workgroups: 2.2 rounds of
-        // indivisible 50-step chains leave a third of the chip idle for the last 100 us of the launch; half-length units empty it more evenly
-        // (DAAM_SLAB_TAIL = percent of a head_dim-40 layer's pixels that go there; bit-identical sums either way).  Every XCD takes an eighth of
-        // each segment.  Round 6 searched the order with a list-scheduling model (tools/slab_order_model.py) and measured its best candidate
-        // ("columns": first halves heavy-first, second halves light-first, half-size units last) on the chip: 3 % SLOWER than this order for
-        // every tail share (LABNOTES R6.2) -- a chain's speed depends on what shares its CU, which the model does not know.
-        auto seg_rank = [](int d) { return d == 160 ? 0 : d == 40 ? 1 : 2; };
-        for (size_t i = 0; i < order.size(); ++i) {
-            if (kind[i] != kd || kd == 73) continue;
-            const DaamQKDesc& d0 = per[i][0]->d;
-            if (kd != 71) { ents.push_back({i, 0, 0, d0.hw, tile}); continue; }
-            const int r = seg_rank(d0.head_dim);
-            const int tail_px = (r == 1 && d0.hw >= 64) ? (int)((int64_t)d0.hw * c->slab_tail_pct / 100 / 32) * 32 : 0;
-            if (d0.hw - tail_px > 0) ents.push_back({i, r, 0, d0.hw - tail_px, tile});
-            if (tail_px > 0) ents.push_back({i, 3, d0.hw - tail_px, d0.hw, tile / 2});
-        }
-        if (kd == 71) std::stable_sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.rank < b.rank; });
-        n_layers = ents.size();
-        // tap_pair_kernel: the chain-B entries follow the chain-A entries, one per pair, in the same order
-        // tap_walk_kernel: its window table and per-entry window ranges follow the step pointers
-        const size_t bytes_layers = n_layers * (kd == 72 ? 2 : 1) * sizeof(TapLayer), bytes_tap = bytes_layers + n_ptrs * sizeof(TapPtr);
-        const size_t bytes = bytes_tap + n_walk_wins * sizeof(WalkWin) + walk.size() * sizeof(WalkEntry);
-        size_t off = 0;
-        hipError_t e = c->ring.alloc(bytes, &off);
-        if (e != hipSuccess) { rc = fail((int)e, "upload ring: %s", hipGetErrorString(e)); break; }
-        TapLayer* hl = reinterpret_cast<TapLayer*>(c->ring.host + off);
-        TapPtr* hp = reinterpret_cast<TapPtr*>(c->ring.host + off + bytes_layers);
-        WalkWin* hw_wins = reinterpret_cast<WalkWin*>(c->ring.host + off + bytes_tap);
-        WalkEntry* hw_ents = reinterpret_cast<WalkEntry*>(c->ring.host + off + bytes_tap + n_walk_wins * sizeof(WalkWin));
-        int wg = 0, ptr = 0, max_d = 0, min_d = 1 << 30, all_round = 1;
-        std::vector<int> ptr_of(order.size(), -1);             // a layer's step pointers are written once, both of its entries point at them
-        for (size_t e = 0, win = 0; e < walk.size(); ++e) {     // (73) a window's step pointers follow the previous window's
-            hw_ents[e].win_begin = (int32_t)win;
-            hw_ents[e].n_win = (int32_t)walk[e].size();
-            for (size_t i : walk[e]) {
-                const Layer& wl = c->layers[order[i]];
-                hw_wins[win].acc = wl.acc;
-                hw_wins[win].n_steps = (int32_t)per[i].size();
-                hw_wins[win].fresh = wl.dirty ? 0 : 1;
-                ++win;
-                ptr_of[i] = ptr;
-                for (auto* p : per[i]) { hp[ptr].q = p->q; hp[ptr].k = p->k; ++ptr; }
-            }
-        }
-        for (size_t i = 0; i < order.size(); ++i) {
-            if (kind[i] != kd || kd == 73) continue;
-            for (size_t m = 0; m < (kd == 72 ? 2u : 1u); ++m) {
-                const size_t ci = m ? (size_t)partner[i] : i;
-                ptr_of[ci] = ptr;
-                for (auto* p : per[ci]) { hp[ptr].q = p->q; hp[ptr].k = p->k; ++ptr; }
-            }
-        }
-        size_t j = 0;
-        int seg_begin[kMaxSlabSegs + 1] = {0}, n_seg = 0;
-        int last_rank = -1;
-        for (const Ent& en : ents) {
-            const auto& v = per[en.i];
-            fill_layer(c, c->layers[order[en.i]], v[0]->d, en.tile, &hl[j]);
-            hl[j].wg_begin = wg;
-            hl[j].n_steps = (int)v.size();
-            if (kd == 73) {                                  // the entry's steps: every window's
-                hl[j].n_steps = 0;
-                for (size_t i : walk[j]) hl[j].n_steps += (int)per[i].size();
-            }
-            hl[j].ptr_begin = ptr_of[en.i];
-            hl[j].px_begin = en.px_begin;
-            hl[j].px_end = en.px_end;
-            hl[j].tile_px = en.tile;
-            hl[j].tiles_per_head = (en.px_end - en.px_begin + en.tile - 1) / en.tile;
-            if (kd == 71) {
-                if (en.rank != last_rank) { seg_begin[n_seg++] = wg; last_rank = en.rank; }
-                wg += hl[j].heads_kept / tap_slab_heads(v[0]->d.head_dim) * hl[j].tiles_per_head;   // tiles_per_head = tiles per slab
-            } else {
-                wg += hl[j].heads_kept * hl[j].tiles_per_head;
-            }
-            max_d = std::max(max_d, v[0]->d.head_dim);
-            min_d = std::min(min_d, v[0]->d.head_dim);
-            all_round = all_round && v[0]->d.round_logits;
-            if (kd == 72) {                                  // chain B: its own sums, fresh flag, K batch stride and pointer pair
-                const size_t bi = (size_t)partner[en.i];
-                TapLayer& hb = hl[n_layers + j];
-                fill_layer(c, c->layers[order[bi]], per[bi][0]->d, en.tile, &hb);
-                hb.wg_begin = hl[j].wg_begin;
-                hb.n_steps = hl[j].n_steps;
-                hb.ptr_begin = ptr_of[bi];
-                hb.tiles_per_head = hl[j].tiles_per_head;
-            }
-            ++j;
-        }
-        seg_begin[n_seg] = wg;
-        // daam_finalize_prepare: the output of the finalize that follows this launch is cleared by this (first) upload kernel
-        const bool fold = c->fold_out && c->fold_stream == s;
-        e = c->ring.commit(off, bytes, s, fold ? c->fold_out : nullptr, fold ? c->fold_bytes : 0);
-        if (e != hipSuccess) { rc = fail((int)e, "table upload: %s", hipGetErrorString(e)); break; }
-        if (fold) {
-            c->prep_out = c->fold_out;
-            c->prep_stream = s;
-            c->fold_out = nullptr;
-        }
-        Prepared pr;
-        pr.kd = kd;
-        memset(&pr.L, 0, sizeof pr.L);
-        pr.L.layers = reinterpret_cast<const TapLayer*>(c->ring.dev + off);
-        pr.L.ptrs = reinterpret_cast<const TapPtr*>(c->ring.dev + off + bytes_layers);
-        pr.L.n_layers = (int)n_layers;
-        pr.L.tokens = c->tokens;
-        pr.L.total_wgs = wg;
-        pr.L.wgs_per_xcd = (wg + 7) / 8;
-        pr.L.n_seg = n_seg;
-        for (int k = 0; k <= kMaxSlabSegs; ++k) pr.L.seg_begin[k] = seg_begin[k];
-        pr.max_d = max_d;
-        pr.min_d = min_d;
-        pr.all_round = all_round;
-        pr.w8 = w8 || kd == 73;
-        pr.walk_entries = reinterpret_cast<const WalkEntry*>(c->ring.dev + off + bytes_tap + n_walk_wins * sizeof(WalkWin));
-        pr.walk_wins = reinterpret_cast<const WalkWin*>(c->ring.dev + off + bytes_tap);
-        pr.ring_begin = c->ring.cur_begin;
-        pr.ring_end = c->ring.cur_end;
-        prepared.push_back(pr);
-    }
-    // pass 2: one launch per kind.  A flush with several kinds (SD-v1.5: head_dim 40 / 80 / 160) has kernels of a
-    // few dozen to a few hundred workgroups x 50 sequential steps each, which leave most of the chip idle when run
-    // one after the other.  The largest stays on the caller's stream, every other kind gets its own auxiliary
-    // non-blocking stream, forked from / joined to the caller's stream by events (all tables are uploaded before
-    // the fork) and launched FIRST so that its few workgroups are resident when the large grid fills the rest.
-    const bool side = !rc && prepared.size() > 1 && prepared.size() <= (size_t)DaamCtx::kAux + 1 && !c->no_side_stream;
-    if (side) {
-        hipError_t ae = ensure_aux(c);
-        if (ae != hipSuccess) rc = fail((int)ae, "auxiliary streams: %s", hipGetErrorString(ae));
-    }
-    size_t main_idx = 0;
-    for (size_t i = 1; i < prepared.size(); ++i)
-        if (prepared[i].L.total_wgs > prepared[main_idx].L.total_wgs) main_idx = i;
-    const bool ev_started = c->profile && !rc && !prepared.empty();
-    if (ev_started) (void)hipEventRecord(c->prof_event(0, 0), s);
-    bool forked = false;
-    if (side && !rc) {
-        if (hipEventRecord(c->aux_fork, s) != hipSuccess) rc = fail(DAAM_E_STATE, "stream fork failed");
-        else forked = true;
-    }
-    std::vector<size_t> launch_order;                        // side kinds first, the main one last
-    for (size_t i = 0; i < prepared.size(); ++i)
-        if (!forked || i != main_idx) launch_order.push_back(i);
-    if (forked) launch_order.push_back(main_idx);
-    int n_side = 0;
-    // start gate: the side kernels' workgroups count themselves in, the main kernel waits (one wave, bounded) until they are
-    // resident -- only for the kernels that carry the counter (the MFMA kinds).
-    // A gate that runs into its 200 us timeout means the side kernels were NOT running beside the caller's stream at that moment (one
-    // hardware queue, GPU_MAX_HW_QUEUES; or another process held the GPU): every gated flush then pays the 200 us for nothing.  The
-    // timeout counter is pinned host memory the gate kernels bump; the host reads it here WITHOUT synchronising, so it lags the
-    // enqueued flushes by however many are still in flight.  Rule (robust against that lag): since the gate was last armed, at least
-    // three timeouts AND at least half of the gated flushes enqueued so far timed out -> the gate rests for 64 flushes (said once),
-    // then is armed again with fresh counts.
-    if (forked && c->gate_timeouts) {
-        const unsigned now = *reinterpret_cast<volatile unsigned*>(c->gate_timeouts);
-        if (c->gate_off_until && c->n_flushes >= c->gate_off_until) { c->gate_off_until = 0; c->gate_timeouts_seen = now; c->gate_enqueued = 0; }
-        if (!c->gate_off_until) {
-            const unsigned timeouts = now - c->gate_timeouts_seen;         // since armed (unsigned wrap-around is fine)
-            if (timeouts >= 3 && 2 * (unsigned long long)timeouts >= c->gate_enqueued) {
-                c->gate_off_until = c->n_flushes + 64;
-                if (!c->gate_said) {
-                    c->gate_said = true;
-                    fprintf(stderr, "libdaam_hip: the start gate of %u of %llu multi-kernel tap launches timed out (side streams not concurrent with "
-                                    "the caller's stream); the gate rests for 64 launches\n", timeouts, c->gate_enqueued);
-                }
-            }
-        }
-    }
-    bool gate = forked && !c->no_start_gate && !c->gate_off_until && c->d_started;
-    for (size_t i = 0; i < prepared.size(); ++i)
-        if (i != main_idx && !prepared[i].kd) gate = false;
-    unsigned gate_wgs = 0;
-    std::string launched_names;
-    for (size_t pi : launch_order) {
-        if (rc) break;
-        Prepared& pr = prepared[pi];
-        hipStream_t ks = s;
-        if (forked && pi != main_idx) {
-            ks = c->aux_stream[n_side];
-            if (hipStreamWaitEvent(ks, c->aux_fork, 0) != hipSuccess) { rc = fail(DAAM_E_STATE, "stream fork failed"); break; }
-            if (gate) { pr.L.started = c->d_started; gate_wgs += (unsigned)pr.L.total_wgs; }
-        } else if (gate && gate_wgs) {
-            c->started_target += gate_wgs;                     // unsigned wrap-around is fine: the kernel compares differences
-            hipError_t ge = launch_start_gate(c->d_started, c->started_target, 200, c->gate_timeouts_dev, s);
-            if (ge != hipSuccess) { rc = fail((int)ge, "start gate: %s", hipGetErrorString(ge)); break; }
-        }
-        int grid = 0;
-        WalkLaunch WL;
-        if (pr.kd == 73) { WL.L = pr.L; WL.entries = pr.walk_entries; WL.wins = pr.walk_wins; }
-        hipError_t e = pr.kd == 73 ? launch_tap_walk(WL, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
-                     : (pr.kd == 65 || pr.kd == 66) ? launch_tap_d64(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d == 64 && pr.max_d == 64, pr.w8 ? 1 : 0, c->tap_sync, ks, &grid, &c->last_lds[0])
-                     : (pr.kd == 67 || pr.kd == 69) ? launch_tap_wide(pr.L, c->acc_dtype, pr.max_d, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
-                     : pr.kd == 70 ? launch_tap_chunk(pr.L, in_dtype, c->acc_dtype, c->fast_exp && pr.all_round, pr.min_d != pr.max_d, ks, &grid, &c->last_lds[0])
-                     : pr.kd == 71 ? launch_tap_slab(pr.L, c->acc_dtype, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
-                     : pr.kd == 72 ? launch_tap_pair(pr.L, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
-                     : pr.kd ? launch_tap_mfma(pr.L, c->acc_dtype, pr.max_d, c->fast_exp && pr.all_round, ks, &grid, &c->last_lds[0])
-                             : launch_tap_generic(pr.L, in_dtype, c->acc_dtype, pr.max_d, ks, &grid, &c->last_lds[0]);
-        grid_total += grid;
-        if (e != hipSuccess) { rc = fail((int)e, "tap launch: %s", hipGetErrorString(e)); break; }
-        launched_names += (launched_names.empty() ? "" : "+") + std::string(tap_kernel_name(pr.kd));
-        e = c->ring.release_range(pr.ring_begin, pr.ring_end, ks);
-        if (e != hipSuccess) { rc = fail((int)e, "event record: %s", hipGetErrorString(e)); break; }
-        if (ks != s) {
-            if (hipEventRecord(c->aux_join[n_side], ks) != hipSuccess) { rc = fail(DAAM_E_STATE, "stream join failed"); break; }
-            ++n_side;
-        }
-        for (size_t i = 0; i < order.size(); ++i)
-            if (kind[i] == pr.kd || (pr.kd == 72 && kind[i] == -1)) { c->layers[order[i]].dirty = true; c->layers[order[i]].zero_pending = false; }
-    }
-    // a flush that failed part-way may have announced side workgroups that never started: counter and target would disagree for
-    // good (every later gate a silent no-op or a full timeout), so the context stops gating
-    if (rc && gate) c->no_start_gate = 1;
-    if (forked && gate && gate_wgs != 0) ++c->gate_enqueued;
-    // join (after the main kernel is enqueued): the caller's stream continues when every side kernel is done
-    for (int i = 0; i < n_side; ++i)
-        if (hipStreamWaitEvent(s, c->aux_join[i], 0) != hipSuccess) rc = rc ? rc : fail(DAAM_E_STATE, "stream join failed");
-    if (c->profile && ev_started) { (void)hipEventRecord(c->prof_event(0, 1), s); ++c->hist_count[0]; }
-    c->last_grid[0] = grid_total;
-    c->last_block[0] = 256;
-    for (auto& pr : prepared)
-        if (pr.w8 || pr.kd == 71 || pr.kd == 72) c->last_block[0] = 512;
-    c->last_kernels[0] = launched_names;
-    c->last_flush_kernels = (int)launch_order.size();
-    c->last_flush_side = n_side;
-    c->last_flush_steps = 0;
-    for (auto& v : per) c->last_flush_steps = std::max(c->last_flush_steps, (int)v.size());
-    ++c->n_flushes;
-    c->drop_pending();
-    c->fold_out = nullptr;                                     // one-shot: never carried to a later launch
-    return rc;
 }
 
 int daam_tap_probs(DaamCtx* c, int layer, const void* probs, int in_dtype, int batch_heads, int hw, int tokens,

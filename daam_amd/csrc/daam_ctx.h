@@ -1,5 +1,6 @@
-// Host-only internals of libdaam_hip.so shared by the two halves of the C ABI (daam_api.hip: context, layers, taps, profiling;
-// daam_finalize_api.hip: the finalize entry points): the kernel files' host launchers, the context and its helpers.
+// Host-only internals of libdaam_hip.so shared by the three parts of the C ABI (daam_api.hip: context, layers, attend, profiling;
+// daam_tap_api.hip: the tap entry points; daam_finalize_api.hip: the finalize entry points): the kernel files' host launchers, the
+// context and its helpers.
 #pragma once
 #include "daam_types.h"
 #include "daam_fin_bins.h"
@@ -12,23 +13,18 @@
 namespace daam {
 hipError_t launch_tap_generic(const TapLaunch&, int, int, int, hipStream_t, int*, int*);
 hipError_t launch_tap_mfma(const TapLaunch&, int acc_dtype, int max_d, int fast_exp, hipStream_t, int*, int*);
-bool tap_mfma_supported(int in_dtype, int head_dim, int tokens, int hw, int64_t q_sp, int64_t k_st,
-                        int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh);
+bool tap_mfma_supported(const DaamQKDesc&, const void* q, const void* k);
 int tap_mfma_tile_pixels();
 int tap_mfma_ksteps(int head_dim);
 int tap_mfma_max_steps();
 hipError_t launch_tap_d64(const TapLaunch&, int in_dtype, int acc_dtype, int fast_exp, int full64, int waves8, int counted, hipStream_t, int*, int*);
 int tap_d64_tile_pixels(int in_dtype, int acc_dtype, int full64);
-bool tap_wide_supported(int in_dtype, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
-                        const void* q, const void* k);
+bool tap_wide_supported(const DaamQKDesc&, const void* q, const void* k);
 hipError_t launch_tap_wide(const TapLaunch&, int acc_dtype, int max_head_dim, int fast_exp, hipStream_t, int*, int*);
-bool tap_d64_supported(int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
-                       const void* q, const void* k);
-bool tap_chunk_supported(int in_dtype, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
-                         int64_t q_extent, const void* q, const void* k);
+bool tap_d64_supported(const DaamQKDesc&, const void* q, const void* k);
+bool tap_chunk_supported(const DaamQKDesc&, const void* q, const void* k);
 hipError_t launch_tap_chunk(const TapLaunch&, int in_dtype, int acc_dtype, int fast_exp, int interleave, hipStream_t, int*, int*);
-bool tap_slab_supported(int in_dtype, int batch, int heads, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb,
-                        int64_t k_sh, int64_t q_extent, const void* q, const void* k);
+bool tap_slab_supported(const DaamQKDesc&, const void* q, const void* k);
 int tap_slab_heads(int head_dim);
 int tap_slab_tile_pixels();
 hipError_t launch_tap_slab(const TapLaunch&, int acc_dtype, int fast_exp, hipStream_t, int*, int*);
@@ -314,4 +310,9 @@ inline int ensure_zeroed(Layer& l, hipStream_t s)
 
 // auxiliary non-blocking streams + fork / join events of a context (multi-kernel tap flushes, multi-class finalize)
 hipError_t ensure_aux(DaamCtx* c);
+
+// a tap call against its layer and the context (daam_tap_api.hip; daam_attend's fused tap asks the same)
+int check_qk(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d);
+// which running-sum dtypes a pipeline dtype may feed: its own (the reference's behaviour) or f32
+inline bool dtypes_compatible(int in_dtype, int acc_dtype) { return acc_dtype == DAAM_F32 || acc_dtype == in_dtype; }
 

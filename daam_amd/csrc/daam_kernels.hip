@@ -437,7 +437,7 @@ __global__ __launch_bounds__(256) void zero_groups_kernel(const ZeroGroups Z)
 }
 
 // ---------------------------------------------------------------------------------------
-// host-callable launchers (called from daam_api.hip)
+// host-callable launchers (called from daam_api.hip / daam_tap_api.hip)
 // ---------------------------------------------------------------------------------------
 template <typename K> static hipError_t allow_lds(K kernel, size_t bytes) {
     if (bytes <= 64 * 1024) return hipSuccess;

@@ -20,6 +20,7 @@
 // head_dim re-fetch piece 0 of their row (a valid address, finite data) and the Q operand of the k-step is cleared in
 // registers after the LDS read (K x 0 = 0); a k-step that lies entirely past head_dim is skipped.
 #include "daam_tap16_softmax.h"
+#include "daam_tap_rows.h"
 
 namespace daam {
 
@@ -273,16 +274,13 @@ __global__ __launch_bounds__(256, ((sizeof(ACC_T) == 2 && !IN::kBf16) ? 4 : 3)) 
     }
 }
 
-// q_extent = elements from the tensor's first to past its last addressed Q element (batch * q_sb): byte offsets stay in 32 bits
-bool tap_chunk_supported(int in_dtype, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb,
-                         int64_t k_sh, int64_t q_extent, const void* q, const void* k)
+// q_extent = elements from the tensor's first to past its last addressed Q element: byte offsets stay in 32 bits
+bool tap_chunk_supported(const DaamQKDesc& d, const void* q, const void* k)
 {
-    if ((in_dtype != 0 && in_dtype != 2) || head_dim < 8 || head_dim > kCkMaxHeadDim || head_dim % 8 != 0 || hw % 8 != 0) return false;
-    const int64_t s[] = {q_sp, k_st, q_sb, q_sh, k_sb, k_sh};
-    for (int64_t v : s)
-        if (v % 8 != 0 || v < 0) return false;
-    if (k_st * 77 >= (int64_t)1 << 30 || q_sp * (int64_t)hw >= (int64_t)1 << 30 || q_extent >= (int64_t)1 << 30) return false;
-    return ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0;
+    if ((d.in_dtype != 0 && d.in_dtype != 2) || d.head_dim < 8 || d.head_dim > kCkMaxHeadDim || d.head_dim % 8 != 0) return false;
+    const int64_t lim = (int64_t)1 << 30, q_extent = (int64_t)d.batch * d.q_stride_b;
+    if (d.k_stride_t * 77 >= lim || d.q_stride_p * (int64_t)d.hw >= lim || q_extent >= lim) return false;
+    return tap_rows_16b(d, q, k, true);
 }
 
 template <typename IN, typename ACC_T, bool FAST>

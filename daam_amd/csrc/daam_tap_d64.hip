@@ -26,6 +26,7 @@
 // lookup -- 0.67 lookups per cycle per CU and a read-tag-conflict stall in 20 % of the cycles
 // (TCP_TOTAL_CACHE_ACCESSES, TCP_READ_TAGCONFLICT_STALL_CYCLES; profiles/r02_tap_tcp.txt).
 #include "daam_tap16_softmax.h"
+#include "daam_tap_rows.h"
 
 // Data path of the head_dim-64 launches (FULL64: every SDXL / SD-2.x layer), as measured over rounds 1-5 (LABNOTES): K and Q go HBM -> LDS by
 // LDS-DMA (buffer_load ... lds: the swizzle is applied to the SOURCE address, the LDS image of a wave-instruction is lane-linear) instead of
@@ -91,15 +92,11 @@ __global__ DAAM_TAP_D64_BOUNDS void tap_d64_kernel(const TapLaunch L)
 #include "daam_tap_d64_body.inc"
 }
 
-bool tap_d64_supported(int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
-                       const void* q, const void* k)
+bool tap_d64_supported(const DaamQKDesc& d, const void* q, const void* k)
 {
-    if (head_dim < 8 || head_dim > 64 || head_dim % 8 != 0 || hw % 8 != 0) return false;
-    const int64_t s[] = {q_sp, k_st, q_sb, q_sh, k_sb, k_sh};
-    for (int64_t v : s)
-        if (v % 8 != 0) return false;
-    if (k_st * 77 >= (int64_t)1 << 30) return false;         // K element offsets are kept in 32 bits
-    return ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0;
+    if (d.head_dim < 8 || d.head_dim > 64 || d.head_dim % 8 != 0) return false;
+    if (d.k_stride_t * 77 >= (int64_t)1 << 30) return false;   // K element offsets are kept in 32 bits
+    return tap_rows_16b(d, q, k, false);
 }
 
 template <typename IN, typename ACC_T, bool FAST, bool FULL64, int WAVES = 4, bool COUNTED = false>

@@ -19,6 +19,7 @@
 // multiple of 4 -> ds_read_b128 conflict-free), double-buffered; Q and the next step's K are
 // fetched global -> VGPR one step ahead.
 #include "daam_tap_common.h"
+#include "daam_tap_rows.h"
 
 namespace daam {
 
@@ -201,16 +202,12 @@ __global__ __launch_bounds__(256, (tap_mfma_min_waves<KS, ACC_T, FAST_EXP>())) v
 }
 
 // ---------------------------------------------------------------------------------------
-bool tap_mfma_supported(int in_dtype, int head_dim, int tokens, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb,
-                        int64_t q_sh, int64_t k_sb, int64_t k_sh)
+// (the pointer alignment is use_mfma()'s test, daam_tap_api.hip -- this predicate's only caller -- repeated by the shared one)
+bool tap_mfma_supported(const DaamQKDesc& d, const void* q, const void* k)
 {
-    if (in_dtype != 0 || tokens != kTok) return false;
-    if (head_dim % 8 != 0 || head_dim < 8 || head_dim > 160) return false;
-    if (hw % 8 != 0) return false;
-    const int64_t s[] = {q_sp, k_st, q_sb, q_sh, k_sb, k_sh};
-    for (int64_t v : s)
-        if (v % 8 != 0) return false;                       // every row piece 16-byte aligned
-    return true;
+    if (d.in_dtype != 0 || d.tokens != kTok) return false;
+    if (d.head_dim % 8 != 0 || d.head_dim < 8 || d.head_dim > 160) return false;
+    return tap_rows_16b(d, q, k, false);                    // every row piece 16-byte aligned
 }
 
 int tap_mfma_tile_pixels() { return kMfmaPixels; }

@@ -32,6 +32,7 @@
 //   K operands + MFMAs; barrier; DMA K(s + 1)                        (an L2 hit; lands during the softmax)
 //   softmax + accumulate (running sums stay in registers for the whole launch)
 #include "daam_tap16_softmax.h"
+#include "daam_tap_rows.h"
 
 // Cache policy of the Q fetches: non-temporal (2).  Every Q line is read exactly once per launch, by one workgroup; with nt the once-read
 // lines no longer push the K slabs, which every tile of a layer re-reads, out of the L2s: SD-v1.5 2517 -> 2583 maps/s, tap 0.351 -> 0.342 ms,
@@ -295,20 +296,18 @@ __global__ __launch_bounds__(64 * kSlabWaves, 4) void tap_slab_kernel(const TapL
 int tap_slab_heads(int head_dim) { return head_dim == 40 ? 8 : head_dim == 80 ? 4 : head_dim == 160 ? 2 : 0; }
 int tap_slab_tile_pixels() { return kSlabPx; }
 
-// q_extent = elements from the tensor's first to past its last addressed Q element (batch * q_sb): byte offsets stay in 32 bits
-bool tap_slab_supported(int in_dtype, int batch, int heads, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh,
-                        int64_t k_sb, int64_t k_sh, int64_t q_extent, const void* q, const void* k)
+// q_extent = elements from the tensor's first to past its last addressed Q element: byte offsets stay in 32 bits
+bool tap_slab_supported(const DaamQKDesc& d, const void* q, const void* k)
 {
-    const int nh = tap_slab_heads(head_dim);
-    if (in_dtype != 0 || !nh || hw % 16 != 0) return false;   // hw % 16: the second half of a pixel tile is inside the layer or outside, never split
+    const int nh = tap_slab_heads(d.head_dim);
+    if (d.in_dtype != 0 || !nh || d.hw % 16 != 0) return false;   // hw % 16: the second half of a pixel tile is inside the layer or outside, never split
     // the slab's heads are adjacent columns of one row, and the kept heads (batch * heads / 2 onwards, trace.py:240) start on a slab
-    if (q_sh != head_dim || k_sh != head_dim || heads % nh != 0 || ((batch * heads) / 2) % nh != 0) return false;
-    const int64_t s[] = {q_sp, k_st, q_sb, k_sb};
-    for (int64_t v : s)
-        if (v % 8 != 0 || v < 0) return false;
-    if (q_sp < (int64_t)heads * head_dim || k_st < (int64_t)heads * head_dim) return false;
-    if (k_st * 77 >= (int64_t)1 << 30 || q_sp * (int64_t)hw >= (int64_t)1 << 30 || q_extent >= (int64_t)1 << 30) return false;
-    return ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0;
+    if (d.q_stride_h != d.head_dim || d.k_stride_h != d.head_dim || d.heads % nh != 0 || ((d.batch * d.heads) / 2) % nh != 0) return false;
+    const int64_t lim = (int64_t)1 << 30, row = (int64_t)d.heads * d.head_dim, q_extent = (int64_t)d.batch * d.q_stride_b;
+    if (d.q_stride_p < row || d.k_stride_t < row) return false;
+    if (d.k_stride_t * 77 >= lim || d.q_stride_p * (int64_t)d.hw >= lim || q_extent >= lim) return false;
+    // (the head strides, here 40 / 80 / 160, pass the shared multiple-of-8 and sign tests by themselves)
+    return tap_rows_16b(d, q, k, true);
 }
 
 template <typename ACC_T, bool FAST>

@@ -1,4 +1,4 @@
-// Argument block and window table of tap_walk_kernel (daam_tap_walk.hip), shared with the host planner (daam_api.hip).
+// Argument block and window table of tap_walk_kernel (daam_tap_walk.hip), shared with the host planner (daam_tap_api.hip).
 #pragma once
 #include "daam_types.h"
 

@@ -14,6 +14,7 @@
 // units: an odd count makes the operand reads -- 16 rows x one chunk per ds_read_b128 -- conflict-free); chunks past head_dim
 // (80 = 10 of 12 chunks) stay zero.  K double-buffered, Q in a wave-private tile, register-staged one step ahead.
 #include "daam_tap16_softmax.h"
+#include "daam_tap_rows.h"
 
 namespace daam {
 
@@ -213,15 +214,11 @@ __global__ __launch_bounds__(256, (KS > 3 ? 1 : 2)) void tap_wide_kernel(const T
     }
 }
 
-bool tap_wide_supported(int in_dtype, int head_dim, int hw, int64_t q_sp, int64_t k_st, int64_t q_sb, int64_t q_sh, int64_t k_sb,
-                        int64_t k_sh, const void* q, const void* k)
+bool tap_wide_supported(const DaamQKDesc& d, const void* q, const void* k)
 {
-    if (in_dtype != 0 || head_dim <= 64 || head_dim > 160 || head_dim % 8 != 0 || hw % 8 != 0) return false;
-    const int64_t s[] = {q_sp, k_st, q_sb, q_sh, k_sb, k_sh};
-    for (int64_t v : s)
-        if (v % 8 != 0) return false;
-    if (k_st * 77 >= (int64_t)1 << 30 || q_sp * (int64_t)hw >= (int64_t)1 << 30) return false;   // byte offsets stay in 32 bits
-    return ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0;
+    if (d.in_dtype != 0 || d.head_dim <= 64 || d.head_dim > 160 || d.head_dim % 8 != 0) return false;
+    if (d.k_stride_t * 77 >= (int64_t)1 << 30 || d.q_stride_p * (int64_t)d.hw >= (int64_t)1 << 30) return false;   // byte offsets stay in 32 bits
+    return tap_rows_16b(d, q, k, false);
 }
 
 template <typename ACC_T, bool FAST, int KS>

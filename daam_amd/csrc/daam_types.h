@@ -1,4 +1,4 @@
-// Device-visible tables shared by the host API (daam_api.hip, daam_finalize_api.hip) and the kernels.
+// Device-visible tables shared by the host API (daam_api.hip, daam_tap_api.hip, daam_finalize_api.hip) and the kernels.
 // gfx950 only; no other architecture is targeted.
 #pragma once
 #include <hip/hip_runtime.h>

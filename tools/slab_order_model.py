@@ -4,7 +4,7 @@ the chip earliest?  CPU only.
 
 The launch is a few hundred to a thousand indivisible units (a workgroup = one (layer, 640-byte slab, pixel tile) walking all
 recorded denoising steps: fp16 sums are order-dependent, a chain cannot be split in time) on 512 slots (256 CUs x 2 workgroups),
-dispatched in workgroup-index order; every XCD takes an eighth of each segment of the order (daam_api.hip: daam_tap_flush).
+dispatched in workgroup-index order; every XCD takes an eighth of each segment of the order (daam_tap_api.hip: tap_entries).
 Durations per unit kind are the measured ones (tools/exp/slab_timeline.py on a timing build: profiles/r0*_slab_timeline_sd15.json);
 the model keeps them fixed, i.e. it ignores that a chain runs faster on a CU whose other slot is empty.
 
