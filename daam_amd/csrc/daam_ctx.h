@@ -19,6 +19,7 @@ int tap_mfma_ksteps(int head_dim);
 int tap_mfma_max_steps();
 hipError_t launch_tap_d64(const TapLaunch&, int in_dtype, int acc_dtype, int fast_exp, int full64, int waves8, int counted, hipStream_t, int*, int*);
 int tap_d64_tile_pixels(int in_dtype, int acc_dtype, int full64);
+bool tap_d64_has_waves8(int in_dtype, int acc_dtype);      // the eight-wave form exists for this dtype pair (tap_tile64_has_waves8)
 bool tap_wide_supported(const DaamQKDesc&, const void* q, const void* k);
 hipError_t launch_tap_wide(const TapLaunch&, int acc_dtype, int max_head_dim, int fast_exp, hipStream_t, int*, int*);
 bool tap_d64_supported(const DaamQKDesc&, const void* q, const void* k);

@@ -315,7 +315,7 @@ void route_walk(const DaamCtx* c, std::vector<TapChain>& chains, int in_dtype)
     std::vector<char> seen(c->max_layers, 0);
     for (const TapChain& ch : chains)
         if (ch.kind == d64) multi = multi || seen[ch.slot % c->max_layers]++;
-    if (multi && all_head_dim_64(chains, d64) && tap_walk_has(in_dtype, c->acc_dtype) &&
+    if (multi && all_head_dim_64(chains, d64) && tap_d64_has_waves8(in_dtype, c->acc_dtype) &&
         tap_d64_tile_pixels(in_dtype, c->acc_dtype, 1) == tap_walk_tile_pixels())
         for (TapChain& ch : chains)
             if (ch.kind == d64) ch.kind = {TapRoute::Walk};

@@ -15,27 +15,23 @@
 // it leaves are bit-identical to theirs.
 //
 // Data path: both operands travel HBM -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds), swizzle applied to the source address,
-// one sub-step ahead (K double-buffered, Q in a wave-private tile, as in the head_dim-64 kernel).  A partial last chunk
+// one sub-step ahead (K double-buffered, Q in a wave-private tile: the tile of daam_tap_tile64.h, which also holds the prologue and
+// the softmax dispatch; this file adds the chunk offset, the partial last chunk and the sub-step protocol).  A partial last chunk
 // (head_dim 40: 5 of 8 sixteen-byte pieces, 80: 2, 160: 4) cannot be zero-padded by a DMA: the lanes whose piece lies past
 // head_dim re-fetch piece 0 of their row (a valid address, finite data) and the Q operand of the k-step is cleared in
 // registers after the LDS read (K x 0 = 0); a k-step that lies entirely past head_dim is skipped.
 #include "daam_tap16_softmax.h"
+#include "daam_tap_tile64.h"
 #include "daam_tap_rows.h"
 
 namespace daam {
 
-constexpr int kCkRow = 128;                         // bytes per K / Q row in LDS: one 64-element chunk, 16-byte pieces swizzled
-constexpr int kCkKBuf = kD64Rows * kCkRow;          // 10240: 80 K rows (77..79 re-read row 76: finite, their logits are masked)
-constexpr int kCkQTile = 32 * kCkRow;               // 4096: one wave's 32 pixel rows
-constexpr int kCkQOff = 2 * kCkKBuf;                // Q tiles of the four waves follow the two K buffers
-constexpr int kCkMaxHeadDim = 256;
+constexpr int kCkMaxHeadDim = 256;                  // a row of the tile (daam_tap_tile64.h) holds one 64-element chunk of it
 
 template <typename ACC_T> constexpr size_t tap_chunk_lds_bytes() {
-    const size_t kb = 2 * (size_t)kCkKBuf + 4 * (size_t)kCkQTile, st = (size_t)kTok * kMfmaPixels * sizeof(ACC_T);
+    const size_t kb = 2 * (size_t)kTapKBuf + 4 * (size_t)kTapQTile, st = (size_t)kTok * kMfmaPixels * sizeof(ACC_T);
     return (kb > st ? kb : st) + (size_t)kMaxStepsPerLaunch * 2 * sizeof(void*);     // fp16 sums: 37888 -> 4 workgroups per CU
 }
-
-__device__ __forceinline__ constexpr int ck_swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // The MFMAs of one sub-step: C (+)= K_chunk Q_chunk^T for the wave's two 16-pixel groups.  `partial`: the chunk is the layer's
 // last and holds only `vc` (1..7) valid 16-byte pieces.  All conditions but the lane-quarter compares are wave-uniform.
@@ -47,11 +43,11 @@ __device__ __forceinline__ void chunk_mfma(const unsigned char* kb, const unsign
 {
     const half8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
     half8 q00 = *reinterpret_cast<const half8*>(qtile + f_rd);
-    half8 q10 = *reinterpret_cast<const half8*>(qtile + 16 * kCkRow + f_rd);
+    half8 q10 = *reinterpret_cast<const half8*>(qtile + 16 * kTapRow + f_rd);
     if (partial && vc < 4 && h >= vc) { q00 = zero; q10 = zero; }          // k-step 0 = pieces 0..3: lane quarter h holds piece h
 #pragma unroll
     for (int mt = 0; mt < 5; ++mt) {
-        const half8 a0 = *reinterpret_cast<const half8*>(kb + mt * 16 * kCkRow + f_rd);
+        const half8 a0 = *reinterpret_cast<const half8*>(kb + mt * 16 * kTapRow + f_rd);
         if constexpr (FIRST) {                                             // tokens 77..79 (tile 4): -inf from the start of their chain
             c0[mt] = IN::mfma(a0, q00, mt == 4 ? cmask : floatx4{0, 0, 0, 0});
             c1[mt] = IN::mfma(a0, q10, mt == 4 ? cmask : floatx4{0, 0, 0, 0});
@@ -62,11 +58,11 @@ __device__ __forceinline__ void chunk_mfma(const unsigned char* kb, const unsign
     }
     if (!partial || vc > 4) {                                              // k-step 1 = pieces 4..7: piece 4 + h
         half8 q01 = *reinterpret_cast<const half8*>(qtile + (f_rd ^ 64));
-        half8 q11 = *reinterpret_cast<const half8*>(qtile + 16 * kCkRow + (f_rd ^ 64));
+        half8 q11 = *reinterpret_cast<const half8*>(qtile + 16 * kTapRow + (f_rd ^ 64));
         if (partial && 4 + h >= vc) { q01 = zero; q11 = zero; }
 #pragma unroll
         for (int mt = 0; mt < 5; ++mt) {
-            const half8 a1 = *reinterpret_cast<const half8*>(kb + mt * 16 * kCkRow + (f_rd ^ 64));
+            const half8 a1 = *reinterpret_cast<const half8*>(kb + mt * 16 * kTapRow + (f_rd ^ 64));
             c0[mt] = IN::mfma(a1, q01, c0[mt]);
             c1[mt] = IN::mfma(a1, q11, c1[mt]);
         }
@@ -83,7 +79,7 @@ __global__ __launch_bounds__(256, ((sizeof(ACC_T) == 2 && !IN::kBf16) ? 4 : 3)) 
     constexpr size_t kPtrOff = tap_chunk_lds_bytes<ACC_T>() - (size_t)kMaxStepsPerLaunch * 2 * sizeof(void*);
 
     extern __shared__ __align__(16) unsigned char smem[];
-    unsigned char* kbuf = smem;                               // [2][kCkKBuf], then the four waves' Q tiles
+    unsigned char* kbuf = smem;                               // [2][kTapKBuf], then the four waves' Q tiles
     ACC_T* stage = reinterpret_cast<ACC_T*>(smem);            // [kTok][kMfmaPixels], aliases both
     const void** sptr = reinterpret_cast<const void**>(smem + kPtrOff);
 
@@ -104,24 +100,11 @@ __global__ __launch_bounds__(256, ((sizeof(ACC_T) == 2 && !IN::kBf16) ? 4 : 3)) 
         lay = L.one;
     }
     const int tid = threadIdx.x;
-    if (table) {
-        const DAAM_GLOBAL TapPtr* ptrs = as_global<TapPtr>(L.ptrs) + lay.ptr_begin;
-        for (int i = tid; i < lay.n_steps; i += 256) {
-            sptr[2 * i] = ptrs[i].q;
-            sptr[2 * i + 1] = ptrs[i].k;
-        }
-    } else if (tid == 0) {
-        sptr[0] = L.one_ptr.q;
-        sptr[1] = L.one_ptr.k;
-    }
+    tap_step_ptrs_to_lds<256>(L, lay, table, sptr, tid);
     const int n_steps = lay.n_steps;
-    const int rel = wg - lay.wg_begin;
-    const int kh = rel / lay.tiles_per_head;
-    const int p0 = (rel - kh * lay.tiles_per_head) * kMfmaPixels;
-    const int bh = lay.bh_first + kh;
-    const int b = bh / lay.heads, hd = bh - b * lay.heads;
-    const int64_t k_off = b * lay.k_sb + hd * lay.k_sh;
-    const int64_t q_off = b * lay.q_sb + hd * lay.q_sh;
+    const TapTile tile = tap_tile_decode<kMfmaPixels>(lay, wg);
+    const int kh = tile.kh, p0 = tile.p0;
+    const int64_t k_off = tile.k_off, q_off = tile.q_off;
 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the DMA block choice must not become exec masks
     const int j = lane & 15, h = lane >> 4;
@@ -161,14 +144,13 @@ __global__ __launch_bounds__(256, ((sizeof(ACC_T) == 2 && !IN::kBf16) ? 4 : 3)) 
     const bool last_partial = vc < 8;
 
     // operand reads: row l&15 of a 16-row tile, piece 4 ks + (l >> 4); the same offset serves K (A) and Q (B)
-    const int f_rd = j * kCkRow + ck_swz(j, h);               // k-step 1: ^ 64
-    unsigned char* qtile = kbuf + kCkQOff + wave * kCkQTile;
+    const int f_rd = j * kTapRow + swz_chunk(j, h);               // k-step 1: ^ 64
+    unsigned char* qtile = kbuf + kTapQOff + wave * kTapQTile;
 
     // DMA sources.  K: 1 KiB block blk = 4 j2 + wave (10 blocks: rows 8 blk .. 8 blk + 7); lane -> row 8 blk + (lane >> 3), LDS
     // piece slot lane & 7 = source piece (lane & 7) ^ ((row >> 1) & 7).  Q: block i = rows 8 i .. 8 i + 7 of the wave's 32, same
     // rule.  *_full: every piece of the chunk is inside head_dim; *_last: the layer's partial last chunk, pieces past head_dim
     // re-fetch piece 0.  The chunk's 128 c bytes and the step's tensor are wave-uniform (scalar offset / resource descriptor).
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
     unsigned kd_full[3], kd_last[3];
 #pragma unroll
     for (int j2 = 0; j2 < 3; ++j2) {
@@ -198,11 +180,8 @@ __global__ __launch_bounds__(256, ((sizeof(ACC_T) == 2 && !IN::kBf16) ? 4 : 3)) 
     for (int i = 0; i < 4; ++i) q_s[i] = 8 * i < q_rows_in ? (unsigned)i * q_step8 : 0u;
     const unsigned k_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(k_off * 2));
 
-    auto tensor = [](const void* p) -> __amdgpu_buffer_rsrc_t {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, -1, 0x00020000);
-    };
+    // (through a lambda: tap_tensor_rsrc called directly from dma() changes the machine code of every instance)
+    auto tensor = [](const void* p) { return tap_tensor_rsrc(p); };
     // the fetches of sub-step (step s, chunk c) into K buffer `buf` and this wave's Q tile
     auto dma = [&](int s, int c, int buf) {
         const unsigned cb = (unsigned)c * 128u;
@@ -212,7 +191,7 @@ __global__ __launch_bounds__(256, ((sizeof(ACC_T) == 2 && !IN::kBf16) ? 4 : 3)) 
         for (int j2 = 0; j2 < 3; ++j2) {
             const int blk = 4 * j2 + wave;                    // wave-uniform
             if (blk < 10)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(kt, (lds_ptr_t)(kbuf + buf * kCkKBuf + blk * 1024), 16,
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(kt, (lds_ptr_t)(kbuf + buf * kTapKBuf + blk * 1024), 16,
                                                          lastp ? kd_last[j2] : kd_full[j2], k_base + cb, 0, 0);
         }
         const __amdgpu_buffer_rsrc_t qt = tensor(sptr[2 * s]);
@@ -235,23 +214,18 @@ __global__ __launch_bounds__(256, ((sizeof(ACC_T) == 2 && !IN::kBf16) ? 4 : 3)) 
         const int s_next = min(s + 1, n_steps - 1);           // branch-free: the last step re-fetches itself
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        chunk_mfma<IN, true>(kbuf + buf * kCkKBuf, qtile, f_rd, last_partial && n_ch == 1, vc, h, c0, c1, cmask);
+        chunk_mfma<IN, true>(kbuf + buf * kTapKBuf, qtile, f_rd, last_partial && n_ch == 1, vc, h, c0, c1, cmask);
         buf ^= 1;
         if (n_ch > 1) dma(s, 1, buf); else dma(s_next, 0, buf);
         for (int c = 1; c < n_ch; ++c) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            chunk_mfma<IN, false>(kbuf + buf * kCkKBuf, qtile, f_rd, last_partial && c == n_ch - 1, vc, h, c0, c1, cmask);
+            chunk_mfma<IN, false>(kbuf + buf * kTapKBuf, qtile, f_rd, last_partial && c == n_ch - 1, vc, h, c0, c1, cmask);
             buf ^= 1;
             if (c + 1 < n_ch) dma(s, c + 1, buf); else dma(s_next, 0, buf);
         }
-        if constexpr (IN::kBf16) {
-            softmax20_accumulate_bf16<ACC_T, true>(c0, lay, h, run0);
-            softmax20_accumulate_bf16<ACC_T, true>(c1, lay, h, run1);
-        } else {
-            softmax20_accumulate<ACC_T, FAST_EXP, true>(c0, lay, h, run0);
-            softmax20_accumulate<ACC_T, FAST_EXP, true>(c1, lay, h, run1);
-        }
+        tap_softmax_accumulate<IN, ACC_T, FAST_EXP>(c0, lay, h, run0);
+        tap_softmax_accumulate<IN, ACC_T, FAST_EXP>(c1, lay, h, run1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the last (redundant) fetch has landed before the staging tile reuses the space
     __syncthreads();                                          // all K reads done

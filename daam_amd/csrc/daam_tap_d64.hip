@@ -26,6 +26,7 @@
 // lookup -- 0.67 lookups per cycle per CU and a read-tag-conflict stall in 20 % of the cycles
 // (TCP_TOTAL_CACHE_ACCESSES, TCP_READ_TAGCONFLICT_STALL_CYCLES; profiles/r02_tap_tcp.txt).
 #include "daam_tap16_softmax.h"
+#include "daam_tap_tile64.h"
 #include "daam_tap_rows.h"
 
 // Data path of the head_dim-64 launches (FULL64: every SDXL / SD-2.x layer), as measured over rounds 1-5 (LABNOTES): K and Q go HBM -> LDS by
@@ -39,19 +40,11 @@
 
 namespace daam {
 
-constexpr int kTapRow = 128;                        // bytes per K / Q row in LDS (head_dim 64 x fp16), chunks swizzled
-constexpr int kTapKBuf = kD64Rows * kTapRow;        // 10240: 80 K rows, rows 77..79 stay zero
-constexpr int kTapQTile = 32 * kTapRow;             // 4096: one wave's 32 pixel rows
-constexpr int kTapQOff = 2 * kTapKBuf;              // Q tiles of the four waves follow the two K buffers
-
 // WAVES = waves per workgroup: 4 (128 pixels) or 8 (256 pixels of one head, ONE K tile for twice the pixels)
 template <typename ACC_T, int WAVES = 4> constexpr size_t tap_d64_lds_bytes() {
     const size_t kb = 2 * (size_t)kTapKBuf + WAVES * (size_t)kTapQTile, st = (size_t)kTok * (32 * WAVES) * sizeof(ACC_T);
     return (kb > st ? kb : st) + (size_t)kMaxStepsPerLaunch * 2 * sizeof(void*);     // fp16 sums: 37888 -> 4 workgroups per CU
 }
-
-// byte offset of 16-byte chunk `chunk` inside row `row` of a swizzled [rows][128 B] image
-__device__ __forceinline__ constexpr int swz_chunk(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // FULL64: every layer of the launch has head_dim == 64 (SDXL): the zero-padding selects of the head_dim < 64 case (8 VALU per
 // wave-step) are compiled out
@@ -73,7 +66,8 @@ __device__ __forceinline__ constexpr int swz_chunk(int row, int chunk) { return 
 // The prologue ends with the same vmcnt(4) + barrier (K(0) is in LDS), the launch with vmcnt(0) + barrier before the staging tile
 // reuses the space.  COUNTED = false is the protocol before it: vmcnt(0) at the end of a step (K AND Q), __syncthreads() at the start of
 // the next (DAAM_TAP_SYNC=0; the register-staged head_dim < 64 form always).
-// (the body is daam_tap_d64_body.inc: one text, two kernel templates, so that the machine code of the earlier protocol stays what it was)
+// (the body is daam_tap_d64_body.inc: one text, two kernel templates, so that the machine code of the earlier protocol stays what it was;
+// the parts of the tile that walk / pair / chunk share with it are daam_tap_tile64.h)
 #define DAAM_TAP_D64_BOUNDS __launch_bounds__(64 * WAVES, ((WAVES == 8 || (sizeof(ACC_T) == 2 && !IN::kBf16)) ? 4 : 3))
 
 // the protocol before the counted waits (DAAM_TAP_SYNC=0) and the register-staged head_dim < 64 form
@@ -133,9 +127,10 @@ static hipError_t launch_d64(const TapLaunch& L, hipStream_t stream, int grid, s
 // with fp16 or f32 sums, bf16 Q / K with bf16 or f32 sums), else 128
 int tap_d64_tile_pixels(int in_dtype, int acc_dtype, int full64)
 {
-    const bool pair = (in_dtype == 0 && (acc_dtype == 0 || acc_dtype == 1)) || (in_dtype == 2 && (acc_dtype == 2 || acc_dtype == 1));
-    return (pair && full64) ? 256 : 128;
+    return (tap_tile64_has_waves8(in_dtype, acc_dtype) && full64) ? 256 : 128;
 }
+
+bool tap_d64_has_waves8(int in_dtype, int acc_dtype) { return tap_tile64_has_waves8(in_dtype, acc_dtype); }
 
 hipError_t launch_tap_d64(const TapLaunch& L, int in_dtype, int acc_dtype, int fast_exp, int full64, int waves8, int counted, hipStream_t stream, int* grid_out, int* lds_out)
 {

@@ -26,29 +26,17 @@
         lay = L.one;
     }
     const int tid = threadIdx.x;
-    if (table) {
-        const DAAM_GLOBAL TapPtr* ptrs = as_global<TapPtr>(L.ptrs) + lay.ptr_begin;
-        for (int i = tid; i < lay.n_steps; i += NT) {
-            sptr[2 * i] = ptrs[i].q;
-            sptr[2 * i + 1] = ptrs[i].k;
-        }
-    } else if (tid == 0) {
-        sptr[0] = L.one_ptr.q;
-        sptr[1] = L.one_ptr.k;
-    }
+    tap_step_ptrs_to_lds<NT>(L, lay, table, sptr, tid);
     const int n_steps = lay.n_steps;
-    const int rel = wg - lay.wg_begin;
-    const int kh = rel / lay.tiles_per_head;                  // (head, tile) numbering: the tiles of a head share its K tile out of one L2
-    const int p0 = (rel - kh * lay.tiles_per_head) * TILE;
-    const int bh = lay.bh_first + kh;
-    const int b = bh / lay.heads, hd = bh - b * lay.heads;
-    const int64_t k_off = b * lay.k_sb + hd * lay.k_sh;
-    const int64_t q_off = b * lay.q_sb + hd * lay.q_sh;
+    const TapTile tile = tap_tile_decode<TILE>(lay, wg);
+    const int kh = tile.kh, p0 = tile.p0;
+    const int64_t k_off = tile.k_off, q_off = tile.q_off;
 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the DMA block choice must not become exec masks
     const int j = lane & 15, h = lane >> 4;
 
     // ---- running sums -> registers (through the staging tile, 16-byte row pieces) --------------
+    // (text in every kernel that has it: as functions shared through daam_tap_tile64.h it changed each of d64, pair, chunk, wide and mfma)
     typename Pair<ACC_T>::T run0[kSlots16 / 2], run1[kSlots16 / 2];   // slot pairs (2i, 2i+1)
     ACC_T* acc = reinterpret_cast<ACC_T*>(lay.acc) + (size_t)kh * kTok * lay.hw;
     if (!lay.fresh) {
@@ -85,11 +73,7 @@
             *reinterpret_cast<float4v*>(kbuf + i * 16) = float4v{0, 0, 0, 0};
         __syncthreads();                                      // the first K tile lands on top of the zeros
     } else {
-        // K rows 77..79 (never written by a step) must be finite: zero them once, both buffers
-        for (int i = tid; i < 2 * 3 * (kTapRow / 16); i += NT) {
-            const int buf = i / (3 * (kTapRow / 16)), r = i % (3 * (kTapRow / 16));
-            *reinterpret_cast<float4v*>(kbuf + buf * kTapKBuf + kTok * kTapRow + r * 16) = float4v{0, 0, 0, 0};
-        }
+        tap64_zero_pad_rows<NT>(kbuf, tid);
     }
 
     // per-thread K piece coordinates: piece c = tid + 256 j2 -> row t = c / 8 = (tid >> 3) + 32 j2, chunk c % 8.  The swizzle
@@ -125,20 +109,12 @@
     unsigned char* qtile = kbuf + kTapQOff + wave * kTapQTile;
     const int q_wr = q_row * kTapRow + ((q_chunk ^ (lane >> 4)) << 4);
     // operand reads: row l&15 of a 16-row tile, chunk 4 ks + (l >> 4); the same offset serves K (A) and Q (B)
-    const int f_rd = j * kTapRow + swz_chunk(j, h);            // k-step 1: ^ 64
-    // Fetches are raw buffer loads: address = the step's tensor (a wave-uniform resource descriptor built from the pointer
-    // in SGPRs) + a per-lane 32-bit byte offset that never changes + a wave-uniform byte offset.  No 64-bit address
-    // arithmetic on the VALU (7 v_lshl_add_u64 per wave-step with plain global loads), offsets stay single registers.
-    auto tensor = [](const void* p) -> __amdgpu_buffer_rsrc_t {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, -1, 0x00020000);
-    };
+    const int f_rd = j * kTapRow + swz_chunk(j, h);            // k-step 1: ^ 64 (not a function of its own: that folds the swizzle differently)
     const unsigned k_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(k_off * 2));
 
     float4v kreg[KCH];
     auto issue_k = [&](int s) {
-        const __amdgpu_buffer_rsrc_t kt = tensor(sptr[2 * s + 1]);
+        const __amdgpu_buffer_rsrc_t kt = tap_tensor_rsrc(sptr[2 * s + 1]);
         kreg[0] = __builtin_bit_cast(float4v, __builtin_amdgcn_raw_buffer_load_b128(kt, k_src0, k_base, 0));
         kreg[1] = __builtin_bit_cast(float4v, __builtin_amdgcn_raw_buffer_load_b128(kt, k_src0, k_base + k_step, 0));
         kreg[2] = __builtin_bit_cast(float4v, __builtin_amdgcn_raw_buffer_load_b128(kt, k_src2, k_base, 0));
@@ -153,7 +129,7 @@
     };
     float4v qreg[4];
     auto issue_q = [&](int s) {
-        const __amdgpu_buffer_rsrc_t qt = tensor(sptr[2 * s]);
+        const __amdgpu_buffer_rsrc_t qt = tap_tensor_rsrc(sptr[2 * s]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) qreg[i] = __builtin_bit_cast(float4v, __builtin_amdgcn_raw_buffer_load_b128(qt, q_b0, q_s[i], 0));
     };
@@ -168,7 +144,6 @@
     // LDS-DMA form (FULL64 launches only).  K: 1 KiB block blk = WAVES j2 + wave (10 blocks: rows 8 blk .. 8 blk + 7; rows 77..79 re-read
     // row 76: finite, their logits are masked); lane -> row 8 blk + (lane >> 3), LDS chunk slot lane & 7 = source chunk
     // (lane & 7) ^ ((row >> 1) & 7).  Q: block i = rows 8 i .. 8 i + 7 of the wave's 32, same rule.
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
     unsigned kd_src[3];
 #pragma unroll
     for (int j2 = 0; j2 < 3; ++j2) {
@@ -184,8 +159,9 @@
         const int px = p0 + wave * 32 + (lane >> 3);
         qd_src[par] = (unsigned)((q_off + (int64_t)min(px, lay.hw - 1) * lay.q_sp) * 2) + (unsigned)ch * 16u;
     }
+    // (text, as in walk: through tap64_dma_k every head_dim-64 instance is scheduled differently; pair calls it)
     auto dma_k = [&](int s, int buf) {
-        const __amdgpu_buffer_rsrc_t kt = tensor(sptr[2 * s + 1]);
+        const __amdgpu_buffer_rsrc_t kt = tap_tensor_rsrc(sptr[2 * s + 1]);
 #pragma unroll
         for (int j2 = 0; j2 < 3; ++j2) {
             const int blk = WAVES * j2 + wave;                // wave-uniform
@@ -195,12 +171,7 @@
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(kt, (lds_ptr_t)(kbuf + buf * kTapKBuf + blk * 1024), 16, kd_src[j2], k_base, 0, 0);
         }
     };
-    auto dma_q = [&](int s) {
-        const __amdgpu_buffer_rsrc_t qt = tensor(sptr[2 * s]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(qt, (lds_ptr_t)(qtile + i * 1024), 16, qd_src[i & 1], q_s[i], 0, 0);
-    };
+    auto dma_q = [&](int s) { tap64_dma_q(sptr[2 * s], qtile, qd_src, q_s); };
     const floatx4 cmask = premask_tile4(h);
     // one denoising step: logits of step s from the K and Q tiles in LDS, then the fetches of the next step (head_dim 64: by DMA
     // into the other K buffer / this wave's own Q tile, whose reads are behind it; head_dim < 64: step s + 1 from the staging
@@ -228,15 +199,7 @@
             dma_q(s_fetch);
         }
         floatx4 c0[5], c1[5];
-#pragma unroll
-        for (int mt = 0; mt < 5; ++mt) {
-            const half8 a0 = *reinterpret_cast<const half8*>(kb + mt * 16 * kTapRow + f_rd);
-            const half8 a1 = *reinterpret_cast<const half8*>(kb + mt * 16 * kTapRow + (f_rd ^ 64));
-            c0[mt] = IN::mfma(a0, q00, mt == 4 ? cmask : floatx4{0, 0, 0, 0});     // tokens 77..79: -inf from the start of their chain
-            c1[mt] = IN::mfma(a0, q10, mt == 4 ? cmask : floatx4{0, 0, 0, 0});
-            c0[mt] = IN::mfma(a1, q01, c0[mt]);
-            c1[mt] = IN::mfma(a1, q11, c1[mt]);
-        }
+        tap64_mfma_chain<IN>(kb, f_rd, q00, q01, q10, q11, cmask, c0, c1);
         if constexpr (!FULL64) {
             // head_dim < 64 (register-staged): the pieces of step s + 1 were requested a whole step ago -- into LDS now (K buffer
             // (s + 1) & 1 was last read in step s - 1, which every wave left before this step's barrier; the Q tile is this wave's
@@ -247,13 +210,8 @@
             issue_k(min(s + 2, n_steps - 1));                 // branch-free: the last steps re-fetch the last one
             issue_q(min(s + 2, n_steps - 1));
         }
-        if constexpr (IN::kBf16) {
-            softmax20_accumulate_bf16<ACC_T, true>(c0, lay, h, run0);
-            softmax20_accumulate_bf16<ACC_T, true>(c1, lay, h, run1);
-        } else {
-            softmax20_accumulate<ACC_T, FAST_EXP, true>(c0, lay, h, run0);
-            softmax20_accumulate<ACC_T, FAST_EXP, true>(c1, lay, h, run1);
-        }
+        tap_softmax_accumulate<IN, ACC_T, FAST_EXP>(c0, lay, h, run0);
+        tap_softmax_accumulate<IN, ACC_T, FAST_EXP>(c1, lay, h, run1);
         if constexpr (COUNTED) {
             // invariants (i) and (ii): this wave's K(s + 1) pieces have landed (only the four Q(s + 1) DMAs may be outstanding), its K(s)
             // reads are done; Q(s + 1) stays in flight across the barrier

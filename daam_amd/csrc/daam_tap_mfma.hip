@@ -19,6 +19,7 @@
 // multiple of 4 -> ds_read_b128 conflict-free), double-buffered; Q and the next step's K are
 // fetched global -> VGPR one step ahead.
 #include "daam_tap_common.h"
+#include "daam_tap_tile64.h"
 #include "daam_tap_rows.h"
 
 namespace daam {
@@ -64,18 +65,7 @@ __global__ __launch_bounds__(256, (tap_mfma_min_waves<KS, ACC_T, FAST_EXP>())) v
         lay = L.one;
     }
     const int tid = threadIdx.x;
-    // per-step q / k base pointers -> LDS once, so the step loop never waits on a dependent
-    // global load (table fetch -> address -> data) on its critical path
-    if (table) {
-        const DAAM_GLOBAL TapPtr* ptrs = as_global<TapPtr>(L.ptrs) + lay.ptr_begin;
-        for (int i = tid; i < lay.n_steps; i += 256) {
-            sptr[2 * i] = ptrs[i].q;
-            sptr[2 * i + 1] = ptrs[i].k;
-        }
-    } else if (tid == 0) {
-        sptr[0] = L.one_ptr.q;
-        sptr[1] = L.one_ptr.k;
-    }
+    tap_step_ptrs_to_lds<256>(L, lay, table, sptr, tid);
     const int n_steps = lay.n_steps;
     const int nch = lay.head_dim >> 3;                        // 16-B pieces per q / k row
     const int rel = wg - lay.wg_begin;

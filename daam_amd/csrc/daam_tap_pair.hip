@@ -1,32 +1,27 @@
 // Paired head_dim-64 tap (probes): one workgroup runs TWO chains over the same recorded Q -- the generation's chain or a
-// probe's (chain A: its per-step K, double-buffered by LDS-DMA exactly as tap_d64_kernel) and a probe's (chain B: one fixed K tile,
+// probe's (chain A: its per-step K, double-buffered by LDS-DMA as in tap_d64_kernel) and a probe's (chain B: one fixed K tile,
 // DMA'd into LDS once at workgroup start).  Each step's Q tile is fetched from HBM once and feeds both MFMA chains; the
 // softmax and the accumulate run per chain, into two register sets of running sums.  Chain B re-reads the step's Q operands from the
 // wave's LDS tile after chain A's softmax (the Q of the next step is requested only then), which keeps the kernel at 128 VGPRs with no
 // scratch: two eight-wave workgroups per CU, four waves per SIMD, like tap_d64_kernel.
 //
 // Every sum set is bit-identical to running its chain alone through tap_d64_kernel<InF16, ACC_T, FAST, true, 8>: the same tiling (eight
-// waves, 256 pixels of one kept head), the same LDS swizzle and operand reads, the same MFMA order per chain
-// (a0 . q00 -> a1 . q01, masked start for tokens 77..79), the same softmax code (daam_tap16_softmax.h).
+// waves, 256 pixels of one kept head) and the same tile (daam_tap_tile64.h: geometry, swizzle, descriptor, prologue, the MFMA chain per
+// chain).  This file adds the second chain, its fixed K tile and the second set of sums.
 // LDS: 2 K buffers (20 KiB) + 8 Q tiles (32 KiB) + the fixed K tile (10 KiB) + step pointers (1 KiB) = 63 KiB: two workgroups per CU.
 #include "daam_tap16_softmax.h"
+#include "daam_tap_tile64.h"
 
 namespace daam {
 namespace tap_pair {
 
-constexpr int kRow = 128;                           // bytes per K / Q row in LDS (head_dim 64 x fp16), chunks swizzled
-constexpr int kKBuf = kD64Rows * kRow;              // 10240: 80 K rows
-constexpr int kQTile = 32 * kRow;                   // 4096: one wave's 32 pixel rows
 constexpr int kWaves = 8;
-constexpr int kQOff = 2 * kKBuf;                    // Q tiles follow the two K buffers
-constexpr int kFixOff = kQOff + kWaves * kQTile;    // then chain B's fixed K tile
+constexpr int kFixOff = kTapQOff + kWaves * kTapQTile;   // behind the tile's K buffers and Q tiles: chain B's fixed K tile
 
 template <typename ACC_T> constexpr size_t lds_bytes() {
-    const size_t kb = (size_t)kFixOff + kKBuf, st = (size_t)kTok * (32 * kWaves) * sizeof(ACC_T);
+    const size_t kb = (size_t)kFixOff + kTapKBuf, st = (size_t)kTok * (32 * kWaves) * sizeof(ACC_T);
     return (kb > st ? kb : st) + (size_t)kMaxStepsPerLaunch * 2 * sizeof(void*);
 }
-
-__device__ __forceinline__ constexpr int swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 }  // namespace tap_pair
 
@@ -59,15 +54,10 @@ __global__ __launch_bounds__(512, 4) void tap_pair_kernel(const TapLaunch L)
     load_layer(gl + li, &lay);
     load_layer(gl + L.n_layers + li, &layb);
     const int tid = threadIdx.x;
-    {
-        const DAAM_GLOBAL TapPtr* ptrs = as_global<TapPtr>(L.ptrs) + lay.ptr_begin;
-        for (int i = tid; i < lay.n_steps; i += NT) {
-            sptr[2 * i] = ptrs[i].q;
-            sptr[2 * i + 1] = ptrs[i].k;
-        }
-    }
+    tap_step_ptrs_to_lds<NT>(L, lay, true, sptr, tid);
     const void* kb_ptr = as_global<TapPtr>(L.ptrs)[layb.ptr_begin].k;
     const int n_steps = lay.n_steps;
+    // tap_tile_decode (daam_tap_tile64.h) plus chain B's K offset, kept as text: through the function both instances come out as other machine code
     const int rel = wg - lay.wg_begin;
     const int kh = rel / lay.tiles_per_head;
     const int p0 = (rel - kh * lay.tiles_per_head) * TILE;
@@ -108,17 +98,8 @@ __global__ __launch_bounds__(512, 4) void tap_pair_kernel(const TapLaunch L)
     read_in(accb, layb.fresh != 0, rb0, rb1);
     // K rows 77..79 of the two step buffers are never written by a step: zero them once (the DMAs below re-read row 76 into them for
     // the fixed tile, exactly as for a step buffer)
-    for (int i = tid; i < 2 * 3 * (kRow / 16); i += NT) {
-        const int buf = i / (3 * (kRow / 16)), r = i % (3 * (kRow / 16));
-        *reinterpret_cast<float4v*>(kbuf + buf * kKBuf + kTok * kRow + r * 16) = float4v{0, 0, 0, 0};
-    }
+    tap64_zero_pad_rows<NT>(kbuf, tid);
 
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
-    auto tensor = [](const void* p) -> __amdgpu_buffer_rsrc_t {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, -1, 0x00020000);
-    };
     const unsigned k_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(k_off * 2));
     const unsigned kb_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(kb_off * 2));
     const int q_rows_in = __builtin_amdgcn_readfirstlane(lay.hw - (p0 + wave * 32));
@@ -126,8 +107,8 @@ __global__ __launch_bounds__(512, 4) void tap_pair_kernel(const TapLaunch L)
     unsigned q_s[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) q_s[i] = 8 * i < q_rows_in ? (unsigned)i * q_step8 : 0u;
-    unsigned char* qtile = kbuf + kQOff + wave * kQTile;
-    const int f_rd = j * kRow + tap_pair::swz(j, h);
+    unsigned char* qtile = kbuf + kTapQOff + wave * kTapQTile;
+    const int f_rd = j * kTapRow + swz_chunk(j, h);
     unsigned kd_src[3];
 #pragma unroll
     for (int j2 = 0; j2 < 3; ++j2) {
@@ -143,46 +124,18 @@ __global__ __launch_bounds__(512, 4) void tap_pair_kernel(const TapLaunch L)
         const int px = p0 + wave * 32 + (lane >> 3);
         qd_src[par] = (unsigned)((q_off + (int64_t)min(px, lay.hw - 1) * lay.q_sp) * 2) + (unsigned)ch * 16u;
     }
-    auto dma_k_to = [&](const void* kp, unsigned base, unsigned char* dst) {
-        const __amdgpu_buffer_rsrc_t kt = tensor(kp);
-#pragma unroll
-        for (int j2 = 0; j2 < 3; ++j2) {
-            const int blk = kWaves * j2 + wave;
-            if (blk < 10)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(kt, (lds_ptr_t)(dst + blk * 1024), 16, kd_src[j2], base, 0, 0);
-        }
-    };
-    auto dma_q = [&](int s) {
-        const __amdgpu_buffer_rsrc_t qt = tensor(sptr[2 * s]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(qt, (lds_ptr_t)(qtile + i * 1024), 16, qd_src[i & 1], q_s[i], 0, 0);
-    };
     const floatx4 cmask = premask_tile4(h);
-    // the MFMA chain of one K image over this step's Q operands (tap_d64_kernel's order)
-    auto chain = [&](const unsigned char* kb, const half8& q00, const half8& q01, const half8& q10, const half8& q11,
-                     floatx4 (&c0)[5], floatx4 (&c1)[5]) {
-#pragma unroll
-        for (int mt = 0; mt < 5; ++mt) {
-            const half8 a0 = *reinterpret_cast<const half8*>(kb + mt * 16 * kRow + f_rd);
-            const half8 a1 = *reinterpret_cast<const half8*>(kb + mt * 16 * kRow + (f_rd ^ 64));
-            c0[mt] = IN::mfma(a0, q00, mt == 4 ? cmask : floatx4{0, 0, 0, 0});
-            c1[mt] = IN::mfma(a0, q10, mt == 4 ? cmask : floatx4{0, 0, 0, 0});
-            c0[mt] = IN::mfma(a1, q01, c0[mt]);
-            c1[mt] = IN::mfma(a1, q11, c1[mt]);
-        }
-    };
     auto step = [&](int s) {
         __syncthreads();
-        const unsigned char* kb = kbuf + (s & 1) * kKBuf;
+        const unsigned char* kb = kbuf + (s & 1) * kTapKBuf;
         const int s_fetch = min(s + 1, n_steps - 1);
-        dma_k_to(sptr[2 * s_fetch + 1], k_base, kbuf + ((s + 1) & 1) * kKBuf);
+        tap64_dma_k<kWaves>(sptr[2 * s_fetch + 1], k_base, kbuf + ((s + 1) & 1) * kTapKBuf, wave, kd_src);
         floatx4 c0[5], c1[5];
         {
             const half8 q00 = *reinterpret_cast<const half8*>(qtile + f_rd), q01 = *reinterpret_cast<const half8*>(qtile + (f_rd ^ 64));
-            const half8 q10 = *reinterpret_cast<const half8*>(qtile + 16 * kRow + f_rd);
-            const half8 q11 = *reinterpret_cast<const half8*>(qtile + 16 * kRow + (f_rd ^ 64));
-            chain(kb, q00, q01, q10, q11, c0, c1);
+            const half8 q10 = *reinterpret_cast<const half8*>(qtile + 16 * kTapRow + f_rd);
+            const half8 q11 = *reinterpret_cast<const half8*>(qtile + 16 * kTapRow + (f_rd ^ 64));
+            tap64_mfma_chain<IN>(kb, f_rd, q00, q01, q10, q11, cmask, c0, c1);
         }
         softmax20_accumulate<ACC_T, FAST_EXP, true>(c0, lay, h, run0);
         softmax20_accumulate<ACC_T, FAST_EXP, true>(c1, lay, h, run1);
@@ -191,19 +144,19 @@ __global__ __launch_bounds__(512, 4) void tap_pair_kernel(const TapLaunch L)
         asm volatile("" ::: "memory");
         {
             const half8 q00 = *reinterpret_cast<const half8*>(qtile + f_rd), q01 = *reinterpret_cast<const half8*>(qtile + (f_rd ^ 64));
-            const half8 q10 = *reinterpret_cast<const half8*>(qtile + 16 * kRow + f_rd);
-            const half8 q11 = *reinterpret_cast<const half8*>(qtile + 16 * kRow + (f_rd ^ 64));
+            const half8 q10 = *reinterpret_cast<const half8*>(qtile + 16 * kTapRow + f_rd);
+            const half8 q11 = *reinterpret_cast<const half8*>(qtile + 16 * kTapRow + (f_rd ^ 64));
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            dma_q(s_fetch);
-            chain(kfix, q00, q01, q10, q11, c0, c1);
+            tap64_dma_q(sptr[2 * s_fetch], qtile, qd_src, q_s);
+            tap64_mfma_chain<IN>(kfix, f_rd, q00, q01, q10, q11, cmask, c0, c1);
         }
         softmax20_accumulate<ACC_T, FAST_EXP, true>(c0, layb, h, rb0);
         softmax20_accumulate<ACC_T, FAST_EXP, true>(c1, layb, h, rb1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
-    dma_k_to(sptr[1], k_base, kbuf);
-    dma_k_to(kb_ptr, kb_base, kfix);
-    dma_q(0);
+    tap64_dma_k<kWaves>(sptr[1], k_base, kbuf, wave, kd_src);
+    tap64_dma_k<kWaves>(kb_ptr, kb_base, kfix, wave, kd_src);
+    tap64_dma_q(sptr[0], qtile, qd_src, q_s);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     for (int s = 0; s < n_steps; ++s) step(s);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -32,6 +32,7 @@
 //   K operands + MFMAs; barrier; DMA K(s + 1)                        (an L2 hit; lands during the softmax)
 //   softmax + accumulate (running sums stay in registers for the whole launch)
 #include "daam_tap16_softmax.h"
+#include "daam_tap_tile64.h"
 #include "daam_tap_rows.h"
 
 // Cache policy of the Q fetches: non-temporal (2).  Every Q line is read exactly once per launch, by one workgroup; with nt the once-read
@@ -178,13 +179,8 @@ __device__ __forceinline__ void slab_body(unsigned char* smem, const TapLaunch& 
     const unsigned xq_s = q_base + (unsigned)(wave >> 1) * q16;
     const int kB_lds = (wx + 10 * (wave >> 1)) * 1024;
     const int xq_lds = kSlabQOff + (wx + 10 * (wave >> 1)) * 1024;
-    auto tensor = [](const void* p) -> __amdgpu_buffer_rsrc_t {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, -1, 0x00020000);
-    };
     auto dma_k = [&](int s) {                                 // six instructions (waves 4..7: seven)
-        const __amdgpu_buffer_rsrc_t kt = tensor(sptr[2 * s + 1]);
+        const __amdgpu_buffer_rsrc_t kt = tap_tensor_rsrc(sptr[2 * s + 1]);
 #pragma unroll
         for (int m = 0; m < 5; ++m)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(kt, (lds_ptr_t)(smem + (wave + 10 * m) * 1024), 16, kdA, k_base + (unsigned)m * k16, 0, 0);
@@ -192,7 +188,7 @@ __device__ __forceinline__ void slab_body(unsigned char* smem, const TapLaunch& 
         if (wave >= 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(kt, (lds_ptr_t)(smem + (kSlabKInstr - 1) * 1024), 16, xd, k_base, 0, 0);
     };
     auto dma_q = [&](int s) {                                 // two instructions (waves 0..3: three)
-        const __amdgpu_buffer_rsrc_t qt = tensor(sptr[2 * s]);
+        const __amdgpu_buffer_rsrc_t qt = tap_tensor_rsrc(sptr[2 * s]);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(qt, (lds_ptr_t)(smem + kSlabQOff + wave * 1024), 16, qdA, q_base, 0, kSlabQAux);
         if constexpr (TP == kSlabPx)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(qt, (lds_ptr_t)(smem + kSlabQOff + (wave + 10) * 1024), 16, qdA, q_base + q16, 0, kSlabQAux);

@@ -27,6 +27,5 @@ struct WalkLaunch {
 
 hipError_t launch_tap_walk(const WalkLaunch&, int in_dtype, int acc_dtype, int fast_exp, hipStream_t, int* grid_out, int* lds_out);
 int tap_walk_tile_pixels();
-bool tap_walk_has(int in_dtype, int acc_dtype);
 
 }  // namespace daam

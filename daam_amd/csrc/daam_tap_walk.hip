@@ -7,31 +7,26 @@
 // a chain; the redundant re-fetch of "the last step" happens once, at the end of the entry.
 //
 // Every window's sums are bit-identical to tap_d64_kernel<IN, ACC_T, FAST, true, 8> run on that window's steps alone: the same
-// tiling (eight waves, 256 pixels of one kept head, one K tile for all of them), the same LDS swizzle and operand reads, the same
-// MFMA order, the same softmax code (daam_tap16_softmax.h), acc = acc + p in the accumulator dtype.
+// tile (daam_tap_tile64.h: geometry, swizzle, descriptor, prologue, MFMA chain, softmax dispatch; eight waves, 256 pixels of one kept
+// head, one K tile for all of them), acc = acc + p in the accumulator dtype.  This file adds the window loop and its own staging.
 //
 // The write-back of a window happens while the next step's tiles already sit in the K buffer / the Q tiles, so the staging tile
 // cannot alias them as it does in tap_d64_kernel: it has LDS of its own and takes the 256 pixels in passes of 128 (2-byte sums) or
 // 64 (f32 sums) -- 19.25 KiB either way.  LDS: 2 K buffers (20 KiB) + 8 Q tiles (32 KiB) + staging (19.25 KiB) + step pointers
 // (1 KiB) = 72.25 KiB: two workgroups per CU, four waves per SIMD at <= 128 VGPRs, like tap_d64_kernel.
 #include "daam_tap16_softmax.h"
+#include "daam_tap_tile64.h"
 #include "daam_tap_walk.h"
 
 namespace daam {
 namespace tap_walk {
 
-constexpr int kRow = 128;                           // bytes per K / Q row in LDS (head_dim 64 x 2 bytes), chunks swizzled
-constexpr int kKBuf = kD64Rows * kRow;              // 10240: 80 K rows, rows 77..79 stay finite
-constexpr int kQTile = 32 * kRow;                   // 4096: one wave's 32 pixel rows
 constexpr int kWaves = 8;
-constexpr int kQOff = 2 * kKBuf;                    // Q tiles follow the two K buffers
-constexpr int kStageOff = kQOff + kWaves * kQTile;  // then the write-back staging tile [kTok][stage pixels]
+constexpr int kStageOff = kTapQOff + kWaves * kTapQTile;   // behind the tile's K buffers and Q tiles: the write-back staging tile [kTok][stage pixels]
 constexpr int kStageBytes = kTok * 256;             // 128 pixels x 2 bytes = 64 pixels x 4 bytes per token row
 constexpr int kPtrOff = kStageOff + kStageBytes;    // then the entry's step pointers
 constexpr size_t kLdsBytes = (size_t)kPtrOff + (size_t)kMaxStepsPerLaunch * 2 * sizeof(void*);
 static_assert(kLdsBytes <= 80 * 1024, "two workgroups per CU");
-
-__device__ __forceinline__ constexpr int swz(int row, int chunk) { return ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // one running-sum element from global memory (the non-fresh first window of an entry: a window cut by a launch boundary)
 template <typename ACC_T> __device__ __forceinline__ ACC_T load_acc(const ACC_T* p, unsigned i) {
@@ -62,7 +57,7 @@ __global__ __launch_bounds__(512, 4) void tap_walk_kernel(const WalkLaunch W)
     constexpr int PPR = CH / VEC;                                 // 16-byte pieces per staged row (16)
 
     extern __shared__ __align__(16) unsigned char smem[];
-    unsigned char* kbuf = smem;                               // [2][kKBuf], then the eight waves' Q tiles
+    unsigned char* kbuf = smem;                               // [2][kTapKBuf], then the eight waves' Q tiles
     ACC_T* stage = reinterpret_cast<ACC_T*>(smem + kStageOff);    // [kTok][CH]: aliases nothing
     const void** sptr = reinterpret_cast<const void**>(smem + kPtrOff);
 
@@ -78,13 +73,7 @@ __global__ __launch_bounds__(512, 4) void tap_walk_kernel(const WalkLaunch W)
     const int n_win = ent->n_win;
     const DAAM_GLOBAL WalkWin* wins = as_global<WalkWin>(W.wins) + ent->win_begin;
     const int tid = threadIdx.x;
-    {
-        const DAAM_GLOBAL TapPtr* ptrs = as_global<TapPtr>(L.ptrs) + lay.ptr_begin;
-        for (int i = tid; i < lay.n_steps; i += NT) {         // every window's steps, once
-            sptr[2 * i] = ptrs[i].q;
-            sptr[2 * i + 1] = ptrs[i].k;
-        }
-    }
+    tap_step_ptrs_to_lds<NT>(L, lay, true, sptr, tid);        // every window's steps, once
     const int n_steps = lay.n_steps;                          // of the whole entry
     const int rel = wg - lay.wg_begin;
     // (the quotient comes off the VALU: as scalars, head and tile do not turn every window's sum address into a per-lane 64-bit value)
@@ -98,28 +87,19 @@ __global__ __launch_bounds__(512, 4) void tap_walk_kernel(const WalkLaunch W)
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, h = lane >> 4;
 
-    // K rows 77..79 (never written by a step) must be finite: zero them once, both buffers
-    for (int i = tid; i < 2 * 3 * (kRow / 16); i += NT) {
-        const int buf = i / (3 * (kRow / 16)), r = i % (3 * (kRow / 16));
-        *reinterpret_cast<float4v*>(kbuf + buf * kKBuf + kTok * kRow + r * 16) = float4v{0, 0, 0, 0};
-    }
+    tap64_zero_pad_rows<NT>(kbuf, tid);
     __syncthreads();                                          // sptr visible
 
-    // fetch addressing: tap_d64_kernel's LDS-DMA form (see there)
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
-    auto tensor = [](const void* p) -> __amdgpu_buffer_rsrc_t {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, -1, 0x00020000);
-    };
+    // fetch addressing: the LDS-DMA form (daam_tap_tile64.h).  The source set-up and the K issue are text here: as functions of the
+    // header they change every instance (set-up 16 bytes shorter, K issue 4 bytes longer, q_s rescheduled; same registers)
     const unsigned k_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(k_off * 2));
     const int q_rows_in = __builtin_amdgcn_readfirstlane(lay.hw - (p0 + wave * 32));
     const unsigned q_step8 = (unsigned)__builtin_amdgcn_readfirstlane(8 * (int)lay.q_sp * 2);   // bytes per 8 pixel rows
     unsigned q_s[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) q_s[i] = 8 * i < q_rows_in ? (unsigned)i * q_step8 : 0u;
-    unsigned char* qtile = kbuf + kQOff + wave * kQTile;
-    const int f_rd = j * kRow + tap_walk::swz(j, h);           // k-step 1: ^ 64
+    unsigned char* qtile = kbuf + kTapQOff + wave * kTapQTile;
+    const int f_rd = j * kTapRow + swz_chunk(j, h);           // k-step 1: ^ 64
     unsigned kd_src[3];
 #pragma unroll
     for (int j2 = 0; j2 < 3; ++j2) {
@@ -136,51 +116,33 @@ __global__ __launch_bounds__(512, 4) void tap_walk_kernel(const WalkLaunch W)
         qd_src[par] = (unsigned)((q_off + (int64_t)min(px, lay.hw - 1) * lay.q_sp) * 2) + (unsigned)ch * 16u;
     }
     auto dma_k = [&](int s, int buf) {
-        const __amdgpu_buffer_rsrc_t kt = tensor(sptr[2 * s + 1]);
+        const __amdgpu_buffer_rsrc_t kt = tap_tensor_rsrc(sptr[2 * s + 1]);
 #pragma unroll
         for (int j2 = 0; j2 < 3; ++j2) {
             const int blk = kWaves * j2 + wave;               // wave-uniform
             if (blk < 10)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(kt, (lds_ptr_t)(kbuf + buf * kKBuf + blk * 1024), 16, kd_src[j2], k_base, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(kt, (lds_ptr_t)(kbuf + buf * kTapKBuf + blk * 1024), 16, kd_src[j2], k_base, 0, 0);
         }
     };
-    auto dma_q = [&](int s) {
-        const __amdgpu_buffer_rsrc_t qt = tensor(sptr[2 * s]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(qt, (lds_ptr_t)(qtile + i * 1024), 16, qd_src[i & 1], q_s[i], 0, 0);
-    };
+    auto dma_q = [&](int s) { tap64_dma_q(sptr[2 * s], qtile, qd_src, q_s); };
     const floatx4 cmask = premask_tile4(h);
     typename Pair<ACC_T>::T run0[kSlots16 / 2], run1[kSlots16 / 2];   // slot pairs (2i, 2i+1)
     // step g of the ENTRY (the windows' steps numbered through): tap_d64_kernel's step body; the fetches of step g + 1 go out whether
     // or not it belongs to the same window
     auto step = [&](int g) {
         __syncthreads();
-        const unsigned char* kb = kbuf + (g & 1) * kKBuf;
+        const unsigned char* kb = kbuf + (g & 1) * kTapKBuf;
         const int g_fetch = min(g + 1, n_steps - 1);          // branch-free: the entry's last step re-fetches itself
         dma_k(g_fetch, (g + 1) & 1);
         const half8 q00 = *reinterpret_cast<const half8*>(qtile + f_rd), q01 = *reinterpret_cast<const half8*>(qtile + (f_rd ^ 64));
-        const half8 q10 = *reinterpret_cast<const half8*>(qtile + 16 * kRow + f_rd);
-        const half8 q11 = *reinterpret_cast<const half8*>(qtile + 16 * kRow + (f_rd ^ 64));
+        const half8 q10 = *reinterpret_cast<const half8*>(qtile + 16 * kTapRow + f_rd);
+        const half8 q11 = *reinterpret_cast<const half8*>(qtile + 16 * kTapRow + (f_rd ^ 64));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         dma_q(g_fetch);
         floatx4 c0[5], c1[5];
-#pragma unroll
-        for (int mt = 0; mt < 5; ++mt) {
-            const half8 a0 = *reinterpret_cast<const half8*>(kb + mt * 16 * kRow + f_rd);
-            const half8 a1 = *reinterpret_cast<const half8*>(kb + mt * 16 * kRow + (f_rd ^ 64));
-            c0[mt] = IN::mfma(a0, q00, mt == 4 ? cmask : floatx4{0, 0, 0, 0});
-            c1[mt] = IN::mfma(a0, q10, mt == 4 ? cmask : floatx4{0, 0, 0, 0});
-            c0[mt] = IN::mfma(a1, q01, c0[mt]);
-            c1[mt] = IN::mfma(a1, q11, c1[mt]);
-        }
-        if constexpr (IN::kBf16) {
-            softmax20_accumulate_bf16<ACC_T, true>(c0, lay, h, run0);
-            softmax20_accumulate_bf16<ACC_T, true>(c1, lay, h, run1);
-        } else {
-            softmax20_accumulate<ACC_T, FAST_EXP, true>(c0, lay, h, run0);
-            softmax20_accumulate<ACC_T, FAST_EXP, true>(c1, lay, h, run1);
-        }
+        tap64_mfma_chain<IN>(kb, f_rd, q00, q01, q10, q11, cmask, c0, c1);
+        tap_softmax_accumulate<IN, ACC_T, FAST_EXP>(c0, lay, h, run0);
+        tap_softmax_accumulate<IN, ACC_T, FAST_EXP>(c1, lay, h, run1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's DMAs have landed; the next step's barrier publishes K
     };
     dma_k(0, 0);
@@ -249,12 +211,6 @@ __global__ __launch_bounds__(512, 4) void tap_walk_kernel(const WalkLaunch W)
 
 int tap_walk_tile_pixels() { return 32 * tap_walk::kWaves; }
 
-// the dtype pairs tap_d64_tile_pixels() sends to the eight-wave form
-bool tap_walk_has(int in_dtype, int acc_dtype)
-{
-    return (in_dtype == 0 && (acc_dtype == 0 || acc_dtype == 1)) || (in_dtype == 2 && (acc_dtype == 2 || acc_dtype == 1));
-}
-
 template <typename IN, typename ACC_T, bool FAST>
 static hipError_t launch_walk(const WalkLaunch& W, hipStream_t stream, int grid)
 {
@@ -267,7 +223,7 @@ static hipError_t launch_walk(const WalkLaunch& W, hipStream_t stream, int grid)
 
 hipError_t launch_tap_walk(const WalkLaunch& W, int in_dtype, int acc_dtype, int fast_exp, hipStream_t stream, int* grid_out, int* lds_out)
 {
-    if (!W.L.layers || !W.entries || !W.wins || !tap_walk_has(in_dtype, acc_dtype)) return hipErrorInvalidValue;
+    if (!W.L.layers || !W.entries || !W.wins || !tap_tile64_has_waves8(in_dtype, acc_dtype)) return hipErrorInvalidValue;
     const int grid = W.L.wgs_per_xcd * 8;
     *grid_out = grid;
     *lds_out = (int)tap_walk::kLdsBytes;

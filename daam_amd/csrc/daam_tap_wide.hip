@@ -14,6 +14,7 @@
 // units: an odd count makes the operand reads -- 16 rows x one chunk per ds_read_b128 -- conflict-free); chunks past head_dim
 // (80 = 10 of 12 chunks) stay zero.  K double-buffered, Q in a wave-private tile, register-staged one step ahead.
 #include "daam_tap16_softmax.h"
+#include "daam_tap_tile64.h"
 #include "daam_tap_rows.h"
 
 namespace daam {
@@ -60,24 +61,11 @@ __global__ __launch_bounds__(256, (KS > 3 ? 1 : 2)) void tap_wide_kernel(const T
         lay = L.one;
     }
     const int tid = threadIdx.x;
-    if (table) {
-        const DAAM_GLOBAL TapPtr* ptrs = as_global<TapPtr>(L.ptrs) + lay.ptr_begin;
-        for (int i = tid; i < lay.n_steps; i += 256) {
-            sptr[2 * i] = ptrs[i].q;
-            sptr[2 * i + 1] = ptrs[i].k;
-        }
-    } else if (tid == 0) {
-        sptr[0] = L.one_ptr.q;
-        sptr[1] = L.one_ptr.k;
-    }
+    tap_step_ptrs_to_lds<256>(L, lay, table, sptr, tid);
     const int n_steps = lay.n_steps;
-    const int rel = wg - lay.wg_begin;
-    const int kh = rel / lay.tiles_per_head;
-    const int p0 = (rel - kh * lay.tiles_per_head) * kMfmaPixels;
-    const int bh = lay.bh_first + kh;
-    const int b = bh / lay.heads, hd = bh - b * lay.heads;
-    const int64_t k_off = b * lay.k_sb + hd * lay.k_sh;
-    const int64_t q_off = b * lay.q_sb + hd * lay.q_sh;
+    const TapTile tile = tap_tile_decode<kMfmaPixels>(lay, wg);
+    const int kh = tile.kh, p0 = tile.p0;
+    const int64_t k_off = tile.k_off, q_off = tile.q_off;
 
     const int lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, h = lane >> 4;
@@ -142,11 +130,8 @@ __global__ __launch_bounds__(256, (KS > 3 ? 1 : 2)) void tap_wide_kernel(const T
     unsigned char* qtile = kbuf + S::kQOff + wave * S::kQTile;
     const int f_rd = j * S::kRow + h * 16;                    // operand reads: row l&15 of a 16-row tile, chunk 4 ks + (l >> 4)
 
-    auto tensor = [](const void* p) -> __amdgpu_buffer_rsrc_t {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, -1, 0x00020000);
-    };
+    // (through a lambda: tap_tensor_rsrc called directly from issue() changes the machine code of every instance)
+    auto tensor = [](const void* p) { return tap_tensor_rsrc(p); };
     const unsigned k_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(k_off * 2));
 
     float4v kreg[KCH], qreg[QCH];

@@ -13,6 +13,15 @@ _PAIRS = [('5InF16E', 'DF16_', 1), ('5InF16E', 'DF16_', 0), ('5InF16E', 'f', 1),
 INSTANCES = [(i, a, f, full, w, c) for (i, a, f) in _PAIRS for (full, w, c) in ((0, 4, 0), (1, 4, 0), (1, 8, 0), (1, 4, 1), (1, 8, 1))]
 K_BUF, Q_TILE, PTRS = 80 * 128, 32 * 128, 64 * 2 * 8            # a K buffer, a wave's Q tile, the per-step tensor pointers
 
+# machine code of the 12 counted-wait instances, (Q / K type, sums type, fast softmax, waves) -> fingerprint (the other 18 are in
+# profiles/r06_counters.json, which tests/test_tap_walk_cpu.py checks)
+COUNTED_SHAS = {('5InF16E', 'DF16_', 0, 4): 'd37c65c6f3b7', ('5InF16E', 'DF16_', 0, 8): 'f5c4476c9779',
+                ('5InF16E', 'DF16_', 1, 4): '0d9d9c2154a1', ('5InF16E', 'DF16_', 1, 8): 'a1045eee27ba',
+                ('5InF16E', 'f', 0, 4): 'd9c3ec096b35', ('5InF16E', 'f', 0, 8): '42ff7ba6ee83',
+                ('5InF16E', 'f', 1, 4): '2a70c48669dd', ('5InF16E', 'f', 1, 8): '2f6562ed9a3f',
+                ('6InBF16E', 'NS_6bf16_tE', 1, 4): 'c47e0e811c7f', ('6InBF16E', 'NS_6bf16_tE', 1, 8): '24b735e83473',
+                ('6InBF16E', 'f', 1, 4): 'a55cd87df449', ('6InBF16E', 'f', 1, 8): '6cad80394276'}
+
 
 def _name(i, a, f, full, w, c):
     return f'_ZN4daam14tap_d64_kernelINS_{i}{a}Lb{f}ELb{full}ELi{w}E{"Lb1E" if c else ""}EEvNS_9TapLaunchE'
@@ -33,6 +42,14 @@ def test_instances(built):
     for (i, a, f, full, w, c) in INSTANCES:
         if c:
             assert have[_name(i, a, f, full, w, 1)] != have[_name(i, a, f, full, w, 0)]
+
+
+@pytest.mark.parametrize('key', sorted(COUNTED_SHAS), ids=lambda x: '-'.join(str(v).strip('_E') for v in x))
+def test_counted_fingerprint(built, key):
+    """The machine code of every counted-wait instance is what it was before the tile moved to daam_tap_tile64.h."""
+    _, have = built
+    i, a, f, w = key
+    assert have.get(_name(i, a, f, 1, w, 1)) == COUNTED_SHAS[key]
 
 
 @pytest.mark.parametrize('inst', INSTANCES, ids=lambda x: '-'.join(str(v).strip('_E') for v in x))

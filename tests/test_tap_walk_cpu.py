@@ -13,6 +13,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAIR_SHAS = {'_ZN4daam15tap_pair_kernelIDF16_Lb1EEEvNS_9TapLaunchE': '073238c22833',
              '_ZN4daam15tap_pair_kernelIDF16_Lb0EEEvNS_9TapLaunchE': 'd011f31fa1e0'}
 
+# the six tap_walk_kernel instances (younger than profiles/r06_counters.json)
+WALK_SHAS = {'_ZN4daam15tap_walk_kernelINS_5InF16EDF16_Lb0EEEvNS_10WalkLaunchE': 'd769333541c8',
+             '_ZN4daam15tap_walk_kernelINS_5InF16EDF16_Lb1EEEvNS_10WalkLaunchE': '3b10c139e131',
+             '_ZN4daam15tap_walk_kernelINS_5InF16EfLb0EEEvNS_10WalkLaunchE': '2a43ae6bbc85',
+             '_ZN4daam15tap_walk_kernelINS_5InF16EfLb1EEEvNS_10WalkLaunchE': 'be9c10d5869c',
+             '_ZN4daam15tap_walk_kernelINS_6InBF16ENS_6bf16_tELb1EEEvNS_10WalkLaunchE': 'f1aa0587245b',
+             '_ZN4daam15tap_walk_kernelINS_6InBF16EfLb1EEEvNS_10WalkLaunchE': 'bf1fe237aa79'}
+
 
 @pytest.fixture(scope='module')
 def built():
@@ -33,6 +41,13 @@ def test_walk_instances_and_untouched_kernels(built):
     assert len(rec) == 132
     assert {k: have.get(k) for k in rec} == rec
     assert {k: have.get(k) for k in PAIR_SHAS} == PAIR_SHAS
+
+
+@pytest.mark.parametrize('name', sorted(WALK_SHAS))
+def test_walk_kernel_fingerprint(built, name):
+    """The machine code of every tap_walk_kernel instance is what it was before the tile moved to daam_tap_tile64.h."""
+    _, have = built
+    assert have.get(name) == WALK_SHAS[name]
 
 
 def _kernel_descriptors(lib):
