@@ -135,6 +135,30 @@ hipError_t ensure_aux(DaamCtx* c)
     return ae;
 }
 
+// The (h, w) table pair of finalize_rect_kernel: bicubic_table(w, out_w) for the row pass, bicubic_table(h, out_h) for the
+// column pass, one pair per distinct (h, w) of the context (as tab_sides for the square classes).
+int rect_tab(DaamCtx* c, Layer& l)
+{
+    if (l.rtab != -2) return 0;
+    if (l.h == c->out_h && l.w == c->out_w) { l.rtab = -1; return 0; }
+    for (size_t i = 0; i < c->rtab_hw.size(); ++i)
+        if (c->rtab_hw[i] == std::make_pair(l.h, l.w)) { l.rtab = (int)i; return 0; }
+    if ((int)c->rtab_hw.size() >= kMaxTabs) return fail(DAAM_E_UNSUPPORTED, "more than %d distinct map sizes", kMaxTabs);
+    const size_t per = (size_t)(c->out_w + c->out_h) * 4;
+    if (!c->d_rtab_idx) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rtab_idx), sizeof(int16_t) * kMaxTabs * per));
+    if (!c->d_rtab_w) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rtab_w), sizeof(float) * kMaxTabs * per));
+    const int tab = (int)c->rtab_hw.size();
+    std::vector<int16_t> idx(per);
+    std::vector<float> w(per);
+    bicubic_table(l.w, c->out_w, idx.data(), w.data());
+    bicubic_table(l.h, c->out_h, idx.data() + (size_t)c->out_w * 4, w.data() + (size_t)c->out_w * 4);
+    HIP_TRY(hipMemcpy(c->d_rtab_idx + tab * per, idx.data(), per * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_rtab_w + tab * per, w.data(), per * sizeof(float), hipMemcpyHostToDevice));
+    c->rtab_hw.push_back({l.h, l.w});
+    l.rtab = tab;
+    return 0;
+}
+
 extern "C" {
 
 int daam_abi_version(void) { return DAAM_ABI_VERSION; }
@@ -142,11 +166,21 @@ const char* daam_last_error(void) { return g_err.c_str(); }
 
 int daam_ctx_create(int max_layers, int tokens, int out_side, int acc_dtype, DaamCtx** out)
 {
+    if (out && (out_side <= 0 || out_side > 128)) {
+        *out = nullptr;
+        return fail(DAAM_E_INVALID, "out_side %d not in 1..128", out_side);
+    }
+    return daam_ctx_create_rect(max_layers, tokens, out_side, out_side, acc_dtype, out);
+}
+
+int daam_ctx_create_rect(int max_layers, int tokens, int out_h, int out_w, int acc_dtype, DaamCtx** out)
+{
     if (!out) return fail(DAAM_E_INVALID, "out is NULL");
     *out = nullptr;
     if (max_layers <= 0 || max_layers > 4096) return fail(DAAM_E_INVALID, "max_layers %d out of range", max_layers);
     if (tokens <= 0 || tokens > kMaxTokens) return fail(DAAM_E_INVALID, "tokens %d not in 1..%d", tokens, kMaxTokens);
-    if (out_side <= 0 || out_side > 128) return fail(DAAM_E_INVALID, "out_side %d not in 1..128", out_side);
+    if (out_h <= 0 || out_h > 128 || out_w <= 0 || out_w > 128) return fail(DAAM_E_INVALID, "output %d x %d not in 1..128 per side", out_h, out_w);
+    const int out_side = out_h == out_w ? out_h : 0;           // 0: no square class kernel, no square table applies
     if (acc_dtype != DAAM_F16 && acc_dtype != DAAM_F32 && acc_dtype != DAAM_BF16) return fail(DAAM_E_INVALID, "acc_dtype %d", acc_dtype);
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
@@ -156,12 +190,14 @@ int daam_ctx_create(int max_layers, int tokens, int out_side, int acc_dtype, Daa
     c->max_layers = max_layers;
     c->tokens = tokens;
     c->out_side = out_side;
+    c->out_h = out_h;
+    c->out_w = out_w;
     c->acc_dtype = acc_dtype;
     c->layers.resize(max_layers);
     c->tap_steps.assign(max_layers, 0);
     hipError_t e = c->ring.init();
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tab_idx), sizeof(int16_t) * kMaxTabs * out_side * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tab_w), sizeof(float) * kMaxTabs * out_side * 4);
+    if (e == hipSuccess && out_side) e = hipMalloc(reinterpret_cast<void**>(&c->d_tab_idx), sizeof(int16_t) * kMaxTabs * out_side * 4);
+    if (e == hipSuccess && out_side) e = hipMalloc(reinterpret_cast<void**>(&c->d_tab_w), sizeof(float) * kMaxTabs * out_side * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_fin_tab), DaamCtx::kFinTabCap);
     if (e != hipSuccess) {
         daam_ctx_destroy(c);
@@ -230,6 +266,8 @@ int daam_ctx_destroy(DaamCtx* c)
     if (c->d_fin_tab) (void)hipFree(c->d_fin_tab);
     if (c->d_tab_idx) (void)hipFree(c->d_tab_idx);
     if (c->d_tab_w) (void)hipFree(c->d_tab_w);
+    if (c->d_rtab_idx) (void)hipFree(c->d_rtab_idx);
+    if (c->d_rtab_w) (void)hipFree(c->d_rtab_w);
     if (c->bin_scratch) (void)hipFree(c->bin_scratch);
     delete c;
     return 0;
@@ -237,9 +275,18 @@ int daam_ctx_destroy(DaamCtx* c)
 
 int daam_layer_configure(DaamCtx* c, int layer, int heads, int side, int factor, void* acc)
 {
+    if (c && layer >= 0 && layer < c->max_layers && (heads <= 0 || side <= 0 || side > 1024))
+        return fail(DAAM_E_INVALID, "heads %d / side %d", heads, side);
+    return daam_layer_configure_rect(c, layer, heads, side, side, factor, acc);
+}
+
+int daam_layer_configure_rect(DaamCtx* c, int layer, int heads, int h, int w, int factor, void* acc)
+{
     if (!c) return fail(DAAM_E_INVALID, "ctx is NULL");
     if (layer < 0 || layer >= c->max_layers) return fail(DAAM_E_INVALID, "layer %d out of range", layer);
-    if (heads <= 0 || side <= 0 || side > 1024) return fail(DAAM_E_INVALID, "heads %d / side %d", heads, side);
+    if (heads <= 0 || h <= 0 || h > 1024 || w <= 0 || w > 1024) return fail(DAAM_E_INVALID, "heads %d / %d x %d positions", heads, h, w);
+    if (h != w && c->n_bins > 1) return fail(DAAM_E_UNSUPPORTED, "a layer of %d x %d positions on a time-binned context", h, w);
+    const int side = h == w ? h : 0;
     DeviceGuard on_device(c);
     for (auto& p : c->pending)
         if (p.layer % c->max_layers == layer) return fail(DAAM_E_STATE, "layer %d re-configured with un-flushed taps pending", layer);
@@ -248,7 +295,9 @@ int daam_layer_configure(DaamCtx* c, int layer, int heads, int side, int factor,
     l = Layer();
     l.heads = heads;
     l.side = side;
-    l.hw = side * side;
+    l.h = h;
+    l.w = w;
+    l.hw = h * w;
     l.factor = factor;
     l.bytes = (size_t)heads * c->tokens * l.hw * acc_elem(c->acc_dtype);
     const int nb = std::max(1, c->n_bins);                     // a binned layer's buffer holds every window
@@ -259,7 +308,10 @@ int daam_layer_configure(DaamCtx* c, int layer, int heads, int side, int factor,
         HIP_TRY(hipMemset(l.acc, 0, l.bytes * nb));
         l.owned = true;
     }
-    if (side != c->out_side) {
+    if (h != w || c->out_h != c->out_w) {                      // finalize_rect_kernel's tables; none of the square classes applies
+        int rc = rect_tab(c, l);
+        if (rc) return rc;
+    } else if (side != c->out_side) {
         int tab = -1;
         for (size_t i = 0; i < c->tab_sides.size(); ++i)
             if (c->tab_sides[i] == side) tab = (int)i;
@@ -324,6 +376,7 @@ int daam_ctx_set_time_bins(DaamCtx* c, int n_bins, const int32_t* first_step)
 {
     if (!c || !first_step) return fail(DAAM_E_INVALID, "NULL argument");
     if (n_bins < 1 || n_bins > kMaxBins) return fail(DAAM_E_INVALID, "n_bins %d not in 1..%d", n_bins, kMaxBins);
+    if (c->out_h != c->out_w) return fail(DAAM_E_UNSUPPORTED, "time windows on a context with a %d x %d output", c->out_h, c->out_w);
     if (first_step[0] != 0) return fail(DAAM_E_INVALID, "the first window starts at step %d, not 0", first_step[0]);
     for (int b = 1; b < n_bins; ++b)
         if (first_step[b] <= first_step[b - 1])
@@ -509,8 +562,13 @@ int daam_key_offset(DaamCtx* c, int layer, int* offset, int* total)
 
 int daam_epilogue_normalize(float* maps, int n_rows, int side, void* stream)
 {
-    if (!maps || n_rows <= 0 || side <= 0) return fail(DAAM_E_INVALID, "bad argument");
-    hipError_t e = launch_normalize(maps, n_rows, side * side, (hipStream_t)stream);
+    return daam_epilogue_normalize_rect(maps, n_rows, side, side, stream);
+}
+
+int daam_epilogue_normalize_rect(float* maps, int n_rows, int h, int w, void* stream)
+{
+    if (!maps || n_rows <= 0 || h <= 0 || w <= 0) return fail(DAAM_E_INVALID, "bad argument");
+    hipError_t e = launch_normalize(maps, n_rows, h * w, (hipStream_t)stream);
     if (e != hipSuccess) return fail((int)e, "normalize launch: %s", hipGetErrorString(e));
     return 0;
 }
@@ -518,10 +576,16 @@ int daam_epilogue_normalize(float* maps, int n_rows, int side, void* stream)
 int daam_word_heat_map(const float* maps, int side, const int32_t* idx, int n_idx, float* word_map, float* out,
                        int out_h, int out_w, int absolute, float threshold, float* workspace, void* stream)
 {
+    return daam_word_heat_map_rect(maps, side, side, idx, n_idx, word_map, out, out_h, out_w, absolute, threshold, workspace, stream);
+}
+
+int daam_word_heat_map_rect(const float* maps, int h, int w, const int32_t* idx, int n_idx, float* word_map, float* out,
+                            int out_h, int out_w, int absolute, float threshold, float* workspace, void* stream)
+{
     if (!maps || !idx || !word_map || !workspace) return fail(DAAM_E_INVALID, "NULL argument");
     if (n_idx <= 0 || n_idx > kMaxTokens) return fail(DAAM_E_INVALID, "n_idx %d not in 1..%d", n_idx, kMaxTokens);
-    if (side <= 0 || (out && (out_h <= 0 || out_w <= 0))) return fail(DAAM_E_INVALID, "bad size");
-    hipError_t e = launch_word(maps, side, idx, n_idx, word_map, out, out_h, out_w, absolute, threshold, workspace,
+    if (h <= 0 || w <= 0 || (out && (out_h <= 0 || out_w <= 0))) return fail(DAAM_E_INVALID, "bad size");
+    hipError_t e = launch_word(maps, h, w, idx, n_idx, word_map, out, out_h, out_w, absolute, threshold, workspace,
                                (hipStream_t)stream);
     if (e != hipSuccess) return fail((int)e, "word map launch: %s", hipGetErrorString(e));
     return 0;

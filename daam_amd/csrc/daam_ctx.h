@@ -4,10 +4,12 @@
 #pragma once
 #include "daam_types.h"
 #include "daam_fin_bins.h"
+#include "daam_fin_rect.h"
 #include "../../include/daam_hip.h"
 
 #include <deque>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace daam {
@@ -56,7 +58,7 @@ hipError_t launch_attend_d64(const AttendLaunch&, int in_dtype, int acc_dtype, i
 hipError_t launch_clock_monitor(unsigned long long* samples, int n_samples, int period_us, hipStream_t);
 hipError_t launch_start_gate(const unsigned* counter, unsigned target, int timeout_us, unsigned* timeouts, hipStream_t);
 constexpr int kClockMaxSamples = 4096;
-hipError_t launch_word(const float*, int, const int32_t*, int, float*, float*, int, int, int, float, float*,
+hipError_t launch_word(const float*, int, int, const int32_t*, int, float*, float*, int, int, int, float, float*,
                        hipStream_t);
 hipError_t launch_finalize_bin_sum(const BinSumLaunch&, int acc_dtype, hipStream_t);
 int bin_sum_elems_per_tile(int acc_dtype);
@@ -157,7 +159,9 @@ struct Ring {
 
 struct Layer {
     bool configured = false;
-    int heads = 0, side = 0, hw = 0, factor = 0;
+    int heads = 0, side = 0, hw = 0, factor = 0;   // side: h == w, or 0 for a layer of unequal sides
+    int h = 0, w = 0;        // hw = h * w, position p = pixel (p / w, p % w)
+    int rtab = -2;           // finalize_rect_kernel's table pair of (h, w): -1 = the output's size, -2 = not looked up yet (rect_tab)
     void* acc = nullptr;
     bool owned = false;
     size_t bytes = 0;
@@ -181,7 +185,20 @@ constexpr int kMaxBins = 64;         // time windows of a binned context (daam_c
 
 struct DaamCtx {
     int device = 0;                    // HIP device the context was created on; every entry point runs there
-    int max_layers, tokens, out_side, acc_dtype;
+    int max_layers, tokens, out_side, acc_dtype;   // out_side: out_h == out_w, or 0 for an output of unequal sides
+    int out_h = 0, out_w = 0;
+    // finalize_rect_kernel: one table pair per distinct (h, w), [kMaxTabs][out_w + out_h][4] (row table, then column table);
+    // allocated with the first layer that needs one
+    std::vector<std::pair<int, int>> rtab_hw;
+    int16_t* d_rtab_idx = nullptr;
+    float* d_rtab_w = nullptr;
+    // the finalize of this context runs finalize_rect_kernel: the output or a configured layer has unequal sides
+    bool rect() const {
+        if (out_h != out_w) return true;
+        for (const Layer& l : layers)
+            if (l.configured && l.h != l.w) return true;
+        return false;
+    }
     // Layer slots.  Un-binned: slot = layer.  Time-binned (daam_ctx_set_time_bins): slot = window * max_layers + layer, an
     // ordinary Layer over the window's slice of the layer's sums [n_bins][heads, tokens, side, side]; every tap entry point maps
     // (layer, step) to its slot, so the deferred launch chains the steps of one window per table entry (TapLayer) as it
@@ -311,6 +328,9 @@ inline int ensure_zeroed(Layer& l, hipStream_t s)
 
 // auxiliary non-blocking streams + fork / join events of a context (multi-kernel tap flushes, multi-class finalize)
 hipError_t ensure_aux(DaamCtx* c);
+
+// the table pair of a layer's (h, w) for finalize_rect_kernel, built and uploaded on first use (daam_api.hip): sets l.rtab
+int rect_tab(DaamCtx* c, Layer& l);
 
 // a tap call against its layer and the context (daam_tap_api.hip; daam_attend's fused tap asks the same)
 int check_qk(DaamCtx* c, int layer, const void* q, const void* k, const DaamQKDesc* d);

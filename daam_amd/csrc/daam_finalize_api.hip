@@ -244,7 +244,7 @@ struct FinTables {
 
 bool fin_out_zeroable(const DaamCtx* c, const float* out, int rows)
 {
-    const size_t out_bytes = sizeof(float) * rows * (size_t)c->out_side * c->out_side;
+    const size_t out_bytes = sizeof(float) * rows * (size_t)c->out_h * c->out_w;
     return out_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
 }
 
@@ -346,6 +346,111 @@ int fin_launch_classes(DaamCtx* c, const FinPlan& P, int dtype, hipStream_t s, c
     return 0;
 }
 
+// ---- outputs or layers of unequal sides: finalize_rect_kernel (daam_finalize_rect.hip) --------------------------------------------
+// Every selected key of such a context takes the one kernel, whatever its own shape: one launch for a single map
+// (finalize_rect_kernel) or for N groups (finalize_rect_grouped_kernel, grid z = group).  The key table goes through the device
+// table cache like the square plan's; the output is cleared by the table-upload launch (single map) or by zero_groups_kernel.
+// key_mask / key_group / rows as fin_plan.
+int fin_rect(DaamCtx* c, Layer* layers, int n_layers, int dtype, const uint8_t* key_mask, const int32_t* key_group, int n_groups,
+             const int* rows, float* out, size_t group_stride, hipStream_t s)
+{
+    std::vector<std::vector<FinRectKey>> per_group(n_groups);
+    int plane_cap = 0, tmp_cap = 0, pos = 0, total = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        Layer& l = layers[i];
+        if (!l.configured) continue;
+        // Layers get their table pair when they are configured; only a square layer configured before the context turned
+        // rectangular (output sides equal, a later layer's not) is still without one.  rect_tab then allocates and copies with
+        // the blocking calls, once per such (h, w): the first finalize of that context synchronises with the device here.
+        int rc = rect_tab(c, l);
+        if (rc) return rc;
+        for (int h = 0; h < l.heads; ++h, ++pos) {
+            const int g = key_group ? key_group[pos] : (key_mask && !key_mask[pos]) ? -1 : 0;
+            if (g < 0) continue;
+            FinRectKey k;
+            k.base = static_cast<const char*>(l.acc) + (size_t)h * c->tokens * l.hw * acc_elem(dtype);
+            k.h = (int16_t)l.h;
+            k.w = (int16_t)l.w;
+            k.tab = l.rtab;
+            per_group[g].push_back(k);
+            ++total;
+            if (l.rtab >= 0) {
+                plane_cap = std::max(plane_cap, (l.hw + 3) & ~3);
+                tmp_cap = std::max(tmp_cap, l.h * c->out_w);
+            }
+        }
+    }
+    if (total == 0) return fail(DAAM_E_NOMAPS, "no heat maps selected");
+    const size_t lds = fin_rect_lds_bytes(c->out_h, c->out_w, plane_cap, tmp_cap);
+    if (lds > kFinRectMaxLds)
+        return fail(DAAM_E_UNSUPPORTED, "finalize of %d x %d maps from these planes needs %zu bytes of LDS per workgroup (limit %zu)",
+                    c->out_h, c->out_w, lds, kFinRectMaxLds);
+    std::vector<char> tab(((size_t)total * sizeof(FinRectKey) + 63) & ~size_t(63), 0);
+    FinRectKey* keys = reinterpret_cast<FinRectKey*>(tab.data());
+    int begin[kFinMaxGroups], max_n = 0, max_rows = 0, sum_rows = 0;
+    for (int g = 0, at = 0; g < n_groups; ++g) {
+        begin[g] = at;
+        for (const FinRectKey& k : per_group[g]) keys[at++] = k;
+        max_n = std::max(max_n, (int)per_group[g].size());
+        max_rows = std::max(max_rows, rows[g]);
+        sum_rows += rows[g];
+    }
+    const size_t plane = (size_t)c->out_h * c->out_w;
+    const bool single = n_groups == 1;
+    const size_t out_bytes = sizeof(float) * rows[0] * plane;
+    const bool zero_in_upload = single && fin_out_zeroable(c, out, rows[0]);
+    if (single && !zero_in_upload) {
+        hipError_t ze = hipMemsetAsync(out, 0, out_bytes, s);
+        if (ze != hipSuccess) return fail((int)ze, "output memset: %s", hipGetErrorString(ze));
+    }
+    if (c->profile) (void)hipEventRecord(c->prof_event(1, 0), s);
+    FinTables T(c, s);
+    int rc = T.put(tab, T.hit(tab), zero_in_upload ? out : nullptr, zero_in_upload ? out_bytes : 0);
+    if (rc) return rc;
+    if (!single) {
+        hipError_t ze = launch_zero_groups(out, group_stride, (int)plane, rows, n_groups, s);
+        if (ze != hipSuccess) return fail((int)ze, "output zeroing: %s", hipGetErrorString(ze));
+    }
+    FinRectGroupLaunch G;
+    memset(&G, 0, sizeof G);
+    FinRectLaunch& L = G.L;
+    L.keys = reinterpret_cast<const FinRectKey*>(T.dev);
+    L.tab_idx = c->d_rtab_idx;
+    L.tab_w = c->d_rtab_w;
+    L.out = out;
+    L.n_keys = max_n;
+    // token rows x key chunks, aimed at 1024 workgroups = four per CU on 256 CUs.  By arithmetic, not by measurement: the
+    // 160 KB of a CU's LDS hold two to five of the tiles the tested shapes need; no other chunk count has been timed.
+    L.n_chunks = std::max(1, std::min(max_n, (1024 + sum_rows / 2) / sum_rows));
+    L.tokens = max_rows;
+    L.out_h = c->out_h;
+    L.out_w = c->out_w;
+    L.plane_cap = plane_cap;
+    for (int g = 0; g < n_groups; ++g) {
+        G.g[g].key_begin = begin[g];
+        G.g[g].n_keys = (int)per_group[g].size();
+        G.g[g].rows = rows[g];
+        G.g[g].inv_n = 1.0f / (float)per_group[g].size();
+        G.g[g].out_off = (int64_t)((size_t)g * group_stride);
+    }
+    int grid = 0, lds_used = 0;
+    hipError_t e;
+    if (single) {
+        L.inv_n = G.g[0].inv_n;
+        e = launch_finalize_rect(L, tmp_cap, dtype, s, &grid, &lds_used);
+    } else {
+        e = launch_finalize_rect_grouped(G, n_groups, tmp_cap, dtype, s, &grid, &lds_used);
+    }
+    if (e != hipSuccess) return fail((int)e, "rectangular finalize launch: %s", hipGetErrorString(e));
+    c->last_block[1] = 256;
+    c->last_grid[1] = grid;
+    c->last_lds[1] = lds_used;
+    c->last_fin_side = 0;
+    c->last_kernels[1] = fin_name(single ? "finalize_rect_kernel" : "finalize_rect_grouped_kernel", dtype_name(dtype));
+    if (c->profile) { (void)hipEventRecord(c->prof_event(1, 1), s); ++c->hist_count[1]; }
+    return 0;
+}
+
 // Key ranges of the chunks of the x2 MFMA finalize: equal shares (even boundaries; the two key lanes of a workgroup take the
 // keys of its range alternately).  Shares shrinking with the dispatch round of a chunk's workgroups (the SIMD arbitrates by
 // age: the first 256 workgroups finish their loop in 23 us, the last 256 in 40 us) were tried and changed nothing -- the kernel
@@ -369,6 +474,7 @@ int fin_single(DaamCtx* c, const uint8_t* key_mask, const int32_t* key_group, in
     int rc = fin_zero_owed(c->layers.data(), c->layers.size(), s);
     if (rc) return rc;
     const int dtype = c->acc_dtype;
+    if (c->rect()) return fin_rect(c, c->layers.data(), c->max_layers, dtype, key_mask, key_group, 1, &rows, out, 0, s);
     FinPlan P;
     if ((rc = fin_plan(c, c->layers.data(), c->max_layers, dtype, key_mask, key_group, 1, &rows, P))) return rc;
     const size_t out_bytes = sizeof(float) * rows * (size_t)c->out_side * c->out_side;
@@ -451,6 +557,7 @@ int fin_grouped(DaamCtx* c, Layer* layers, int n_layers, int dtype, const int32_
 {
     int rc = fin_zero_owed(layers, (size_t)n_layers, s);
     if (rc) return rc;
+    if (c->rect()) return fin_rect(c, layers, n_layers, dtype, nullptr, key_group, n_groups, rows, out, group_stride, s);
     FinPlan P;
     if ((rc = fin_plan(c, layers, n_layers, dtype, nullptr, key_group, n_groups, rows, P))) return rc;
     if (P.mfma_up && !P.pipe_up && per_group_fallback) {
@@ -522,7 +629,7 @@ int fin_check_groups(DaamCtx* c, const int32_t* key_group, int n_groups, const i
     }
     daam_key_offset(c, 0, nullptr, total_keys);
     for (int g = 0; g < n_groups; ++g) rows[g] = fin_rows(c, n_rows[g]);
-    const size_t plane = (size_t)c->out_side * c->out_side;
+    const size_t plane = (size_t)c->out_h * c->out_w;
     for (int g = 0; g + 1 < n_groups; ++g)
         if (group_stride < (size_t)rows[g] * plane)
             return fail(DAAM_E_INVALID, "group_stride %zu < %d rows of %zu floats: groups would overlap", group_stride, rows[g], plane);
@@ -546,6 +653,7 @@ int daam_finalize_prepare(DaamCtx* c, const uint8_t* key_mask, int n_rows, float
 {
     if (!c || !out) return fail(DAAM_E_INVALID, "NULL argument");
     if (c->n_bins > 1) return fail(DAAM_E_UNSUPPORTED, "daam_finalize_prepare: not on a time-binned context (daam_finalize_bins)");
+    if (c->rect()) return fail(DAAM_E_UNSUPPORTED, "daam_finalize_prepare: not on a context with an output or a layer of unequal sides");
     DeviceGuard on_device(c);
     hipStream_t s = (hipStream_t)stream;
     const int rows = fin_rows(c, n_rows);
@@ -626,6 +734,8 @@ int daam_finalize_bins(DaamCtx* c, const int32_t* key_group, int n_groups, const
         for (int h = 0; h < g && direct; ++h) direct = !(bin_begin[h] == bin_begin[g] && set_of(h) == set_of(g));
     }
     if (direct && nb == 1 && !group_set) return daam_finalize_groups(c, key_group, n_groups, n_rows, out, group_stride, stream);
+    if (c->rect() && (nb > 1 || !direct))
+        return fail(DAAM_E_UNSUPPORTED, "daam_finalize_bins: no window ranges on a context with an output or a layer of unequal sides");
     DeviceGuard on_device(c);
     hipStream_t s = (hipStream_t)stream;
     c->prep_out = c->fold_out = nullptr;

@@ -266,54 +266,25 @@ __device__ __forceinline__ void cubic_coeffs(float t, float w[4]) {
 // calls) -- with write-through stores the result does not depend on when an L2 writes a dirty line back.
 __device__ __forceinline__ void store_for_host(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 
-// one thread per output pixel; source plane (<= 96x96 f32) is L1/L2 resident
 __global__ __launch_bounds__(256) void word_expand_kernel(const float* word_map, int side, float* out, int out_h,
                                                           int out_w, float* minmax)
 {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    float v = 0.f;
-    const bool valid = i < out_h * out_w;
-    if (valid) {
-        const int oy = i / out_w, ox = i - oy * out_w;
-        float wy[4], wx[4];
-        int iy[4], ix[4];
-        {
-            const float sc = (float)side / (float)out_h;
-            const float src = sc * ((float)oy + 0.5f) - 0.5f;
-            const float f = floorf(src);
-            cubic_coeffs(src - f, wy);
-            for (int a = 0; a < 4; ++a) iy[a] = min(max((int)f - 1 + a, 0), side - 1);
-        }
-        {
-            const float sc = (float)side / (float)out_w;
-            const float src = sc * ((float)ox + 0.5f) - 0.5f;
-            const float f = floorf(src);
-            cubic_coeffs(src - f, wx);
-            for (int a = 0; a < 4; ++a) ix[a] = min(max((int)f - 1 + a, 0), side - 1);
-        }
-        if (side == out_h && side == out_w) {
-            v = word_map[i];
-        } else {
-            float rows[4];
-            for (int a = 0; a < 4; ++a) {
-                const float* r = word_map + iy[a] * side;
-                rows[a] = r[ix[0]] * wx[0] + r[ix[1]] * wx[1] + r[ix[2]] * wx[2] + r[ix[3]] * wx[3];
-            }
-            v = rows[0] * wy[0] + rows[1] * wy[1] + rows[2] * wy[2] + rows[3] * wy[3];
-        }
-        store_for_host(out + i, v);
-    }
-    // wave64 min / max, one atomic pair per wave
-    float lo = valid ? v : INFINITY, hi = valid ? v : -INFINITY;
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicMin(reinterpret_cast<int*>(minmax), enc_ordered(lo));
-        atomicMax(reinterpret_cast<int*>(minmax) + 1, enc_ordered(hi));
-    }
+#define SRC_H side
+#define SRC_W side
+#include "daam_word_expand_body.inc"
+#undef SRC_H
+#undef SRC_W
+}
+
+// a source plane of unequal sides (daam_word_heat_map_rect)
+__global__ __launch_bounds__(256) void word_expand_rect_kernel(const float* word_map, int src_h, int src_w, float* out, int out_h,
+                                                               int out_w, float* minmax)
+{
+#define SRC_H src_h
+#define SRC_W src_w
+#include "daam_word_expand_body.inc"
+#undef SRC_H
+#undef SRC_W
 }
 
 __global__ __launch_bounds__(256) void word_post_kernel(float* out, int n, const float* minmax, int absolute,
@@ -605,19 +576,23 @@ hipError_t launch_normalize(float* maps, int n_rows, int plane, hipStream_t stre
     return hipGetLastError();
 }
 
-hipError_t launch_word(const float* maps, int side, const int32_t* idx, int n_idx, float* word_map, float* out,
+hipError_t launch_word(const float* maps, int src_h, int src_w, const int32_t* idx, int n_idx, float* word_map, float* out,
                        int out_h, int out_w, int absolute, float threshold, float* workspace, hipStream_t stream)
 {
     WordIdx w;
     w.n = n_idx;
     for (int i = 0; i < n_idx; ++i) w.idx[i] = idx[i];
-    const int plane = side * side;
+    const int plane = src_h * src_w;
     hipLaunchKernelGGL(word_mean_kernel, dim3((plane + 255) / 256), dim3(256), 0, stream, maps, plane, w, word_map,
                        workspace);
     if (out) {
         const int n = out_h * out_w;
-        hipLaunchKernelGGL(word_expand_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, word_map, side, out,
-                           out_h, out_w, workspace);
+        if (src_h == src_w)
+            hipLaunchKernelGGL(word_expand_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, word_map, src_h, out,
+                               out_h, out_w, workspace);
+        else
+            hipLaunchKernelGGL(word_expand_rect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, word_map, src_h, src_w, out,
+                               out_h, out_w, workspace);
         if (!absolute || threshold != 0.f)
             hipLaunchKernelGGL(word_post_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, out, n, workspace,
                                absolute, threshold);

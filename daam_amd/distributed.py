@@ -58,7 +58,7 @@ def trace_prompts(pipe, prompts: Sequence[str], seeds: Optional[Sequence[int]] =
                   pipe_kwargs: Optional[dict] = None, prompts_per_call: int = 1) -> Tuple[torch.Tensor, List[int]]:
     """Run this rank's shard of ``prompts`` through ``pipe`` under ``daam_amd.trace`` and gather the
     global heat maps of ALL prompts (padded to 77 rows) on every rank.  Returns ``(maps
-    [n_prompts, 77, x, x], rows)`` with ``rows[i]`` = valid rows (``n_tokens + 2``) of prompt i.
+    [n_prompts, 77, out_h, out_w], rows)`` with ``rows[i]`` = valid rows (``n_tokens + 2``) of prompt i.
     ``prompts_per_call`` > 1: the shard goes through ``pipe`` in calls of up to that many prompts (one generator per
     prompt, a list as diffusers takes it; ``trace(..., batch_prompts=True)``), each call's maps from one grouped finalize."""
     from .trace import trace
@@ -86,12 +86,12 @@ def trace_prompts(pipe, prompts: Sequence[str], seeds: Optional[Sequence[int]] =
             else:
                 pipe([prompts[i] for i in idx], num_inference_steps=num_inference_steps, **kw)
                 local.extend(tc.engine.global_heat_maps(len(idx), [tc.engine.tokens] * len(idx), **filters).unbind(0))
-    tokens, side = tc.engine.tokens, tc.engine.out_side
+    tokens, out_h, out_w = tc.engine.tokens, tc.engine.out_h, tc.engine.out_w
     if local:
         local_maps = torch.stack(local)
     else:
         device = tc.engine.device or torch.device('cuda', torch.cuda.current_device())
-        local_maps = torch.zeros(0, tokens, side, side, device=device)
+        local_maps = torch.zeros(0, tokens, out_h, out_w, device=device)
     maps = gather_heat_maps(local_maps, len(prompts), group=group)
     rows = [len(pipe.tokenizer.tokenize(p)) + 2 for p in prompts]
     return maps, rows

@@ -86,6 +86,44 @@ def drain_released() -> None:
 
 
 MAX_TIME_BINS = 64
+MAX_MAP_SIDE = 128                                            # daam_ctx_create's limit per output side
+
+
+def map_geometry(base: int, height: int, width: int) -> Tuple[int, int]:
+    """``(out_h, out_w)``: the heat-map size of a generation of ``height x width`` pixels on a pipeline whose default size is
+    ``base = unet.config.sample_size * vae_scale_factor``.  The reference fixes a square map of side ``x`` = 64 for 512 / 1024
+    pipelines, else 96 (trace.py:32-33): one map cell is ``cell = base // x`` pixels (8 for SD, 16 for SDXL), and a
+    generation of another size has ``height // cell x width // cell`` cells.  Both sizes must be multiples of ``2 * cell`` (the
+    factor-2 layers stay integral) and give at most 128 cells per side; otherwise ValueError."""
+    for name, v in (('base', base), ('height', height), ('width', width)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
+            raise ValueError(f'{name} must be a positive int, got {v!r}')
+    base, height, width = int(base), int(height), int(width)
+    x = 64 if base in (512, 1024) else 96
+    cell = base // x
+    if cell <= 0:
+        raise ValueError(f'pipeline size {base} is smaller than its {x} map cells')
+    if height % (2 * cell) or width % (2 * cell):
+        raise ValueError(f'height {height} and width {width} must be multiples of {2 * cell} (map cell {cell} px, pipeline size {base})')
+    out_h, out_w = height // cell, width // cell
+    if out_h > MAX_MAP_SIDE or out_w > MAX_MAP_SIDE:
+        raise ValueError(f'{height} x {width} px gives a {out_h} x {out_w} map: at most {MAX_MAP_SIDE} cells per side')
+    return out_h, out_w
+
+
+def layer_geometry(out_h: int, out_w: int, positions: int) -> Tuple[int, int, int]:
+    """``(factor, h, w)`` of a tapped call with ``positions`` query positions on an ``out_h x out_w`` map:
+    ``factor = int(sqrt(out_h * out_w // positions))`` (trace.py:285 with ``latent_hw = out_h * out_w``), ``h = out_h // factor``,
+    ``w = out_w // factor``; position ``p`` is pixel ``(p // w, p % w)``.  A layer whose size does not divide that way (a UNet
+    whose down-sampling rounds differently) is a ValueError, not a guess."""
+    positions = int(positions)
+    if positions <= 0:
+        raise ValueError(f'{positions} query positions')
+    factor = int(math.sqrt(out_h * out_w // positions))
+    if factor <= 0 or out_h % factor or out_w % factor or (out_h // factor) * (out_w // factor) != positions:
+        raise ValueError(f'a layer of {positions} query positions does not fit a {out_h} x {out_w} map: factor {factor} '
+                         f'gives {out_h / max(factor, 1):g} x {out_w / max(factor, 1):g}')
+    return factor, out_h // factor, out_w // factor
 
 
 def check_time_bins(time_bins) -> Optional[Tuple[int, ...]]:
@@ -176,7 +214,7 @@ def release_parked_contexts() -> None:
 class HeatMapEngine:
     def __init__(self, n_layers: int, tokens: int = 77, out_side: int = 64, accumulate: str = 'exact',
                  defer_steps: int = 0, defer_bytes: int = 32 << 30, reuse_context: bool = False, time_bins=None,
-                 n_probes: int = 0):
+                 n_probes: int = 0, out_hw: Optional[Tuple[int, int]] = None):
         """``accumulate``: ``'exact'`` keeps the running sums in the pipeline dtype like the
         reference (fp16 sums on an fp16 pipeline, heatmap.py:156); ``'float32'`` is the
         accuracy mode.  ``defer_steps`` > 0 records Q/K pointers and taps ``defer_steps``
@@ -189,13 +227,27 @@ class HeatMapEngine:
         ``n_probes`` (0 to 8): every layer also keeps one running sum per probe, in the slot ``(1 + p) * n_layers + layer`` of the same
         context (``probe_slot``), fed by the layer's queries against the probe's keys (``set_probe_keys``); one deferred launch taps
         the generation and every probe.  Each probe costs one more set of sums (221 MB for SDXL-1024 with fp16 sums) and records no
-        Q / K of its own (``defer_bytes`` counts the generation's only)."""
+        Q / K of its own (``defer_bytes`` counts the generation's only).
+        ``out_hw`` = ``(out_h, out_w)``: the map of a non-square generation (``map_geometry``; replaces ``out_side``).  Layers are then
+        ``[heads, tokens, h, w]`` by ``layer_geometry``, maps ``[rows, out_h, out_w]``, and the finalize is ``finalize_rect_kernel``.
+        Not with ``time_bins`` (ValueError); ``daam_finalize_prepare`` does not apply (the finalize clears its output itself).
+        Equal sides are ``out_side``."""
         if accumulate not in ('exact', 'float32'):
             raise ValueError("accumulate must be 'exact' or 'float32'")
         self.lib = nat.load()
         self.n_layers = int(n_layers)
         self.tokens = int(tokens)
         self.out_side = int(out_side)
+        if out_hw is not None:
+            self.out_h, self.out_w = int(out_hw[0]), int(out_hw[1])
+            if not (1 <= self.out_h <= MAX_MAP_SIDE and 1 <= self.out_w <= MAX_MAP_SIDE):
+                raise ValueError(f'out_hw {out_hw!r}: 1 to {MAX_MAP_SIDE} cells per side')
+            self.out_side = self.out_h                    # read only where the sides are equal
+        else:
+            self.out_h = self.out_w = self.out_side
+        self.rect = self.out_h != self.out_w
+        if self.rect and time_bins is not None:
+            raise ValueError('time_bins cannot be combined with a non-square map (height= / width=)')
         self.accumulate = accumulate
         self.time_bins = check_time_bins(time_bins)
         self.n_bins = len(self.time_bins) if self.time_bins is not None else 0
@@ -292,9 +344,13 @@ class HeatMapEngine:
             return
         ctx = nat.c_void_p()
         with torch.cuda.device(self.device):
-            nat.check(self.lib.daam_ctx_create(self.n_layers * (1 + self.n_probes), self.tokens, self.out_side,
-                                               _DTYPE_CODE[self.acc_dtype],
-                                               nat.byref(ctx)))
+            if self.rect:
+                nat.check(self.lib.daam_ctx_create_rect(self.n_layers * (1 + self.n_probes), self.tokens, self.out_h, self.out_w,
+                                                        _DTYPE_CODE[self.acc_dtype], nat.byref(ctx)))
+            else:
+                nat.check(self.lib.daam_ctx_create(self.n_layers * (1 + self.n_probes), self.tokens, self.out_side,
+                                                   _DTYPE_CODE[self.acc_dtype],
+                                                   nat.byref(ctx)))
         if self.time_bins is not None:
             try:
                 nat.check(self.lib.daam_ctx_set_time_bins(ctx, self.n_bins, (ctypes.c_int32 * self.n_bins)(*self.time_bins)))
@@ -307,7 +363,8 @@ class HeatMapEngine:
     def _park_key(self) -> tuple:
         # DAAM_TAP_WALK is read when a native context is created: a context parked without the switch is not adopted with it
         walk = os.environ.get('DAAM_TAP_WALK', '')[:1] == '1'
-        return (str(self.device), self.n_layers, self.tokens, self.out_side, self.acc_dtype, walk, self.time_bins, self.n_probes)
+        side = (self.out_h, self.out_w) if self.rect else self.out_side
+        return (str(self.device), self.n_layers, self.tokens, side, self.acc_dtype, walk, self.time_bins, self.n_probes)
 
     def close(self) -> None:
         if self.ctx is not None:
@@ -349,17 +406,32 @@ class HeatMapEngine:
     def stream(self) -> int:
         return self._current_stream().cuda_stream
 
-    def _ensure_layer(self, layer: int, heads: int, side: int, factor: int) -> None:
+    def _side(self, hw: int, factor: int):
+        """A tapped call's layer size: ``int(sqrt(hw))`` (trace.py:233), or ``(h, w)`` on a non-square map (``layer_geometry``; the
+        caller's factor must be the rule's)."""
+        if not self.rect:
+            return int(math.sqrt(hw))
+        f, h, w = layer_geometry(self.out_h, self.out_w, hw)
+        if f != factor:
+            raise ValueError(f'a layer of {hw} query positions on a {self.out_h} x {self.out_w} map has factor {f}, the call says {factor}')
+        return (h, w)
+
+    def _ensure_layer(self, layer: int, heads: int, side, factor: int) -> None:
+        """``side``: an int, or ``(h, w)`` (``_side``)."""
         info = self.layer_info.get(layer)
         if info == (factor, heads, side):
             return
         if info is not None:
             # the reference would simply start a new key set / fail on a shape mismatch in `+`
             self.flush()
-        shape = (heads, self.tokens, side, side) if self.time_bins is None else (self.n_bins, heads, self.tokens, side, side)
+        h, w = side if isinstance(side, tuple) else (side, side)
+        shape = (heads, self.tokens, h, w) if self.time_bins is None else (self.n_bins, heads, self.tokens, h, w)
         for slot in [layer] + [self.probe_slot(p, layer) for p in range(self.n_probes)]:     # a probe's sums: the layer's geometry
             buf = torch.zeros(shape, dtype=self.acc_dtype, device=self.device)
-            nat.check(self.lib.daam_layer_configure(self.ctx, slot, heads, side, factor, buf.data_ptr()))
+            if isinstance(side, tuple):
+                nat.check(self.lib.daam_layer_configure_rect(self.ctx, slot, heads, h, w, factor, buf.data_ptr()))
+            else:
+                nat.check(self.lib.daam_layer_configure(self.ctx, slot, heads, side, factor, buf.data_ptr()))
             self.acc[slot] = buf
             self.layer_info[slot] = (factor, heads, side)
         self._mask_cache.clear()
@@ -507,7 +579,7 @@ class HeatMapEngine:
         b, hw, c = query.shape
         tokens = key.shape[1]
         d = c // heads
-        side = int(math.sqrt(hw))
+        side = self._side(hw, factor)
         bh = b * heads
         self._ensure_layer(layer, bh - bh // 2, side, factor)
         desc = nat.QKDesc(
@@ -732,7 +804,7 @@ class HeatMapEngine:
         b, hw, c = query.shape
         d = c // heads
         bh = b * heads
-        self._ensure_layer(layer, bh - bh // 2, int(math.sqrt(hw)), factor)
+        self._ensure_layer(layer, bh - bh // 2, self._side(hw, factor), factor)
         desc = nat.QKDesc(in_dtype=_DTYPE_CODE[query.dtype], batch=b, heads=heads, hw=hw, tokens=self.tokens, head_dim=d,
                           round_logits=1 if round_logits else 0, scale=float(scale),
                           q_stride_b=hw * c, q_stride_h=d, q_stride_p=c,
@@ -791,8 +863,8 @@ class HeatMapEngine:
             raise LookupError('no heat maps')
         rows = [max(1, min(int(n_rows[g // n_prompts]), self.tokens)) for g in range(n_groups)]
         self.flush()
-        plane = self.tokens * self.out_side * self.out_side
-        out = torch.empty(n_groups, self.tokens, self.out_side, self.out_side, dtype=torch.float32, device=self.device)
+        plane = self.tokens * self.out_h * self.out_w
+        out = torch.empty(n_groups, self.tokens, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
         i32 = ctypes.c_int32
         for start in range(0, n_groups, 64):                    # the library takes at most 64 groups per call
             n = min(64, n_groups - start)
@@ -815,7 +887,7 @@ class HeatMapEngine:
         self.flush()
         probs = probs if probs.is_contiguous() else probs.contiguous()
         bh, hw, tokens = probs.shape
-        self._ensure_layer(layer, bh - bh // 2, int(math.sqrt(hw)), factor)
+        self._ensure_layer(layer, bh - bh // 2, self._side(hw, factor), factor)
         nat.check(self.lib.daam_tap_probs(self.ctx, layer, probs.data_ptr(),
                                           _DTYPE_CODE[probs.dtype],
                                           bh, hw, tokens, self.stream))
@@ -947,7 +1019,12 @@ class HeatMapEngine:
         if n == 0:
             self.flush()
             raise LookupError('no heat maps')
-        out = torch.empty(rows, self.out_side, self.out_side, dtype=torch.float32, device=self.device)
+        out = torch.empty(rows, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
+        if self.rect:
+            # no announcement on a non-square map (daam_finalize_prepare is DAAM_E_UNSUPPORTED there): the finalize clears its output
+            self.flush()
+            nat.check(self.lib.daam_finalize(self.ctx, mask, rows, out.data_ptr(), self.stream))
+            return out
         # the output is announced BEFORE the deferred taps go out: the launch's table-upload kernel clears it and the key tables
         # stay on the device between generations, so the finalize call below is its class kernel(s) only (daam_finalize_prepare)
         optr = out.data_ptr()
@@ -1005,9 +1082,9 @@ class HeatMapEngine:
             raise LookupError('no heat maps')
         rows = [max(1, min(int(r), self.tokens)) for r in n_rows]
         self.flush()
-        out = torch.empty(n_groups, self.tokens, self.out_side, self.out_side, dtype=torch.float32, device=self.device)
+        out = torch.empty(n_groups, self.tokens, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
         nat.check(self.lib.daam_finalize_groups(self.ctx, table, n_groups, (ctypes.c_int32 * n_groups)(*rows), out.data_ptr(),
-                                                self.tokens * self.out_side * self.out_side, self.stream))
+                                                self.tokens * self.out_h * self.out_w, self.stream))
         return out
 
     def time_heat_maps(self, groups: Sequence[Tuple[int, int, int]], n_prompts: int, n_rows: Sequence[int],
@@ -1035,8 +1112,8 @@ class HeatMapEngine:
             raise LookupError('no heat maps')
         rows = [max(1, min(int(r), self.tokens)) for r in n_rows]
         self.flush()
-        plane = self.tokens * self.out_side * self.out_side
-        out = torch.empty(len(groups), self.tokens, self.out_side, self.out_side, dtype=torch.float32, device=self.device)
+        plane = self.tokens * self.out_h * self.out_w
+        out = torch.empty(len(groups), self.tokens, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
         for start in range(0, len(groups), 64):                 # the library takes at most 64 groups per call
             part = groups[start:start + 64]
             n = len(part)
@@ -1047,8 +1124,12 @@ class HeatMapEngine:
         return out
 
     def normalize_(self, maps: torch.Tensor) -> torch.Tensor:
-        """trace.py:129-130, in place on ``maps`` [n_rows, x, x] (contiguous fp32)."""
-        nat.check(self.lib.daam_epilogue_normalize(maps.data_ptr(), maps.shape[0], maps.shape[-1], self.stream))
+        """trace.py:129-130, in place on ``maps`` [n_rows, x, x] -- or [n_rows, out_h, out_w] -- (contiguous fp32)."""
+        h, w = maps.shape[-2:]
+        if h == w:
+            nat.check(self.lib.daam_epilogue_normalize(maps.data_ptr(), maps.shape[0], w, self.stream))
+        else:
+            nat.check(self.lib.daam_epilogue_normalize_rect(maps.data_ptr(), maps.shape[0], h, w, self.stream))
         return maps
 
 
@@ -1073,19 +1154,27 @@ def prompt_key_groups(layout: Sequence[Tuple[int, int, int, int]], total: int, n
     return groups
 
 
-def word_heat_map(maps: torch.Tensor, idxs: Sequence[int]) -> torch.Tensor:
-    """heatmap.py:121-123: mean of the planes ``idxs`` of ``maps`` [rows, s, s] -> [s, s]."""
+def _launch_word(src: torch.Tensor, idxs: Sequence[int], word: torch.Tensor, out: Optional[torch.Tensor], absolute: bool,
+                 threshold: float) -> None:
+    """``daam_word_heat_map`` on square planes ``src`` [rows, s, s], ``daam_word_heat_map_rect`` on [rows, h, w]: the one place that
+    chooses between them.  ``word`` takes the mean of the planes ``idxs``, ``out`` (or None) its resize."""
     lib = nat.load()
+    h, w = src.shape[-2:]
+    fn, size = (lib.daam_word_heat_map, (h,)) if h == w else (lib.daam_word_heat_map_rect, (h, w))
+    ws = torch.empty(2, dtype=torch.float32, device=src.device)
+    out_ptr, out_h, out_w = (None, 0, 0) if out is None else (out.data_ptr(), out.shape[0], out.shape[1])
+    nat.check(fn(src.data_ptr(), *size, (ctypes.c_int32 * len(idxs))(*[int(i) for i in idxs]), len(idxs), word.data_ptr(), out_ptr,
+                 out_h, out_w, 1 if absolute else 0, threshold, ws.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream))
+
+
+def word_heat_map(maps: torch.Tensor, idxs: Sequence[int]) -> torch.Tensor:
+    """heatmap.py:121-123: mean of the planes ``idxs`` of ``maps`` [rows, s, s] -> [s, s] (or [rows, h, w] -> [h, w])."""
     _check_maps(maps)
-    side = maps.shape[-1]
-    idx = (ctypes.c_int32 * len(idxs))(*[int(i) for i in idxs])
     for i in idxs:
         if not 0 <= int(i) < maps.shape[0]:
             raise IndexError(f'index {i} is out of bounds for dimension 0 with size {maps.shape[0]}')
-    word = torch.empty(side, side, dtype=torch.float32, device=maps.device)
-    ws = torch.empty(2, dtype=torch.float32, device=maps.device)
-    nat.check(lib.daam_word_heat_map(maps.data_ptr(), side, idx, len(idxs), word.data_ptr(), None, 0, 0, 1, 0.0,
-                                     ws.data_ptr(), torch.cuda.current_stream(maps.device).cuda_stream))
+    word = torch.empty(maps.shape[-2], maps.shape[-1], dtype=torch.float32, device=maps.device)
+    _launch_word(maps, idxs, word, None, True, 0.0)
     return word
 
 
@@ -1093,23 +1182,16 @@ def expand_word_map(word: torch.Tensor, out_h: int, out_w: int, absolute: bool =
                     threshold: Optional[float] = None) -> torch.Tensor:
     """heatmap.py:77-93 up to (not including) the ``.cpu()``: bicubic to ``out_h x out_w``,
     min-max normalise unless ``absolute``, optional threshold."""
-    lib = nat.load()
-    if word.device.type != 'cuda' or word.dtype != torch.float32 or word.dim() != 2 or word.shape[0] != word.shape[1]:
-        raise RuntimeError('daam_amd: expand_as needs a square fp32 word map on the HIP device')
+    if word.device.type != 'cuda' or word.dtype != torch.float32 or word.dim() != 2:
+        raise RuntimeError('daam_amd: expand_as needs an fp32 [h, w] word map on the HIP device')
     word = word.contiguous()
-    side = word.shape[-1]
     out = torch.empty(out_h, out_w, dtype=torch.float32, device=word.device)
-    tmp = torch.empty(side, side, dtype=torch.float32, device=word.device)
-    ws = torch.empty(2, dtype=torch.float32, device=word.device)
-    idx = (ctypes.c_int32 * 1)(0)
-    nat.check(lib.daam_word_heat_map(word.data_ptr(), side, idx, 1, tmp.data_ptr(), out.data_ptr(), out_h, out_w,
-                                     1 if absolute else 0, float(threshold) if threshold else 0.0, ws.data_ptr(),
-                                     torch.cuda.current_stream(word.device).cuda_stream))
+    _launch_word(word, [0], torch.empty_like(word), out, absolute, float(threshold) if threshold else 0.0)
     return out
 
 
 def _check_maps(maps: torch.Tensor) -> None:
     if maps.device.type != 'cuda':
         raise RuntimeError('daam_amd: heat maps must live on the HIP device (no CPU fallback)')
-    if maps.dtype != torch.float32 or not maps.is_contiguous() or maps.dim() != 3 or maps.shape[1] != maps.shape[2]:
-        raise RuntimeError('daam_amd: heat maps must be a contiguous fp32 [rows, s, s] tensor')
+    if maps.dtype != torch.float32 or not maps.is_contiguous() or maps.dim() != 3:
+        raise RuntimeError('daam_amd: heat maps must be a contiguous fp32 [rows, h, w] tensor')

@@ -65,8 +65,11 @@ class WordHeatMap:
                   **plot_kwargs) -> torch.Tensor:
         """Bicubic to ``(image.size[0], image.size[1])`` (PIL order, as the reference passes
         it, heatmap.py:80), min-max normalise unless ``absolute``, optional threshold; returns a
-        CPU tensor like the reference (heatmap.py:88)."""
-        out = _engine.expand_word_map(self.heatmap.float(), int(image.size[0]), int(image.size[1]),
+        CPU tensor like the reference (heatmap.py:88).  A word map of unequal sides (a non-square generation,
+        ``trace(pipe, height=, width=)``) is resized to ``(image.size[1], image.size[0])`` = ``[image height, image width]`` instead:
+        PIL's ``size`` is (width, height), which the reference's order only survives on square images."""
+        size = (image.size[0], image.size[1]) if self.heatmap.shape[-2] == self.heatmap.shape[-1] else (image.size[1], image.size[0])
+        out = _engine.expand_word_map(self.heatmap.float(), int(size[0]), int(size[1]),
                                       absolute=absolute, threshold=threshold)
         out = out.cpu()
         if plot:

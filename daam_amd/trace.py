@@ -25,7 +25,7 @@ from typing import Any, List, Optional, Type, Union
 import torch
 import torch.nn.functional as F
 
-from .engine import HeatMapEngine, check_probes, check_time_bins
+from .engine import HeatMapEngine, check_probes, check_time_bins, map_geometry
 from .heatmap import GlobalHeatMap, RawHeatMapCollection
 from .hook import AggregateHooker, ObjectHooker, UNetCrossAttentionLocator
 from .utils import cache_dir
@@ -94,7 +94,7 @@ class DiffusionHeatMapHooker(AggregateHooker):
     def __init__(self, pipeline, low_memory: bool = False, load_heads: bool = False, save_heads: bool = False,
                  data_dir: Optional[str] = None, *, accumulate: str = 'exact', tap: str = 'qk',
                  defer_steps: Optional[int] = None, batch_prompts: bool = False, time_bins=None, probes=None,
-                 probe_embeds: Optional[torch.Tensor] = None):
+                 probe_embeds: Optional[torch.Tensor] = None, height: Optional[int] = None, width: Optional[int] = None):
         """Positional arguments as in the reference (trace.py:23-30).  Keyword-only extras:
         ``accumulate`` = ``'exact'`` (running sums in the pipeline dtype, like the reference) or
         ``'float32'``; ``tap`` = ``'qk'`` (fused, default) or ``'probs'`` (materialised
@@ -118,7 +118,14 @@ class DiffusionHeatMapHooker(AggregateHooker):
         ``pipe.encode_prompt(p, device=..., num_images_per_prompt=1, do_classifier_free_guidance=False)[0]``, encoded once here;
         ``probe_embeds`` ([P, 77, C]) replaces that encoding (the strings still name the tokens).  ``compute_probe_heat_map(p)`` /
         ``compute_probe_heat_maps()`` / ``raw_probe_heat_maps(p)`` read them.  Each probe holds one more set of running sums (221 MB
-        for SDXL-1024 with fp16 sums).  Not with ``time_bins``, ``save_heads`` or ``load_heads`` (ValueError)."""
+        for SDXL-1024 with fp16 sums).  Not with ``time_bins``, ``save_heads`` or ``load_heads`` (ValueError).
+        ``height`` / ``width`` (both or neither; ints): the pixel size that will be passed to ``pipe(...)``, for generations that are
+        not the pipeline's default square -- SDXL at 832 x 1216 and the like.  The map is then ``out_h x out_w`` =
+        ``height // cell x width // cell`` with ``cell`` = 8 px (SD) or 16 px (SDXL) (``engine.map_geometry``: both sizes multiples of
+        ``2 * cell``, at most 128 cells per side), the running sums are ``[heads, 77, h, w]`` per layer (position ``p`` = pixel
+        ``(p // w, p % w)``) and every ``compute_*_heat_map(s)`` returns ``[rows, out_h, out_w]`` maps.  A tapped layer whose size
+        does not divide the map by its factor is a ValueError.  ``height == width ==`` the pipeline's default size is the default
+        trace.  Not with ``time_bins`` (ValueError: the window-range reduction is not extended to such maps)."""
         if tap not in ('qk', 'probs'):
             raise ValueError("tap must be 'qk' or 'probs'")
         self.probes = check_probes(probes, time_bins)
@@ -130,12 +137,23 @@ class DiffusionHeatMapHooker(AggregateHooker):
             raise ValueError('probe_embeds needs probes (the strings that name its tokens)')
         h = pipeline.unet.config.sample_size * pipeline.vae_scale_factor
         self.latent_hw = 4096 if h == 512 or h == 1024 else 9216          # trace.py:32-33
+        out_hw = None
+        if height is not None or width is not None:
+            if height is None or width is None:
+                raise ValueError('height and width go together: pass both (the size given to pipe(...)) or neither')
+            if time_bins is not None:
+                raise ValueError('time_bins cannot be combined with height / width')
+            out_hw = map_geometry(h, height, width)
+            if out_hw[0] * out_hw[1] == self.latent_hw and out_hw[0] == out_hw[1]:
+                out_hw = None                                              # the pipeline's default size: the default trace
+            else:
+                self.latent_hw = out_hw[0] * out_hw[1]                     # trace.py:285 takes the factor from it
         locate_middle = load_heads or save_heads
         self.locator = UNetCrossAttentionLocator(restrict={0} if low_memory else None,
                                                  locate_middle_block=locate_middle)
         modules_found = self.locator.locate(pipeline.unet)
-        self.engine = HeatMapEngine(max(1, len(modules_found)), tokens=77, out_side=int(math.sqrt(self.latent_hw)),
-                                    accumulate=accumulate,
+        self.engine = HeatMapEngine(max(1, len(modules_found)), tokens=77,
+                                    out_side=int(math.sqrt(self.latent_hw)), out_hw=out_hw, accumulate=accumulate,
                                     defer_steps=_default_defer() if defer_steps is None else defer_steps,
                                     defer_bytes=_default_defer_bytes(pipeline), reuse_context=True, time_bins=self.time_bins,
                                     n_probes=len(self.probes) if self.probes is not None else 0)

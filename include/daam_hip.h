@@ -67,7 +67,7 @@ typedef struct DaamQKDesc {
     int32_t in_dtype;        /* DAAM_F16 | DAAM_F32 | DAAM_BF16: dtype of q and k (the pipeline dtype) */
     int32_t batch;           /* B */
     int32_t heads;           /* H */
-    int32_t hw;              /* query positions = h*w, square (trace.py:233) */
+    int32_t hw;              /* query positions = h*w (trace.py:233), pixel (p / w, p % w) */
     int32_t tokens;          /* key positions; only ctx->tokens (77) is tapped (trace.py:289) */
     int32_t head_dim;        /* d */
     int32_t round_logits;    /* 1: round scale*q.k to in_dtype before softmax (baddbmm output
@@ -86,12 +86,29 @@ typedef struct DaamQKDesc {
  * mode.  Activations must have the dtype of the sums, or the sums must be DAAM_F32. */
 DAAM_API int daam_ctx_create(int max_layers, int tokens, int out_side, int acc_dtype, DaamCtx** out);
 DAAM_API int daam_ctx_destroy(DaamCtx* ctx);
+/* Non-square generations (same ABI version: additive).  The reference fixes a square latent (latent_hw, trace.py:32-33) and takes
+ * x = int(sqrt(latent_hw)) as the map side (trace.py:109); a generation of height x width pixels has out_h x out_w map cells
+ * instead (1 <= out_h, out_w <= 128), and the bicubic of trace.py:116 resizes each [h, w] plane to it with one tap table per axis.
+ * daam_ctx_create(.., s, ..) is daam_ctx_create_rect(.., s, s, ..).  On a context with
+ * out_h != out_w -- or with a layer of unequal sides -- daam_finalize and daam_finalize_groups run finalize_rect_kernel
+ * (daam_finalize_rect.hip: separable bicubic with one tap table per axis, f32 arithmetic on any finite planes, the
+ * err_t <= 2^-19 * rowmax_t class below; DAAM_E_UNSUPPORTED when a selection's planes need more than 160 KB of LDS), and
+ * daam_ctx_set_time_bins and daam_finalize_prepare are DAAM_E_UNSUPPORTED (daam_finalize then clears its output itself), and so
+ * is daam_finalize_bins whenever the call needs the window-range reduction: a group over more than one window, or two groups
+ * over the same window and key set (also with a single window).  Groups of one window each with distinct key sets are served:
+ * that is daam_finalize_groups. */
+DAAM_API int daam_ctx_create_rect(int max_layers, int tokens, int out_h, int out_w, int acc_dtype, DaamCtx** out);
 
 /* Declare layer `layer` (= position in UNetCrossAttentionLocator.locate order, trace.py:45,50):
  * `heads` = kept batch*heads entries (BH - BH/2), `side` = sqrt(hw), `factor` =
  * int(sqrt(latent_hw // hw)) (trace.py:285).  `acc` = caller-owned zero-initialised device
  * buffer [heads, tokens, side, side] of acc_dtype, or NULL to let the library allocate it. */
 DAAM_API int daam_layer_configure(DaamCtx* ctx, int layer, int heads, int side, int factor, void* acc);
+/* daam_layer_configure for a layer of h x w query positions: position p is pixel (p / w, p % w), row-major as the NCHW
+ * activations are flattened (trace.py:233 reshapes to [heads, tokens, h, w] with h = w); `factor` = int(sqrt(out_h * out_w // (h * w)))
+ * (trace.py:285 with latent_hw = out_h * out_w); `acc` is [heads, tokens, h, w].  The taps read only h * w (DaamQKDesc.hw).
+ * daam_layer_configure(.., side, ..) is the h == w case.  DAAM_E_UNSUPPORTED for h != w on a time-binned context. */
+DAAM_API int daam_layer_configure_rect(DaamCtx* ctx, int layer, int heads, int h, int w, int factor, void* acc);
 DAAM_API int daam_layer_acc(DaamCtx* ctx, int layer, void** acc, size_t* bytes);
 /* The caller is about to write into the layer's sums itself (RawHeatMapCollection.update called by hand,
  * heatmap.py:153-156): a zeroing still owed to the buffer since the last daam_reset is enqueued on `stream` first,
@@ -232,6 +249,8 @@ DAAM_API int daam_finalize_bins(DaamCtx* ctx, const int32_t* key_group, int n_gr
 /* trace.py:129-130: maps[:n_rows] / (maps[1:n_rows-1].sum(0) + 1e-6), in place on the first
  * n_rows planes of `maps` [*, side, side] fp32. */
 DAAM_API int daam_epilogue_normalize(float* maps, int n_rows, int side, void* stream);
+/* the same on planes of h x w (trace.py:129-130 does not look at the shape); the square call is h == w == side */
+DAAM_API int daam_epilogue_normalize_rect(float* maps, int n_rows, int h, int w, void* stream);
 
 /* ---- word maps (next row f1) -------------------------------------------------------------
  * heatmap.py:121-123 + 77-93: mean of the planes `idx[0..n_idx)` (HOST int array) of
@@ -240,6 +259,11 @@ DAAM_API int daam_epilogue_normalize(float* maps, int n_rows, int side, void* st
  * the un-expanded mean plane; `out` [out_h, out_w] fp32 (NULL: only the mean plane is computed);
  * `workspace` >= 2 floats of device scratch for the min/max. */
 DAAM_API int daam_word_heat_map(const float* maps, int side, const int32_t* idx, int n_idx, float* word_map,
+                       float* out, int out_h, int out_w, int absolute, float threshold,
+                       float* workspace, void* stream);
+/* the same from maps[*, h, w]: word_map is [h * w], the bicubic reads a rectangular source (heatmap.py:77-93 generalised: the
+ * reference's F.interpolate takes any source shape); the square call is h == w == side */
+DAAM_API int daam_word_heat_map_rect(const float* maps, int h, int w, const int32_t* idx, int n_idx, float* word_map,
                        float* out, int out_h, int out_w, int absolute, float threshold,
                        float* workspace, void* stream);
 
