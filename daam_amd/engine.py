@@ -49,6 +49,16 @@ class CallShape:
 _DTYPE_CODE = {torch.float16: nat.DAAM_F16, torch.float32: nat.DAAM_F32, torch.bfloat16: nat.DAAM_BF16}
 
 
+def _contiguous_qk_desc(dtype, b, heads, hw, tokens, c, scale, round_logits, k_stride_b=None) -> 'nat.QKDesc':
+    """``DaamQKDesc`` of contiguous ``query`` [b, hw, c] / ``key`` [b, tokens, c] straight out of the projections (``c`` =
+    ``heads * head_dim``).  ``k_stride_b=0``: one key set serves every batch entry (the probes)."""
+    d = c // heads
+    return nat.QKDesc(in_dtype=_DTYPE_CODE[dtype], batch=b, heads=heads, hw=hw, tokens=tokens, head_dim=d,
+                      round_logits=1 if round_logits else 0, scale=float(scale),
+                      q_stride_b=hw * c, q_stride_h=d, q_stride_p=c,
+                      k_stride_b=tokens * c if k_stride_b is None else k_stride_b, k_stride_h=d, k_stride_t=c)
+
+
 # Parked native contexts (with their running-sum buffers) of closed engines, per (device, layers, tokens, map side,
 # sum dtype).  A pipeline is usually traced once per generation: re-adopting the previous trace's context saves the
 # 1.5 ms of set-up / tear-down and the device synchronisation that destroying a context implies (hipFree).
@@ -280,7 +290,7 @@ class HeatMapEngine:
         self._qk_cache: List[Optional[CallShape]] = [None] * self.n_layers
         self._att_cache: List[Optional[CallShape]] = [None] * self.n_layers   # attend(): per-layer call descriptors
         self._touched_flag: List[bool] = [False] * self.n_layers
-        self._mask_cache: Dict[tuple, tuple] = {}        # finalize key masks per selection
+        self._mask_cache: Dict[tuple, tuple] = {}        # finalize key tables per selection (_select)
         # deferred mode: the per-call bookkeeping runs in the C++ recorder (csrc/daam_fastpath.cpp) when
         # that extension is built; the Python implementation below is the same logic and stays the
         # slow path (first call of a layer, shape changes) and the fallback.  Both only record host-side
@@ -381,15 +391,20 @@ class HeatMapEngine:
                 self.lib.daam_ctx_destroy(self.ctx)
             self.ctx = None
             self._sync_native()
-        self.acc.clear()
-        self.layer_info.clear()
+        self._forget_layers()
         self.touched.clear()
         self._touched_flag = [False] * self.n_layers
+        self._drop_recorded()
+
+    def _forget_layers(self) -> None:
+        """No layer is configured any more: the sum buffers go (to whoever still holds them), and with them everything that was
+        derived per layer -- the validated call shapes of both recorders and the finalize key tables."""
+        self.acc, self.layer_info = {}, {}
         self._qk_cache = [None] * self.n_layers
         self._att_cache = [None] * self.n_layers
+        self._mask_cache.clear()
         if self._fast is not None:
             self._fast.invalidate()
-        self._drop_recorded()
 
     def __del__(self):
         if sys is None or sys.is_finalizing():          # no HIP calls while the interpreter (and the HIP runtime) shut down
@@ -467,12 +482,7 @@ class HeatMapEngine:
             if self.ctx is not None:
                 for layer in list(self.layer_info):
                     nat.check(self.lib.daam_layer_release(self.ctx, layer))
-            self.acc, self.layer_info = {}, {}
-            self._qk_cache = [None] * self.n_layers
-            self._att_cache = [None] * self.n_layers
-            self._mask_cache.clear()
-            if self._fast is not None:
-                self._fast.invalidate()
+            self._forget_layers()
             self._views_out = False
 
     # ---- tap -------------------------------------------------------------------------------------
@@ -560,6 +570,14 @@ class HeatMapEngine:
         if self._fast is not None:
             self._fast.set_window(w)
 
+    def _ensure_call_layer(self, layer: int, query: torch.Tensor, heads: int, factor: int) -> Tuple[int, int, int]:
+        """Configure ``layer`` for a call whose ``query`` is [B, hw, heads*d]: the kept (conditional) half of ``B * heads`` planes
+        of ``_side(hw, factor)``.  Returns ``query.shape``."""
+        b, hw, c = query.shape
+        bh = b * heads
+        self._ensure_layer(layer, bh - bh // 2, self._side(hw, factor), factor)
+        return b, hw, c
+
     def _prepare_qk(self, layer, query, key, heads, scale, factor, round_logits):
         """Slow path of ``tap_qk``: validate, (re)configure the layer, build the call descriptor.
         Returns ``(query, key, cache entry)`` with both tensors contiguous."""
@@ -576,18 +594,8 @@ class HeatMapEngine:
         if self.acc_dtype not in (torch.float32, query.dtype):
             raise RuntimeError(f'daam_amd: {query.dtype} activations on a trace whose running sums are {self.acc_dtype} '
                                '(fp32 activations need fp32 sums; fp16 / bf16 sums need activations of the same dtype)')
-        b, hw, c = query.shape
-        tokens = key.shape[1]
-        d = c // heads
-        side = self._side(hw, factor)
-        bh = b * heads
-        self._ensure_layer(layer, bh - bh // 2, side, factor)
-        desc = nat.QKDesc(
-            in_dtype=_DTYPE_CODE[query.dtype],
-            batch=b, heads=heads, hw=hw, tokens=tokens, head_dim=d, round_logits=1 if round_logits else 0,
-            scale=float(scale),
-            q_stride_b=hw * c, q_stride_h=d, q_stride_p=c,
-            k_stride_b=tokens * c, k_stride_h=d, k_stride_t=c)
+        b, hw, c = self._ensure_call_layer(layer, query, heads, factor)
+        desc = _contiguous_qk_desc(query.dtype, b, heads, hw, key.shape[1], c, scale, round_logits)
         # a shape change of a layer inside a deferred batch starts a new batch (the C side checks too)
         if self._pending(layer):
             self.flush()
@@ -648,10 +656,7 @@ class HeatMapEngine:
             self._ensure_ctx(query.dtype)
             if self.acc_dtype in (query.dtype, torch.float32):
                 b, hw, c = query.shape
-                qk = nat.QKDesc(in_dtype=_DTYPE_CODE[query.dtype], batch=b, heads=heads, hw=hw, tokens=self.tokens, head_dim=d,
-                                round_logits=1 if round_logits else 0, scale=float(scale),
-                                q_stride_b=hw * c, q_stride_h=d, q_stride_p=c,
-                                k_stride_b=self.tokens * c, k_stride_h=d, k_stride_t=c)
+                qk = _contiguous_qk_desc(query.dtype, b, heads, hw, self.tokens, c, scale, round_logits)
                 desc = nat.AttendDesc(qk=qk, v_stride_b=self.tokens * c, v_stride_h=d, v_stride_t=c,
                                       o_stride_b=hw * c, o_stride_h=d, o_stride_p=c)
         entry = CallShape(query, key, heads, scale, round_logits, 0, desc)
@@ -677,30 +682,33 @@ class HeatMapEngine:
         (stream order keeps their memory valid until the kernel has consumed it).  ``_before_launch(stream)`` is called between
         handing the recorded calls to the library and the launch (``global_heat_map`` announces its output there, so that the
         launch's table-upload kernel clears it).  Returns whether anything was launched."""
-        if self._fast is not None:
-            n, la, qa, ka, da = self._fast.buffers()
-            if self.ctx is None or n == 0:
-                return False
-            try:
-                stream, rec_stream = self._launch_stream()
-                if self.n_probes:
-                    arrays = [np.ctypeslib.as_array((t * n).from_address(a)) for t, a in
-                              ((ctypes.c_int32, la), (ctypes.c_uint64, qa), (ctypes.c_uint64, ka), (ctypes.c_uint64, da))]
-                    n, arrays = self._with_probes(*arrays)
-                    la, qa, ka, da = (a.ctypes.data for a in arrays)
-                nat.check(self.lib.daam_tap_qk_enqueue_many(self.ctx, n, la, qa, ka, da))
-                self._announce_then_launch(_before_launch, stream)
-                if rec_stream is not None:
-                    # the Q / K blocks return to the recording stream's allocator pool: not before the tap has read them
-                    rec_stream.wait_stream(self._current_stream())
-                self._set_window(self.defer_steps)
-            finally:
-                self._drop_recorded()
-            return True
-        rec = self._rec
-        n = len(rec)
+        # the two recorders differ only in where the four arrays live; ``keep`` holds the Python recorder's until the call is made
+        n, la, qa, ka, da, keep = (*self._fast.buffers(), None) if self._fast is not None else self._rec_buffers()
         if self.ctx is None or n == 0:
             return False
+        try:
+            stream, rec_stream = self._launch_stream()
+            if self.n_probes:
+                arrays = [np.ctypeslib.as_array((t * n).from_address(a)) for t, a in
+                          ((ctypes.c_int32, la), (ctypes.c_uint64, qa), (ctypes.c_uint64, ka), (ctypes.c_uint64, da))]
+                n, keep = self._with_probes(*arrays)
+                la, qa, ka, da = (a.ctypes.data for a in keep)
+            nat.check(self.lib.daam_tap_qk_enqueue_many(self.ctx, n, la, qa, ka, da))
+            self._announce_then_launch(_before_launch, stream)
+            if rec_stream is not None:
+                # the Q / K blocks return to the recording stream's allocator pool: not before the tap has read them
+                rec_stream.wait_stream(self._current_stream())
+            self._set_window(self.defer_steps)
+        finally:
+            self._drop_recorded()
+        return True
+
+    def _rec_buffers(self):
+        """The Python recorder's calls as the C++ recorder's ``buffers()`` gives its own: ``(n, layers, q, k, desc)``, the four as
+        addresses of int32 / uint64 arrays, plus the arrays themselves (they must outlive the call).  ``n`` = 0 without a context."""
+        rec = self._rec
+        if self.ctx is None or not rec:
+            return 0, 0, 0, 0, 0, None
         if self._check_versions:
             for layer, q, k, _d, qv, kv in rec:
                 if q._version != qv or k._version != kv:
@@ -709,23 +717,9 @@ class HeatMapEngine:
                                        'attention call and the deferred tap launch (use defer_steps=0 for such a pipeline)')
             rec = [r[:4] for r in rec]
         lay_t, q_t, k_t, d_t = zip(*rec)                       # one C-level pass
-        layers = np.array(lay_t, dtype=np.int32)
-        qp = np.array([t.data_ptr() for t in q_t], dtype=np.uint64)
-        kp = np.array([t.data_ptr() for t in k_t], dtype=np.uint64)
-        dp = np.array(d_t, dtype=np.uint64)
-        try:
-            stream, rec_stream = self._launch_stream()
-            if self.n_probes:
-                n, (layers, qp, kp, dp) = self._with_probes(layers, qp, kp, dp)
-            nat.check(self.lib.daam_tap_qk_enqueue_many(self.ctx, n, layers.ctypes.data, qp.ctypes.data, kp.ctypes.data,
-                                                        dp.ctypes.data))
-            self._announce_then_launch(_before_launch, stream)
-            if rec_stream is not None:
-                rec_stream.wait_stream(self._current_stream())
-            self._window = self.defer_steps
-        finally:
-            self._drop_recorded()
-        return True
+        arrays = (np.array(lay_t, dtype=np.int32), np.array([t.data_ptr() for t in q_t], dtype=np.uint64),
+                  np.array([t.data_ptr() for t in k_t], dtype=np.uint64), np.array(d_t, dtype=np.uint64))
+        return (len(rec), *(a.ctypes.data for a in arrays), arrays)
 
     def _announce_then_launch(self, before_launch, stream) -> None:
         """The recorded calls are in the library's hands: whatever ``before_launch`` does, the launch that consumes (and drops) them
@@ -801,14 +795,8 @@ class HeatMapEngine:
             # this call has just flushed it (daam_tap_probs takes no pending taps), so this adds no launch of its own
             self.flush()
         query = query if query.is_contiguous() else query.contiguous()
-        b, hw, c = query.shape
-        d = c // heads
-        bh = b * heads
-        self._ensure_layer(layer, bh - bh // 2, self._side(hw, factor), factor)
-        desc = nat.QKDesc(in_dtype=_DTYPE_CODE[query.dtype], batch=b, heads=heads, hw=hw, tokens=self.tokens, head_dim=d,
-                          round_logits=1 if round_logits else 0, scale=float(scale),
-                          q_stride_b=hw * c, q_stride_h=d, q_stride_p=c,
-                          k_stride_b=0, k_stride_h=d, k_stride_t=c)
+        b, hw, c = self._ensure_call_layer(layer, query, heads, factor)
+        desc = _contiguous_qk_desc(query.dtype, b, heads, hw, self.tokens, c, scale, round_logits, k_stride_b=0)
         stream = self.stream
         for p in range(self.n_probes):
             nat.check(self.lib.daam_tap_qk(self.ctx, self.probe_slot(p, layer), query.data_ptr(), self._probe_key_ptr(layer, p),
@@ -819,59 +807,24 @@ class HeatMapEngine:
         rules of ``items``."""
         if not 0 <= probe < self.n_probes:
             raise IndexError(f'probe {probe} out of range: the trace has {self.n_probes} probe(s)')
-        self.flush()
-        self._views_out = True
-        out: Dict[Key, torch.Tensor] = {}
-        for layer in list(self.touched):
-            factor, heads, _ = self.layer_info[layer]
-            buf = self.acc[self.probe_slot(probe, layer)]
-            for h in range(heads):
-                out[(factor, layer, h)] = buf[h]
-        return out
+        return dict(self._views(lambda layer: self.acc[self.probe_slot(probe, layer)]))
 
     def probe_heat_maps(self, probes: Sequence[int], n_prompts: int, n_rows: Sequence[int], factors: Optional[Sequence[int]] = None,
                         head_idx: Optional[int] = None, layer_idx: Optional[int] = None) -> torch.Tensor:
         """Global heat maps of the probes ``probes`` x ``n_prompts`` prompts from ONE ``daam_finalize_groups`` call (groups of 64 per
         call beyond that): returns ``[len(probes) * n_prompts, tokens, x, x]`` fp32, group ``i * n_prompts + j`` = probe ``probes[i]``
         seen by prompt ``j``, whose rows ``[0, n_rows[i])`` are its map."""
-        if self.ctx is None or not self.touched:
-            raise LookupError('no heat maps')
-        if len(n_rows) != len(probes):
-            raise ValueError(f'{len(n_rows)} row counts for {len(probes)} probes')
-        sel = ('probes', tuple(probes), n_prompts, None if factors is None else tuple(sorted(set(factors))), head_idx, layer_idx,
-               tuple(self.touched), len(self.layer_info))
-        cached = self._mask_cache.get(sel)
+        table, _ = self._select(n_prompts, factors, head_idx, layer_idx, probes=probes, n_rows=n_rows)
         n_groups = len(probes) * n_prompts
-        if cached is None:
-            total = ctypes.c_int()
-            nat.check(self.lib.daam_key_offset(self.ctx, 0, None, ctypes.byref(total)))
-            layout = []
-            for i, p in enumerate(probes):
-                for layer in self.touched:
-                    factor, heads, _ = self.layer_info[layer]
-                    off = ctypes.c_int()
-                    nat.check(self.lib.daam_key_offset(self.ctx, self.probe_slot(p, layer), ctypes.byref(off), None))
-                    layout.append((i, layer, off.value, factor, heads))
-            table = probe_key_groups(layout, total.value, len(probes), n_prompts, factors, head_idx, layer_idx)
-            counts = [table.count(g) for g in range(n_groups)]
-            if len(self._mask_cache) > 64:
-                self._mask_cache.clear()
-            cached = self._mask_cache[sel] = (table, counts)
-        table, counts = cached
-        if min(counts) == 0:
-            self.flush()
-            raise LookupError('no heat maps')
-        rows = [max(1, min(int(n_rows[g // n_prompts]), self.tokens)) for g in range(n_groups)]
+        rows = [self._rows(n_rows[g // n_prompts]) for g in range(n_groups)]
         self.flush()
-        plane = self.tokens * self.out_h * self.out_w
-        out = torch.empty(n_groups, self.tokens, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
         i32 = ctypes.c_int32
-        for start in range(0, n_groups, 64):                    # the library takes at most 64 groups per call
-            n = min(64, n_groups - start)
+
+        def call(start, n, out_ptr, plane):
             part = [g - start if start <= g < start + n else -1 for g in table]
-            nat.check(self.lib.daam_finalize_groups(self.ctx, (i32 * len(part))(*part), n, (i32 * n)(*rows[start:start + n]),
-                                                    out.data_ptr() + start * plane * 4, plane, self.stream))
-        return out
+            return self.lib.daam_finalize_groups(self.ctx, (i32 * len(part))(*part), n, (i32 * n)(*rows[start:start + n]), out_ptr, plane,
+                                                 self.stream)
+        return self._finalize_chunks(n_groups, call)
 
     def tap_probs(self, layer: int, probs: torch.Tensor, factor: int) -> None:
         """``probs`` [B*H, hw, tokens] as returned by ``get_attention_scores`` (trace.py:276).
@@ -928,26 +881,23 @@ class HeatMapEngine:
         the iteration do show up in them."""
         if self.time_bins is not None:
             raise RuntimeError('daam_amd: a trace with time_bins keeps one sum per window: use raw_heat_maps(time_bin)')
+        yield from self._views(lambda layer: self.acc[layer])
+
+    def _views(self, buffer_of) -> Iterator[Tuple[Key, torch.Tensor]]:
+        """The walk behind ``items`` / ``window_items`` / ``probe_items``: launch what is recorded, remember that views of the live
+        buffers are out (``clear`` / ``close``), then every touched layer's ``buffer_of(layer)`` [heads, tokens, h, w] head by head."""
         self.flush()
         self._views_out = True
         for layer in list(self.touched):
             factor, heads, _ = self.layer_info[layer]
-            buf = self.acc[layer]
+            buf = buffer_of(layer)
             for h in range(heads):
                 yield (factor, layer, h), buf[h]
 
     def window_items(self, window: int) -> Dict[Key, torch.Tensor]:
         """``{(factor, layer, head): running sum of window ``window`` [tokens, h, w]}`` -- views of the live buffers, with the
         lifetime rules of ``items``."""
-        self.flush()
-        self._views_out = True
-        out: Dict[Key, torch.Tensor] = {}
-        for layer in list(self.touched):
-            factor, heads, _ = self.layer_info[layer]
-            buf = self.acc[layer][window]
-            for h in range(heads):
-                out[(factor, layer, h)] = buf[h]
-        return out
+        return dict(self._views(lambda layer: self.acc[layer][window]))
 
     def tap_steps(self) -> Dict[int, int]:
         """Taps each touched layer received since the last reset (``daam_tap_steps``; pending deferred taps are launched first)."""
@@ -978,6 +928,69 @@ class HeatMapEngine:
         return False
 
     # ---- finalize ---------------------------------------------------------------------------------
+    def _rows(self, n_rows) -> int:
+        """The crop of trace.py:127 as the library takes it: 1 to ``tokens`` rows."""
+        return max(1, min(int(n_rows), self.tokens))
+
+    def _key_layout(self, slots: Sequence[int]) -> Tuple[int, List[int]]:
+        """``(keys of the context, key offset of every slot of ``slots``)`` in the library's key order (configured slots by index,
+        heads inside): ``daam_key_offset``."""
+        total, off = ctypes.c_int(), ctypes.c_int()
+        nat.check(self.lib.daam_key_offset(self.ctx, 0, None, ctypes.byref(total)))
+        offsets = []
+        for slot in slots:
+            nat.check(self.lib.daam_key_offset(self.ctx, slot, ctypes.byref(off), None))
+            offsets.append(off.value)
+        return total.value, offsets
+
+    def _select(self, n_sets: int, factors, head_idx, layer_idx, probes: Optional[Sequence[int]] = None, used=None,
+                n_rows: Optional[Sequence[int]] = None, mask: bool = False):
+        """What every finalize entry point decides before its library call.  Nothing tapped: LookupError.  ``n_rows`` (the grouped
+        calls): one per prompt -- per probe with ``probes`` --, else ValueError.  Then the key -> group table of the selection:
+        ``prompt_key_groups`` over the touched layers for ``n_sets`` prompts, or ``probe_key_groups`` over the slots of ``probes``
+        (group = probe x prompt); cached per selection -- building it costs more host time than the finalize kernels take on the
+        device -- as ``(table, its ctypes form, keys per group)``; the ctypes form is the int32 table, or with ``mask`` the byte mask
+        ``table >= 0`` of ``daam_finalize``.  A group of ``used`` (default: every group) without a key: the recorded taps are still
+        launched, then LookupError.  Returns ``(table, ctypes form)``; the caller flushes."""
+        if self.ctx is None or not self.touched:
+            raise LookupError('no heat maps')
+        if n_rows is not None and len(n_rows) != (n_sets if probes is None else len(probes)):
+            raise ValueError(f'{len(n_rows)} row counts for {n_sets} prompts' if probes is None else
+                             f'{len(n_rows)} row counts for {len(probes)} probes')
+        sel = (mask, None if probes is None else tuple(probes), n_sets, None if factors is None else tuple(sorted(set(factors))),
+               head_idx, layer_idx, tuple(self.touched), len(self.layer_info))
+        cached = self._mask_cache.get(sel)
+        if cached is None:
+            info = [self.layer_info[layer][:2] for layer in self.touched]
+            if probes is None:
+                total, offs = self._key_layout(self.touched)
+                table = prompt_key_groups([(layer, off, *fh) for layer, off, fh in zip(self.touched, offs, info)], total, n_sets,
+                                          factors, head_idx, layer_idx)
+            else:
+                where = [(i, layer, fh) for i in range(len(probes)) for layer, fh in zip(self.touched, info)]
+                total, offs = self._key_layout([self.probe_slot(probes[i], layer) for i, layer, _ in where])
+                table = probe_key_groups([(i, layer, off, *fh) for (i, layer, fh), off in zip(where, offs)], total, len(probes),
+                                         n_sets, factors, head_idx, layer_idx)
+            counts = [table.count(g) for g in range(n_sets * (1 if probes is None else len(probes)))]
+            form = (ctypes.c_uint8 * total)(*[g >= 0 for g in table]) if mask else (ctypes.c_int32 * total)(*table)
+            if len(self._mask_cache) > 64:
+                self._mask_cache.clear()
+            cached = self._mask_cache[sel] = (table, form, counts)
+        table, form, counts = cached
+        if any(counts[g] == 0 for g in (range(len(counts)) if used is None else used)):
+            self.flush()
+            raise LookupError('no heat maps')
+        return table, form
+
+    def _finalize_chunks(self, n_groups: int, call) -> torch.Tensor:
+        """``[n_groups, tokens, out_h, out_w]`` fp32 from a grouped finalize that takes at most 64 groups per call:
+        ``call(first group, groups, output address of the first, group stride)`` returns the library's status."""
+        plane = self.tokens * self.out_h * self.out_w
+        out = torch.empty(n_groups, self.tokens, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
+        for start in range(0, n_groups, 64):
+            nat.check(call(start, min(64, n_groups - start), out.data_ptr() + start * plane * 4, plane))
+        return out
+
     def global_heat_map(self, factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None,
                         layer_idx: Optional[int] = None, n_rows: Optional[int] = None,
                         bins: Optional[Tuple[int, int]] = None) -> torch.Tensor:
@@ -985,40 +998,14 @@ class HeatMapEngine:
         crop of trace.py:127 applied BEFORE the work: the planes of the token rows nobody reads are neither fetched nor
         written (``daam_finalize``'s ``n_rows``, ABI v6).  ``bins`` = ``(first, end)`` window range of a trace with ``time_bins``
         (default: the whole generation)."""
-        if self._binned(bins):
+        binned = self._binned(bins)
+        rows = self.tokens if n_rows is None else self._rows(n_rows)
+        if binned:
             b0, b1 = bins if bins is not None else (0, self.n_bins)
-            rows = self.tokens if n_rows is None else max(1, min(int(n_rows), self.tokens))
             return self.time_heat_maps([(b0, b1, 0)], 1, [rows], factors, head_idx, layer_idx)[0, :rows]
-        rows = self.tokens if n_rows is None else max(1, min(int(n_rows), self.tokens))
-        fset = {0, 1, 2, 4, 8, 16, 32, 64} if factors is None else set(factors)
-        if self.ctx is None or not self.touched:
-            raise LookupError('no heat maps')
-        # key mask in the library's key order (configured layers by index, heads inside); cached per
-        # selection -- building it costs more host time than the finalize kernels take on the device
-        sel = (tuple(sorted(fset)), head_idx, layer_idx, tuple(self.touched), len(self.layer_info))
-        cached = self._mask_cache.get(sel)
-        if cached is None:
-            total = ctypes.c_int()
-            nat.check(self.lib.daam_key_offset(self.ctx, 0, None, ctypes.byref(total)))
-            mask = (ctypes.c_uint8 * total.value)()
-            n = 0
-            for layer in self.touched:
-                factor, heads, _ = self.layer_info[layer]
-                if factor not in fset or (layer_idx is not None and layer_idx != layer):
-                    continue
-                off = ctypes.c_int()
-                nat.check(self.lib.daam_key_offset(self.ctx, layer, ctypes.byref(off), None))
-                for h in range(heads):
-                    if head_idx is None or head_idx == h:
-                        mask[off.value + h] = 1
-                        n += 1
-            if len(self._mask_cache) > 64:
-                self._mask_cache.clear()
-            cached = self._mask_cache[sel] = (mask, n)
-        mask, n = cached
-        if n == 0:
-            self.flush()
-            raise LookupError('no heat maps')
+        factors = None if factors is None else set(factors)         # a factors argument that is no iterable fails first, as ever
+        # the key mask in the library's key order: the one-prompt table, ``>= 0``
+        _, mask = self._select(1, factors, head_idx, layer_idx, mask=True)
         out = torch.empty(rows, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
         if self.rect:
             # no announcement on a non-square map (daam_finalize_prepare is DAAM_E_UNSUPPORTED there): the finalize clears its output
@@ -1042,15 +1029,9 @@ class HeatMapEngine:
         under classifier-free guidance: a layer's kept keys are ``[cond x N*k]`` batch items of H heads each, so prompt ``p``
         owns the block ``[p * kept/N, (p+1) * kept/N)``.  ``head_idx`` counts inside a prompt's block (the reference's
         ``head_idx`` on a single prompt), ``factors`` / ``layer_idx`` filter as in ``global_heat_map``."""
-        total = ctypes.c_int()
-        nat.check(self.lib.daam_key_offset(self.ctx, 0, None, ctypes.byref(total)))
-        layout = []
-        for layer in self.touched:
-            factor, heads, _ = self.layer_info[layer]
-            off = ctypes.c_int()
-            nat.check(self.lib.daam_key_offset(self.ctx, layer, ctypes.byref(off), None))
-            layout.append((layer, off.value, factor, heads))
-        return prompt_key_groups(layout, total.value, n_groups, factors, head_idx, layer_idx)
+        total, offs = self._key_layout(self.touched)
+        layout = [(layer, off, *self.layer_info[layer][:2]) for layer, off in zip(self.touched, offs)]
+        return prompt_key_groups(layout, total, n_groups, factors, head_idx, layer_idx)
 
     def global_heat_maps(self, n_groups: int, n_rows: Sequence[int], factors: Optional[Sequence[int]] = None,
                          head_idx: Optional[int] = None, layer_idx: Optional[int] = None,
@@ -1063,24 +1044,8 @@ class HeatMapEngine:
                 raise ValueError(f'{len(n_rows)} row counts for {n_groups} prompts')
             b0, b1 = bins if bins is not None else (0, self.n_bins)
             return self.time_heat_maps([(b0, b1, p) for p in range(n_groups)], n_groups, n_rows, factors, head_idx, layer_idx)
-        if self.ctx is None or not self.touched:
-            raise LookupError('no heat maps')
-        if len(n_rows) != n_groups:
-            raise ValueError(f'{len(n_rows)} row counts for {n_groups} prompts')
-        sel = ('groups', n_groups, None if factors is None else tuple(sorted(set(factors))), head_idx, layer_idx,
-               tuple(self.touched), len(self.layer_info))
-        cached = self._mask_cache.get(sel)
-        if cached is None:
-            groups = self.key_groups(n_groups, factors, head_idx, layer_idx)
-            counts = [groups.count(p) for p in range(n_groups)]
-            if len(self._mask_cache) > 64:
-                self._mask_cache.clear()
-            cached = self._mask_cache[sel] = ((ctypes.c_int32 * len(groups))(*groups), counts)
-        table, counts = cached
-        if min(counts) == 0:
-            self.flush()
-            raise LookupError('no heat maps')
-        rows = [max(1, min(int(r), self.tokens)) for r in n_rows]
+        _, table = self._select(n_groups, factors, head_idx, layer_idx, n_rows=n_rows)
+        rows = [self._rows(r) for r in n_rows]
         self.flush()
         out = torch.empty(n_groups, self.tokens, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
         nat.check(self.lib.daam_finalize_groups(self.ctx, table, n_groups, (ctypes.c_int32 * n_groups)(*rows), out.data_ptr(),
@@ -1093,35 +1058,17 @@ class HeatMapEngine:
         """Global heat maps of ``(first window, end window, prompt)`` groups (``daam_finalize_bins``, at most 64 groups per call):
         returns ``[len(groups), tokens, x, x]`` fp32 whose rows ``[0, n_rows[prompt])`` of each group are its map.  ``n_prompts``
         prompts share the key table (``key_groups``); the filters are per prompt."""
-        if self.ctx is None or not self.touched:
-            raise LookupError('no heat maps')
-        if len(n_rows) != n_prompts:
-            raise ValueError(f'{len(n_rows)} row counts for {n_prompts} prompts')
-        sel = ('bins', n_prompts, None if factors is None else tuple(sorted(set(factors))), head_idx, layer_idx,
-               tuple(self.touched), len(self.layer_info))
-        cached = self._mask_cache.get(sel)
-        if cached is None:
-            table = self.key_groups(n_prompts, factors, head_idx, layer_idx)
-            counts = [table.count(p) for p in range(n_prompts)]
-            if len(self._mask_cache) > 64:
-                self._mask_cache.clear()
-            cached = self._mask_cache[sel] = ((ctypes.c_int32 * len(table))(*table), counts)
-        table, counts = cached
-        if any(counts[p] == 0 for _, _, p in groups):
-            self.flush()
-            raise LookupError('no heat maps')
-        rows = [max(1, min(int(r), self.tokens)) for r in n_rows]
+        _, table = self._select(n_prompts, factors, head_idx, layer_idx, used=(p for _, _, p in groups), n_rows=n_rows)
+        rows = [self._rows(r) for r in n_rows]
         self.flush()
-        plane = self.tokens * self.out_h * self.out_w
-        out = torch.empty(len(groups), self.tokens, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
-        for start in range(0, len(groups), 64):                 # the library takes at most 64 groups per call
-            part = groups[start:start + 64]
-            n = len(part)
+
+        def call(start, n, out_ptr, plane):
+            part = groups[start:start + n]
             i32 = ctypes.c_int32 * n
-            nat.check(self.lib.daam_finalize_bins(self.ctx, table, n, i32(*[p for _, _, p in part]), i32(*[b for b, _, _ in part]),
-                                                  i32(*[e for _, e, _ in part]), i32(*[rows[p] for _, _, p in part]),
-                                                  out.data_ptr() + start * plane * 4, plane, self.stream))
-        return out
+            return self.lib.daam_finalize_bins(self.ctx, table, n, i32(*[p for _, _, p in part]), i32(*[b for b, _, _ in part]),
+                                               i32(*[e for _, e, _ in part]), i32(*[rows[p] for _, _, p in part]), out_ptr, plane,
+                                               self.stream)
+        return self._finalize_chunks(len(groups), call)
 
     def normalize_(self, maps: torch.Tensor) -> torch.Tensor:
         """trace.py:129-130, in place on ``maps`` [n_rows, x, x] -- or [n_rows, out_h, out_w] -- (contiguous fp32)."""

@@ -90,6 +90,13 @@ def _probe_embeddings(pipeline, probes, probe_embeds=None) -> torch.Tensor:
     return torch.cat(rows)
 
 
+def _no_maps(filtered: bool) -> RuntimeError:
+    """What the engine's ``LookupError('no heat maps')`` means to the caller (the reference's two texts, trace.py:119-124)."""
+    if filtered:
+        return RuntimeError('No heat maps found for the given parameters.')
+    return RuntimeError('No heat maps found. Did you forget to call `with trace(...)` during generation?')
+
+
 class DiffusionHeatMapHooker(AggregateHooker):
     def __init__(self, pipeline, low_memory: bool = False, load_heads: bool = False, save_heads: bool = False,
                  data_dir: Optional[str] = None, *, accumulate: str = 'exact', tap: str = 'qk',
@@ -220,6 +227,17 @@ class DiffusionHeatMapHooker(AggregateHooker):
         return GenerationExperiment(image, maps, self.last_prompts[prompt_idx], seed=seed, id=id, subtype=subtype, path=path,
                                     tokenizer=self.pipe.tokenizer)
 
+    # -- from the engine's maps to GlobalHeatMap -------------------------------------------------------
+    def _n_rows(self, text: str) -> int:
+        return len(self.pipe.tokenizer.tokenize(text)) + 2                 # 1 for SOS and 1 for padding (trace.py:127)
+
+    def _wrap(self, maps: torch.Tensor, rows: int, text: str, normalize: bool) -> GlobalHeatMap:
+        """``maps`` [>= rows, h, w] of the engine, cropped to the rows of ``text`` (a view), normalised in place on request."""
+        maps = maps[:rows]
+        if normalize:
+            maps = self.engine.normalize_(maps)
+        return GlobalHeatMap(self.pipe.tokenizer, text, maps)
+
     # -- time windows ------------------------------------------------------------------------------
     @property
     def n_time_bins(self) -> int:
@@ -296,21 +314,18 @@ class DiffusionHeatMapHooker(AggregateHooker):
         steps = self.time_bin_steps()
         windows = [w for w, k in enumerate(steps) if k > 0]
         if not windows:
-            raise RuntimeError('No heat maps found. Did you forget to call `with trace(...)` during generation?')
-        n_rows = [len(self.pipe.tokenizer.tokenize(p)) + 2 for p in prompts]
+            raise _no_maps(False)
+        n_rows = [self._n_rows(p) for p in prompts]
         which = [prompt_idx] if (batched and prompt_idx is not None) else list(range(len(prompts)))
         groups = [(w, w + 1, p) for w in windows for p in which]
         try:
             maps = self.engine.time_heat_maps(groups, len(prompts), n_rows, factors=factors, head_idx=head_idx,
                                               layer_idx=layer_idx)
         except LookupError:
-            raise RuntimeError('No heat maps found for the given parameters.') from None
+            raise _no_maps(True) from None
         out: list = [None] * len(steps)
         for gi, (w, _, p) in enumerate(groups):
-            m = maps[gi, :n_rows[p]]
-            if normalize:
-                m = self.engine.normalize_(m)
-            hm = GlobalHeatMap(self.pipe.tokenizer, prompts[p], m)
+            hm = self._wrap(maps[gi], n_rows[p], prompts[p], normalize)
             if batched and prompt_idx is None:
                 if out[w] is None:
                     out[w] = []
@@ -356,22 +371,13 @@ class DiffusionHeatMapHooker(AggregateHooker):
             prompts = self.last_prompts or [self.last_prompt]
         elif len(prompts) != max(1, len(self.last_prompts)):
             raise ValueError(f'{len(prompts)} prompts given for {len(self.last_prompts)} traced')
-        n_rows = [len(self.pipe.tokenizer.tokenize(p)) + 2 for p in prompts]
+        n_rows = [self._n_rows(p) for p in prompts]
         try:
             kw = {} if rng is None else dict(bins=rng)
             maps = self.engine.global_heat_maps(len(prompts), n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx, **kw)
         except LookupError:
-            if head_idx is not None or layer_idx is not None:
-                raise RuntimeError('No heat maps found for the given parameters.') from None
-            raise RuntimeError('No heat maps found. Did you forget to call `with trace(...)` during generation?') \
-                from None
-        out = []
-        for p, (prompt, rows) in enumerate(zip(prompts, n_rows)):
-            m = maps[p, :rows]
-            if normalize:
-                m = self.engine.normalize_(m)
-            out.append(GlobalHeatMap(self.pipe.tokenizer, prompt, m))
-        return out
+            raise _no_maps(head_idx is not None or layer_idx is not None) from None
+        return [self._wrap(maps[p], rows, prompt, normalize) for p, (prompt, rows) in enumerate(zip(prompts, n_rows))]
 
     def compute_global_heat_map(self, prompt=None, factors=None, head_idx=None, layer_idx=None, normalize=False,
                                 prompt_idx: Optional[int] = None, time_bin=None):
@@ -401,21 +407,15 @@ class DiffusionHeatMapHooker(AggregateHooker):
             return maps
         if prompt is None:
             prompt = self.last_prompt
-        n_rows = len(self.pipe.tokenizer.tokenize(prompt)) + 2                 # 1 for SOS and 1 for padding (trace.py:127)
+        n_rows = self._n_rows(prompt)
         self._check_bin_steps(rng)
         try:
             # the crop is handed to the finalize: rows nobody reads are not computed (daam_finalize n_rows, ABI v6)
             kw = {} if rng is None else dict(bins=rng)
             maps = self.engine.global_heat_map(factors=factors, head_idx=head_idx, layer_idx=layer_idx, n_rows=n_rows, **kw)
         except LookupError:
-            if head_idx is not None or layer_idx is not None:
-                raise RuntimeError('No heat maps found for the given parameters.') from None
-            raise RuntimeError('No heat maps found. Did you forget to call `with trace(...)` during generation?') \
-                from None
-        maps = maps[:n_rows]
-        if normalize:
-            maps = self.engine.normalize_(maps)
-        return GlobalHeatMap(self.pipe.tokenizer, prompt, maps)
+            raise _no_maps(head_idx is not None or layer_idx is not None) from None
+        return self._wrap(maps, n_rows, prompt, normalize)
 
     # -- probes (open-vocabulary heat maps) ----------------------------------------------------------
     def _check_probe(self, probe) -> int:
@@ -437,25 +437,13 @@ class DiffusionHeatMapHooker(AggregateHooker):
         if prompt_idx is not None:
             prompt_idx = self._check_prompt_idx(prompt_idx)
         texts = [self.probes[p] for p in probes]
-        n_rows = [len(self.pipe.tokenizer.tokenize(t)) + 2 for t in texts]
+        n_rows = [self._n_rows(t) for t in texts]
         try:
             maps = self.engine.probe_heat_maps(probes, n, n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx)
         except LookupError:
-            if head_idx is not None or layer_idx is not None:
-                raise RuntimeError('No heat maps found for the given parameters.') from None
-            raise RuntimeError('No heat maps found. Did you forget to call `with trace(...)` during generation?') from None
-        out = []
-        for i, (text, rows) in enumerate(zip(texts, n_rows)):
-            row = []
-            for j in range(n):
-                if prompt_idx is not None and j != prompt_idx:
-                    continue
-                m = maps[i * n + j, :rows]
-                if normalize:
-                    m = self.engine.normalize_(m)
-                row.append(GlobalHeatMap(self.pipe.tokenizer, text, m))
-            out.append(row)
-        return out
+            raise _no_maps(head_idx is not None or layer_idx is not None) from None
+        which = range(n) if prompt_idx is None else [prompt_idx]
+        return [[self._wrap(maps[i * n + j], rows, text, normalize) for j in which] for i, (text, rows) in enumerate(zip(texts, n_rows))]
 
     def compute_probe_heat_map(self, probe: int, factors=None, head_idx=None, layer_idx=None, normalize=False,
                                prompt_idx: Optional[int] = None) -> GlobalHeatMap:

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from _fake_native import fake_engine  # noqa: F401 -- the recording stand-in of libdaam_hip (fixture)
 from conftest import ROOT, golden_pipe, load_golden
 from oracle import fake_diffusers as fd
 from oracle import heatmap_oracle as ho
@@ -165,51 +166,6 @@ def test_trace_installs_and_restores_processors():
 # ------------------------------------------------------------------------------------------------
 # engine bookkeeping against a recording fake of libdaam_hip (test-only)
 # ------------------------------------------------------------------------------------------------
-class _FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith('daam_'):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            if name == 'daam_ctx_create':
-                args[-1]._obj.value = 1234
-            if name == 'daam_key_offset':
-                return 0
-            return 0
-        return fn
-
-    def names(self):
-        return [c[0] for c in self.calls]
-
-
-@pytest.fixture
-def fake_engine(monkeypatch):
-    from daam_amd import engine as E
-    lib = _FakeLib()
-    monkeypatch.setattr(E.nat, 'load', lambda: lib)
-    monkeypatch.setattr(E.HeatMapEngine, '_require_device',
-                        lambda self, t: setattr(self, 'device', torch.device('cpu')))
-    class _Stream:
-        cuda_stream = 0
-
-        def wait_stream(self, other):
-            pass
-
-        def wait_event(self, ev):
-            pass
-
-        def record_event(self):
-            return object()
-    one = _Stream()
-    monkeypatch.setattr(E.HeatMapEngine, '_current_stream', lambda self: one)
-    monkeypatch.setattr(torch.cuda, 'device', lambda d: __import__('contextlib').nullcontext())
-    return E, lib
-
-
 @pytest.mark.parametrize('recorder', ['c++', 'python'])
 def test_engine_deferred_bookkeeping(fake_engine, monkeypatch, recorder):
     E, lib = fake_engine

@@ -1,11 +1,12 @@
 """Host-side pieces of probe tracing (open-vocabulary heat maps): argument checks, the probe encoding, the probe rows, the probe
 key-group table, and the deferred launch's extra chains, on a recording stand-in of the library."""
-import ctypes
 import types
 
 import numpy as np
 import pytest
 import torch
+
+from _fake_native import fake_engine  # noqa: F401 -- the recording stand-in of libdaam_hip (fixture)
 
 
 def _pipe():
@@ -130,67 +131,11 @@ def test_probe_key_group_table():
     assert probe_key_groups(layout, total, 2, 1, factors=[1]) == [-1] * 12 + [0] * 4 + [-1] * 2 + [1] * 4 + [-1] * 2
 
 
-class _RecLib:
-    """A stand-in of libdaam_hip that records every call and copies the deferred launch's arrays while they are alive."""
-
-    def __init__(self):
-        self.calls, self.enqueued = [], []
-
-    def __getattr__(self, name):
-        if not name.startswith('daam_'):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            if name == 'daam_ctx_create':
-                args[-1]._obj.value = 1234
-            if name == 'daam_tap_qk_enqueue_many':
-                n = args[1]
-
-                def arr(t, a):
-                    return list((t * n).from_address(a if isinstance(a, int) else ctypes.addressof(a)))
-                layers, q, k, d = arr(ctypes.c_int32, args[2]), arr(ctypes.c_uint64, args[3]), arr(ctypes.c_uint64, args[4]), \
-                    arr(ctypes.c_uint64, args[5])
-                from daam_amd import _native as nat
-                self.enqueued.append([(l, qq, kk, bytes(nat.QKDesc.from_address(dd))) for l, qq, kk, dd in zip(layers, q, k, d)])
-            return 0
-        return fn
-
-    def names(self):
-        return [c[0] for c in self.calls]
-
-
-@pytest.fixture
-def rec_engine(monkeypatch):
-    from daam_amd import engine as E
-    lib = _RecLib()
-    monkeypatch.setattr(E.nat, 'load', lambda: lib)
-    monkeypatch.setattr(E.HeatMapEngine, '_require_device', lambda self, t: setattr(self, 'device', torch.device('cpu')))
-
-    class _Stream:
-        cuda_stream = 0
-
-        def wait_stream(self, other):
-            pass
-
-        def wait_event(self, ev):
-            pass
-
-        def record_event(self):
-            return object()
-    one = _Stream()
-    monkeypatch.setattr(E.HeatMapEngine, '_current_stream', lambda self: one)
-    monkeypatch.setattr(torch.cuda, 'device', lambda d: __import__('contextlib').nullcontext())
-    E._PARKED.clear()
-    yield E, lib
-    E._PARKED.clear()
-
-
 @pytest.mark.parametrize('recorder', ['c++', 'python'])
 @pytest.mark.parametrize('n_probes', [1, 3])
-def test_deferred_launch_adds_probe_chains(rec_engine, monkeypatch, recorder, n_probes):
+def test_deferred_launch_adds_probe_chains(fake_engine, monkeypatch, recorder, n_probes):
     from daam_amd import _native as nat
-    E, lib = rec_engine
+    E, lib = fake_engine
     if recorder == 'python':
         monkeypatch.setenv('DAAM_NO_FASTPATH', '1')
     q = [torch.zeros(2, 64, 16, dtype=torch.float16) for _ in range(3)]
@@ -228,8 +173,8 @@ def test_deferred_launch_adds_probe_chains(rec_engine, monkeypatch, recorder, n_
     eng.close()
 
 
-def test_no_probes_launch_is_unchanged(rec_engine):
-    E, lib = rec_engine
+def test_no_probes_launch_is_unchanged(fake_engine):
+    E, lib = fake_engine
     q, k = torch.zeros(2, 64, 16, dtype=torch.float16), torch.zeros(2, 77, 16, dtype=torch.float16)
     eng = E.HeatMapEngine(2, defer_steps=8)
     for _ in range(2):
@@ -241,8 +186,8 @@ def test_no_probes_launch_is_unchanged(rec_engine):
     eng.close()
 
 
-def test_probe_keys_must_match(rec_engine):
-    E, lib = rec_engine
+def test_probe_keys_must_match(fake_engine):
+    E, lib = fake_engine
     eng = E.HeatMapEngine(2, defer_steps=8, n_probes=2)
     with pytest.raises(ValueError):
         eng.set_probe_keys(0, torch.zeros(3, 77, 16))

@@ -9,6 +9,8 @@ import types
 import pytest
 import torch
 
+from _fake_native import fake_engine  # noqa: F401 -- the recording stand-in of libdaam_hip (fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -103,56 +105,6 @@ def test_load_rejects_library_without_new_symbol(tmp_path):
     env = dict(os.environ, DAAM_HIP_LIB=str(lib), PYTHONPATH=ROOT)
     out = subprocess.run(['python', '-c', code], capture_output=True, text=True, env=env, cwd=ROOT).stdout
     assert 'ERR' in out and 'rebuild' in out and 'daam_finalize_bins' in out, out
-
-
-class _FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith('daam_'):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            if name == 'daam_ctx_create':
-                args[-1]._obj.value = 1234
-            if name == 'daam_key_offset':                      # two heads per layer, four keys in all
-                if args[2] is not None:
-                    args[2]._obj.value = 2 * args[1]
-                if args[3] is not None:
-                    args[3]._obj.value = 4
-            return 0
-        return fn
-
-    def names(self):
-        return [c[0] for c in self.calls]
-
-
-@pytest.fixture
-def fake_engine(monkeypatch):
-    from daam_amd import engine as E
-    lib = _FakeLib()
-    monkeypatch.setattr(E.nat, 'load', lambda: lib)
-    monkeypatch.setattr(E.HeatMapEngine, '_require_device', lambda self, t: setattr(self, 'device', torch.device('cpu')))
-
-    class _Stream:
-        cuda_stream = 0
-
-        def wait_stream(self, other):
-            pass
-
-        def wait_event(self, ev):
-            pass
-
-        def record_event(self):
-            return object()
-    one = _Stream()
-    monkeypatch.setattr(E.HeatMapEngine, '_current_stream', lambda self: one)
-    monkeypatch.setattr(torch.cuda, 'device', lambda d: __import__('contextlib').nullcontext())
-    E._PARKED.clear()
-    yield E, lib
-    E._PARKED.clear()
 
 
 @pytest.mark.parametrize('recorder', ['c++', 'python'])
