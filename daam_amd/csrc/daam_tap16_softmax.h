@@ -155,13 +155,17 @@ __device__ __forceinline__ void softmax20_accumulate_bf16(const floatx4 (&c)[5],
 // daam_attend (daam_attend_d64.hip), whose fused sums are therefore bit-identical to the stand-alone tap's.
 //   logits stay packed fp16 (their reference precision); e = 2^(x L) by ONE mixed-precision FMA + v_exp_f32 per element.
 //   When scale is a power of two (head_dim 64: 1/8) the multiply commutes with the fp16 rounding (fp16(c) * 2^k == fp16(c * 2^k)
-//   unless the result is an fp16 subnormal, |logit| < 6.1e-5, where the two differ by < 6e-8 absolute): the logits stay unscaled
-//   in fp16 and the scale is folded into L.
+//   unless the result is an fp16 subnormal, |logit| < 6.1e-5, where the two differ by < 6e-8 absolute, or the UNSCALED q.k is
+//   beyond the fp16 range: for 65504 < |c| <= 65504 / scale, fp16(c) is +-inf while fp16(c * scale) is finite -- the redo below then
+//   takes max = inf and fma(inf, L, -inf) makes the pixel's 77 probabilities NaN): the logits stay unscaled in fp16 and the scale
+//   is folded into L.  DOMAIN of this flavour with a power-of-two scale: |q.k| <= 65504 (include/daam_hip.h, DESIGN section 4;
+//   DAAM_STRICT_EXP=1 lifts it).
 //   Reference point (round 4): NONE.  Softmax is shift-invariant, and cross-attention logits are small numbers (|x| <= ~40 for
 //   real prompts: 2^(40 log2 e) = 2^58 against an f32 range of 2^+-126), so the exponentials are taken of the logits themselves
 //   and the row is only redone with its true maximum -- as the reference does (18 v_pk_max_f16 + a lane reduction) -- when the
 //   sum of a pixel leaves [2^-100, 2^100] (then 1 / sum would leave the normal range; past 2^127 the exponentials overflow, below
-//   2^-126 they vanish): tests/test_gpu_parity.py::test_tap_wide_logit_spread drives both directions.  Rounds 1-3 subtracted token
+//   2^-126 they vanish): tests/test_gpu_parity.py::test_tap_wide_logit_spread and, per row class on every route,
+//   tests/test_gpu_softmax_domain.py drive both directions.  Rounds 1-3 subtracted token
 //   0's logit (the start-of-text token): one f32 conversion, a five-instruction lane broadcast and a multiply per 16 pixels that buy
 //   nothing.  The relative error of e is that of the one f32 rounding of x L (|x L| <= 64: <= 2.6e-6, typically 4e-7) -- the
 //   same class as before and as the f32 summation order of q.k.

@@ -151,7 +151,19 @@ DAAM_API int daam_reset(DaamCtx* ctx, void* stream);
  * sum once per flush instead of once per step.
  * daam_tap_probs: same accumulate from materialised probabilities [B*H, hw, tokens]
  * (the save_heads / load_heads path, trace.py:279-282, and any processor that already
- * holds attention_probs); bit-exact with the reference in the add. */
+ * holds attention_probs); bit-exact with the reference in the add.
+ *
+ * Logit domain (daam_tap_qk*, daam_attend; tests/test_gpu_softmax_domain.py).  The softmax is the reference's at any logit
+ * magnitude the pipeline dtype holds: a pixel whose sum of exponentials leaves [2^-100, 2^100] is redone with its row maximum.
+ * One exception, stated by its condition: a call with in_dtype = DAAM_F16, round_logits = 1 and a `scale` that is a positive
+ * power of two (head_dim 64: 1/8, head_dim 16: 1/4 -- or any head_dim when the caller passes such a scale; it is a descriptor
+ * field) on a context with the fast softmax (the default) keeps the UNSCALED q.k in fp16 and folds the scale into the exponent.
+ * This holds for every kernel built on the 16x16 tile (tap_d64 / tap_wide / tap_walk / tap_pair / tap_chunk / tap_slab and the fp16
+ * daam_attend).  Such a call requires |q.k| <= 65504 (|logit| <= 65504 * scale: 8188 at 1/8).  Beyond it the fp16 q.k is +-inf
+ * and the pixel's 77 probabilities (and the pixel's daam_attend output row) are NaN where the reference, which rounds
+ * q.k * scale, is finite; nothing checks this.  Outside the condition the limit does not exist: DAAM_STRICT_EXP=1 (read when the
+ * context is created), a scale that is no power of two (head_dim 40 / 80 / 160 with head_dim^-1/2), round_logits = 0, bf16 and
+ * f32 pipelines, and tap_mfma_kernel (DAAM_NO_D64=1) all scale before they round. */
 DAAM_API int daam_tap_qk(DaamCtx* ctx, int layer, const void* q, const void* k, const DaamQKDesc* d, void* stream);
 DAAM_API int daam_tap_qk_enqueue(DaamCtx* ctx, int layer, const void* q, const void* k, const DaamQKDesc* d);
 /* the same as n daam_tap_qk_enqueue calls in order (all or nothing): lets a host runtime that

@@ -164,9 +164,9 @@ def _configure(monkeypatch, env):
         monkeypatch.setenv(var, val)
 
 
-def _qk_desc(nat, dtype, heads, hw, d, q, k):
+def _qk_desc(nat, dtype, heads, hw, d, q, k, round_logits=1):
     code = {torch.float16: 0, torch.float32: 1, torch.bfloat16: 2}[dtype]
-    return nat.QKDesc(in_dtype=code, batch=BATCH, heads=heads, hw=hw, tokens=77, head_dim=d, round_logits=1, scale=float(d ** -0.5),
+    return nat.QKDesc(in_dtype=code, batch=BATCH, heads=heads, hw=hw, tokens=77, head_dim=d, round_logits=round_logits, scale=float(d ** -0.5),
                       q_stride_b=q.strides[0], q_stride_h=q.strides[1], q_stride_p=q.strides[2],
                       k_stride_b=k.strides[0], k_stride_h=k.strides[1], k_stride_t=k.strides[2])
 
@@ -186,7 +186,7 @@ def _last_launch(nat, eng):
     return eng.last_kernels(0), block.value
 
 
-def _tap_raw(steps, heads, d, hw, dtype, accumulate, layout, deferred, bins=None):
+def _tap_raw(steps, heads, d, hw, dtype, accumulate, layout, deferred, bins=None, round_logits=1):
     """Tap ``steps`` = [(q, k)] (logical device tensors) through the C ABI with Q / K laid out in ``layout``.  Returns the sums
     (a binned context: [windows, heads, 77, side, side]), the kernel name and block size of the last launch, and whether every
     input storage is bit-unchanged."""
@@ -194,7 +194,7 @@ def _tap_raw(steps, heads, d, hw, dtype, accumulate, layout, deferred, bins=None
     eng = _raw_engine(dtype, accumulate, heads, hw, bins)
     placed = [(_Placed(q, _layout_of(layout, 'q'), 'q', heads, float('nan')), _Placed(k, _layout_of(layout, 'k'), 'k', heads, float('nan')))
               for q, k in steps]
-    desc = _qk_desc(nat, dtype, heads, hw, d, *placed[0])
+    desc = _qk_desc(nat, dtype, heads, hw, d, *placed[0], round_logits=round_logits)
     for q, k in placed:
         if deferred:
             nat.check(eng.lib.daam_tap_qk_enqueue(eng.ctx, 0, q.ptr, k.ptr, ctypes.byref(desc)))
