@@ -276,6 +276,9 @@ class HeatMapEngine:
         self._check_versions = bool(os.environ.get('DAAM_CHECK_VERSIONS'))
         self._rec_stream: Optional[torch.cuda.Stream] = None   # stream the generation's Q / K are produced on
         self._views_out = False                           # all_heat_maps handed out views of the live sum buffers
+        # slots whose buffers were kept across a reset: may hold an earlier generation's sums.  Read by window_items only; probe
+        # slots land here too and are never looked at (probes and time_bins exclude each other)
+        self._stale: set = set()
         self._held = 0                                    # bytes of recorded Q / K (Python recorder)
         self.ctx: Optional[nat.c_void_p] = None
         self.device: Optional[torch.device] = None
@@ -350,6 +353,7 @@ class HeatMapEngine:
             # whatever the previous owner queued (on its stream) comes first
             self._current_stream().wait_event(st['event'])
             nat.check(self.lib.daam_reset(self.ctx, self.stream))      # sums start from zero (lazily, like clear())
+            self._stale = set(self.acc)
             self._sync_native()
             return
         ctx = nat.c_void_p()
@@ -400,6 +404,7 @@ class HeatMapEngine:
         """No layer is configured any more: the sum buffers go (to whoever still holds them), and with them everything that was
         derived per layer -- the validated call shapes of both recorders and the finalize key tables."""
         self.acc, self.layer_info = {}, {}
+        self._stale.clear()
         self._qk_cache = [None] * self.n_layers
         self._att_cache = [None] * self.n_layers
         self._mask_cache.clear()
@@ -448,6 +453,7 @@ class HeatMapEngine:
             else:
                 nat.check(self.lib.daam_layer_configure(self.ctx, slot, heads, side, factor, buf.data_ptr()))
             self.acc[slot] = buf
+            self._stale.discard(slot)
             self.layer_info[slot] = (factor, heads, side)
         self._mask_cache.clear()
 
@@ -473,6 +479,7 @@ class HeatMapEngine:
             self._fast.reset_touched()
         if self.ctx is not None:
             nat.check(self.lib.daam_reset(self.ctx, self.stream))
+            self._stale = set(self.acc)                    # kept buffers (unless the views take them, below): zeroed lazily
         if self._views_out:
             # the reference's clear() drops its dict and the tensors it handed out live on unchanged
             # (heatmap.py:170-172): leave the old buffers to those views and start the next generation on new ones.
@@ -896,8 +903,28 @@ class HeatMapEngine:
 
     def window_items(self, window: int) -> Dict[Key, torch.Tensor]:
         """``{(factor, layer, head): running sum of window ``window`` [tokens, h, w]}`` -- views of the live buffers, with the
-        lifetime rules of ``items``."""
+        lifetime rules of ``items``.  A window the layer has not reached in this generation reads zero (``_zero_unreached_windows``)."""
+        self._zero_unreached_windows()
         return dict(self._views(lambda layer: self.acc[layer][window]))
+
+    def _zero_unreached_windows(self) -> None:
+        """``clear()`` and the adoption of a parked context keep the sum buffers and ``daam_reset`` zeroes lazily: a slot is overwritten
+        by its first tap, or cleared by the first finalize that covers it.  A window that a touched layer has not reached in this
+        generation (a shorter generation, a layer tapped fewer times) gets neither before its view is handed out, and would show the
+        previous generation's sums.  The engine knows which windows those are -- a layer tapped ``n`` times has reached the windows that
+        start before step ``n`` -- and zeroes them here, once per layer and reset, on the current stream behind the launch of
+        whatever was recorded.  The library still owes them its own zeroing; a later tap into one overwrites it (the slot is fresh)."""
+        if self.time_bins is None:                         # no windows: items() hands out touched layers, which their first tap overwrote
+            return
+        layers = [layer for layer in self.touched if layer in self._stale]
+        if not layers:
+            return
+        steps = self.tap_steps()                           # launches what is recorded first
+        for layer in layers:
+            reached = sum(1 for first in self.time_bins if first < steps[layer])
+            if reached < self.n_bins:
+                self.acc[layer][reached:].zero_()
+            self._stale.discard(layer)
 
     def tap_steps(self) -> Dict[int, int]:
         """Taps each touched layer received since the last reset (``daam_tap_steps``; pending deferred taps are launched first)."""

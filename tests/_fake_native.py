@@ -12,17 +12,20 @@ class FakeLib:
     """Records ``(name, args)`` of every ``daam_*`` call and returns 0.  It hands out contexts (``daam_ctx_create`` /
     ``daam_ctx_create_rect``), copies the arrays of ``daam_tap_qk_enqueue_many`` while they are alive (``enqueued``: one list of
     ``(layer, q, k, bytes of the DaamQKDesc)`` per call) and answers ``daam_key_offset`` as the C function does, from the slots
-    that ``daam_layer_configure`` / ``_rect`` / ``daam_layer_release`` left configured."""
+    that ``daam_layer_configure`` / ``_rect`` / ``daam_layer_release`` left configured, and ``daam_tap_steps`` from the taps it was
+    handed since the last ``daam_reset`` (recorded ones count when they are enqueued, as in the library)."""
 
     def __init__(self):
         self.calls, self.enqueued = [], []
         self.contexts = []                                 # handle values, in creation order
         self.heads = {}                                    # handle -> {configured slot: heads}
+        self.steps = {}                                    # handle -> {layer: taps since daam_reset}
 
     def _create(self, out):
         handle = 1234 + len(self.contexts)
         self.contexts.append(handle)
         self.heads[handle] = {}
+        self.steps[handle] = {}
         out._obj.value = handle
 
     def _key_offset(self, ctx, layer, offset, total):
@@ -32,12 +35,18 @@ class FakeLib:
         if total is not None:
             total._obj.value = sum(heads.values())
 
-    def _enqueue_many(self, n, layers, q, k, desc):
+    def _count(self, ctx, layer):
+        steps = self.steps[ctx.value]
+        steps[layer] = steps.get(layer, 0) + 1
+
+    def _enqueue_many(self, ctx, n, layers, q, k, desc):
         from daam_amd import _native as nat
 
         def arr(t, a):
             return list((t * n).from_address(a if isinstance(a, int) else ctypes.addressof(a)))
         u64 = ctypes.c_uint64
+        for layer in arr(ctypes.c_int32, layers):
+            self._count(ctx, layer)
         self.enqueued.append([(l, qq, kk, bytes(nat.QKDesc.from_address(dd)))
                               for l, qq, kk, dd in zip(arr(ctypes.c_int32, layers), arr(u64, q), arr(u64, k), arr(u64, desc))])
 
@@ -56,7 +65,15 @@ class FakeLib:
             elif name == 'daam_key_offset':
                 self._key_offset(*args)
             elif name == 'daam_tap_qk_enqueue_many':
-                self._enqueue_many(*args[1:])
+                self._enqueue_many(*args)
+            # include/daam_hip.h: daam_tap_qk(ctx, layer, ...), daam_tap_probs(ctx, layer, ...),
+            # daam_attend(ctx, layer, q, k, v, out, desc, tap, stream): args[7] is ``tap`` (the call feeds the sums)
+            elif name in ('daam_tap_qk', 'daam_tap_probs') or (name == 'daam_attend' and args[7]):
+                self._count(args[0], args[1])
+            elif name == 'daam_reset':
+                self.steps[args[0].value] = {}
+            elif name == 'daam_tap_steps':                 # daam_tap_steps(ctx, layer, int* steps)
+                args[2]._obj.value = self.steps[args[0].value].get(args[1], 0)
             return 0
         return fn
 

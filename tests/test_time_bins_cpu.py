@@ -175,3 +175,54 @@ def test_binned_finalize_routes_through_finalize_bins(fake_engine):
     calls = [c for c in lib.calls if c[0] == 'daam_finalize_bins']
     assert [c[1][2] for c in calls[-2:]] == [64, 26]
     eng.close()
+
+
+@pytest.mark.parametrize('how', ['clear', 'adopted'])
+def test_windows_a_shorter_generation_does_not_reach_read_zero(fake_engine, how):
+    """The buffers are kept across ``clear()`` (no views out) and across the adoption of a parked context, and ``daam_reset``
+    zeroes nothing: the windows the next generation does not reach hold the previous one's sums until ``window_items`` zeroes
+    them -- those windows only, for the touched layers only, once per reset, and never in a first generation."""
+    E, lib = fake_engine
+    q, k = torch.zeros(2, 64, 16, dtype=torch.float16), torch.zeros(2, 77, 16, dtype=torch.float16)
+
+    def make():
+        return E.HeatMapEngine(3, defer_steps=8, reuse_context=True, time_bins=[0, 2, 4])
+
+    def taps(eng, counts):
+        for s in range(max(counts)):
+            for layer, n in enumerate(counts):
+                if s < n:
+                    eng.tap_qk(layer, q, k, 2, 0.35, 1)
+    eng = make()
+    taps(eng, (5, 5, 5))
+    eng.flush()
+    for buf in eng.acc.values():
+        buf.fill_(7.0)                                          # what generation 1 left (the stand-in computes nothing)
+    bufs = dict(eng.acc)
+    if how == 'clear':
+        eng.clear()
+    else:
+        eng.close()
+        eng = make()
+    taps(eng, (3, 1, 0))                                        # layer 0 reaches windows 0 and 1, layer 1 window 0, layer 2 none
+    before = len(lib.calls)
+    views = eng.window_items(2)
+    assert all(eng.acc[layer] is bufs[layer] for layer in range(3))
+    assert [c[0] for c in lib.calls[before:]].count('daam_tap_steps') == 2          # the two touched layers
+    assert sorted(key[1] for key in views) == [0, 0, 1, 1]
+    assert [bool((eng.acc[0][w] == 7.0).all()) for w in range(3)] == [True, True, False] and not bool(eng.acc[0][2].any())
+    assert [bool((eng.acc[1][w] == 7.0).all()) for w in range(3)] == [True, False, False] and not bool(eng.acc[1][1:].any())
+    assert bool((eng.acc[2] == 7.0).all())                       # not touched: not handed out, left to the library's finalize
+    assert all(not bool(v.any()) for v in views.values())
+    eng.acc[0][2].fill_(3.0)                                    # once per reset: what arrives later in the generation stays
+    before = len(lib.calls)
+    eng.window_items(2)
+    assert 'daam_tap_steps' not in [c[0] for c in lib.calls[before:]] and bool((eng.acc[0][2] == 3.0).all())
+    eng.close()
+    E._PARKED.clear()
+    first = E.HeatMapEngine(1, defer_steps=8, time_bins=[0, 2, 4])                   # a first generation: nothing to zero, nothing asked
+    first.tap_qk(0, q, k, 2, 0.35, 1)
+    before = len(lib.calls)
+    first.window_items(1)
+    assert 'daam_tap_steps' not in [c[0] for c in lib.calls[before:]]
+    first.close()
