@@ -1164,6 +1164,44 @@ def expand_word_map(word: torch.Tensor, out_h: int, out_w: int, absolute: bool =
     return out
 
 
+MAX_MASK_WORDS, MAX_MASK_INDICES = 32, 255        # limits of one daam_word_masks call (include/daam_hip.h)
+
+
+def word_masks(maps: torch.Tensor, idx_lists: Sequence[Sequence[int]], out_h: int, out_w: int, absolute: bool = False,
+               threshold: float = 0.4, labels: bool = True):
+    """``daam_word_masks``: for up to 32 words (``idx_lists[j]`` = the planes of ``maps`` [rows, h, w] word ``j`` is the mean of) the
+    mean planes ``word_maps`` [n, h, w] fp32, the masks ``expand_as(threshold=) > threshold`` as uint8 [n, out_h, out_w] and, with
+    ``labels``, the uint8 [out_h, out_w] map of the word with the largest value at each pixel (lowest index on a tie, 255 where no
+    word exceeds the threshold) -- three launches, all results on the device.  Returns ``(word_maps, masks, labels or None)``."""
+    _check_maps(maps)
+    idx_lists = [[int(i) for i in idxs] for idxs in idx_lists]
+    n = len(idx_lists)
+    if not 1 <= n <= MAX_MASK_WORDS:
+        raise ValueError(f'word_masks takes 1..{MAX_MASK_WORDS} words per call, got {n}')
+    flat, begin = [], [0]
+    for idxs in idx_lists:
+        if not idxs:
+            raise ValueError('word_masks: a word with no token indices')
+        for i in idxs:
+            if not 0 <= i < maps.shape[0]:
+                raise IndexError(f'index {i} is out of bounds for dimension 0 with size {maps.shape[0]}')
+        flat += idxs
+        begin.append(len(flat))
+    if len(flat) > MAX_MASK_INDICES:
+        raise ValueError(f'word_masks takes at most {MAX_MASK_INDICES} token indices per call, got {len(flat)}')
+    rows, h, w = maps.shape
+    out_h, out_w = int(out_h), int(out_w)
+    word_maps = torch.empty(n, h, w, dtype=torch.float32, device=maps.device)
+    masks = torch.empty(n, out_h, out_w, dtype=torch.uint8, device=maps.device)
+    label_map = torch.empty(out_h, out_w, dtype=torch.uint8, device=maps.device) if labels else None
+    ws = torch.empty(2 * n, dtype=torch.float32, device=maps.device)
+    nat.check(nat.load().daam_word_masks(
+        maps.data_ptr(), rows, h, w, (ctypes.c_int32 * len(flat))(*flat), (ctypes.c_int32 * len(begin))(*begin), n, word_maps.data_ptr(),
+        out_h, out_w, 1 if absolute else 0, float(threshold), masks.data_ptr(), label_map.data_ptr() if labels else None, ws.data_ptr(),
+        torch.cuda.current_stream(maps.device).cuda_stream))
+    return word_maps, masks, label_map
+
+
 def _check_maps(maps: torch.Tensor) -> None:
     if maps.device.type != 'cuda':
         raise RuntimeError('daam_amd: heat maps must live on the HIP device (no CPU fallback)')

@@ -5,14 +5,14 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from functools import lru_cache
-from typing import Any, Iterable, Iterator, Optional, Set, Tuple
+from typing import Any, ClassVar, Iterable, Iterator, List, Optional, Sequence, Set, Tuple, Union
 
 import torch
 
 from . import engine as _engine
 from .utils import cached_nlp, compute_token_merge_indices
 
-__all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair']
+__all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair', 'Segmentation']
 
 RawHeatMapKey = Tuple[int, int, int]  # factor, layer, head
 
@@ -104,6 +104,28 @@ class ParsedHeatMap:
     token: Any
 
 
+@dataclass
+class Segmentation:
+    """Masks of several words of one prompt at image resolution and the map of which word owns each pixel
+    (``GlobalHeatMap.segment``).  Everything lives on the device until ``cpu()`` is asked for."""
+    BACKGROUND: ClassVar[int] = 255             # label of a pixel where no word exceeds the threshold
+
+    words: List[str]
+    word_heat_maps: List[WordHeatMap]
+    masks: torch.Tensor                         # uint8 [len(words), height, width]: 1 where the word's expanded map > threshold
+    labels: Optional[torch.Tensor]              # uint8 [height, width]: index into ``words`` or BACKGROUND; None if not computed
+
+    def mask(self, word: str) -> torch.Tensor:
+        """The uint8 [height, width] mask of ``word`` (its first entry, when the word was asked for twice)."""
+        if word not in self.words:
+            raise KeyError(word)
+        return self.masks[self.words.index(word)]
+
+    def cpu(self) -> 'Segmentation':
+        maps = [WordHeatMap(m.heatmap.cpu(), m.word, m.word_idx) for m in self.word_heat_maps]
+        return Segmentation(list(self.words), maps, self.masks.cpu(), None if self.labels is None else self.labels.cpu())
+
+
 class GlobalHeatMap:
     """reference heatmap.py:114-142."""
 
@@ -116,6 +138,39 @@ class GlobalHeatMap:
     def compute_word_heat_map(self, word: str, word_idx: Optional[int] = None, offset_idx: int = 0) -> WordHeatMap:
         merge_idxs, word_idx = compute_token_merge_indices(self.tokenizer, self.prompt, word, word_idx, offset_idx)
         return WordHeatMap(_engine.word_heat_map(self.heat_maps, merge_idxs), word, word_idx)
+
+    def segment(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]], image, threshold: float = 0.4, absolute: bool = False,
+                labels: bool = True) -> Segmentation:
+        """``compute_word_heat_map(w).expand_as(image, threshold=) > threshold`` for every ``w`` of ``words`` (strings, or
+        ``(word, word_idx)`` pairs) and the label map over them, in three launches per 32 words (``engine.word_masks``) with the
+        results left on the device.  The output size follows ``WordHeatMap.expand_as``.  A label map orders at most 32 words:
+        more are a ``ValueError`` unless ``labels=False``, which serves the masks in chunks."""
+        pairs = [(w, None) if isinstance(w, str) else (w[0], w[1]) for w in words]
+        if not pairs:
+            raise ValueError('segment needs at least one word')
+        if labels and len(pairs) > _engine.MAX_MASK_WORDS:
+            raise ValueError(f'a label map orders at most {_engine.MAX_MASK_WORDS} words, got {len(pairs)}; pass labels=False for masks only')
+        resolved = [compute_token_merge_indices(self.tokenizer, self.prompt, w, i) for w, i in pairs]
+        maps = self.heat_maps
+        size = (image.size[0], image.size[1]) if maps.shape[-2] == maps.shape[-1] else (image.size[1], image.size[0])
+        chunks, count = [[]], 0
+        for idxs, _ in resolved:                 # a call takes 32 words and 255 indices
+            if len(chunks[-1]) == _engine.MAX_MASK_WORDS or count + len(idxs) > _engine.MAX_MASK_INDICES:
+                chunks.append([])
+                count = 0
+            chunks[-1].append(idxs)
+            count += len(idxs)
+        if labels and len(chunks) > 1:
+            raise ValueError(f'a label map takes at most {_engine.MAX_MASK_INDICES} token indices over all words; pass labels=False')
+        word_maps, masks, label_map = [], [], None
+        for chunk in chunks:
+            wm, mk, label_map = _engine.word_masks(maps, chunk, int(size[0]), int(size[1]), absolute=absolute, threshold=threshold,
+                                                   labels=labels)
+            word_maps.append(wm)
+            masks.append(mk)
+        planes = [plane for wm in word_maps for plane in wm]
+        heat = [WordHeatMap(plane, w, r[1]) for plane, (w, _), r in zip(planes, pairs, resolved)]
+        return Segmentation([w for w, _ in pairs], heat, masks[0] if len(masks) == 1 else torch.cat(masks), label_map)
 
     def parsed_heat_maps(self) -> Iterable[ParsedHeatMap]:
         """One ``ParsedHeatMap`` per token of the parsed prompt whose text is found among the prompt's tokenizer tokens

@@ -279,6 +279,20 @@ DAAM_API int daam_word_heat_map_rect(const float* maps, int h, int w, const int3
                        float* out, int out_h, int out_w, int absolute, float threshold,
                        float* workspace, void* stream);
 
+/* Masks and a label map for many words in three launches (same ABI version: additive).  `idx` / `idx_begin[n_words + 1]` are HOST
+ * arrays: word j owns the planes idx[idx_begin[j] .. idx_begin[j + 1]) of maps[rows, h, w] (h, w <= 128); idx_begin[0] == 0,
+ * 1 <= n_words <= 32, every word non-empty, at most 255 indices in total, every index in [0, rows), words may share planes;
+ * out_h, out_w >= 1, `threshold` finite -- anything else is DAAM_E_INVALID before any launch.
+ *   word_maps [n_words, h, w] fp32 (required): word_maps[j] is bit for bit the word_map of daam_word_heat_map[_rect] on word j.
+ *   v_j(p) = what daam_word_heat_map[_rect] writes to `out` for word j with the same `absolute` and threshold 0.
+ *   masks  [n_words, out_h, out_w] uint8 or NULL: masks[j][p] = v_j(p) > threshold.
+ *   labels [out_h, out_w] uint8 or NULL: the smallest j with v_j(p) = max_j v_j(p) when that maximum is > threshold, else 255.
+ * `workspace` >= 2 * n_words floats of device scratch (the min / max pairs, started anew by every call).  Planes are assumed
+ * finite.  No fp32 plane of out_h x out_w is written anywhere. */
+DAAM_API int daam_word_masks(const float* maps, int rows, int h, int w, const int32_t* idx, const int32_t* idx_begin, int n_words,
+                       float* word_maps, int out_h, int out_w, int absolute, float threshold, uint8_t* masks, uint8_t* labels,
+                       float* workspace, void* stream);
+
 /* ---- evaluation (next row f4) --------------------------------------------------------------
  * evaluate.compute_iou / compute_ioa (daam/evaluate.py:14-35) and WordHeatMap.compute_ioa (daam/heatmap.py:95-96) for a
  * batch of n pairs: a [n, a_h, a_w] (prediction) and b [n, b_h, b_w] (truth), fp32.  When a_h != b_h -- the reference tests
