@@ -24,7 +24,7 @@ EXPORTS = (
     'daam_tap_probs', 'daam_attend_supported', 'daam_attend', 'daam_key_offset', 'daam_finalize', 'daam_finalize_prepare', 'daam_finalize_groups', 'daam_finalize_bins', 'daam_epilogue_normalize', 'daam_word_heat_map', 'daam_mask_overlap',
     'daam_last_launch', 'daam_last_flush', 'daam_last_kernels', 'daam_profile_enable', 'daam_profile_last_ms', 'daam_profile_history', 'daam_clock_monitor_start', 'daam_clock_monitor_read',
     'daam_ctx_create_rect', 'daam_layer_configure_rect', 'daam_epilogue_normalize_rect', 'daam_word_heat_map_rect',
-    'daam_word_masks',
+    'daam_word_masks', 'daam_mask_overlap_matrix',
 )
 
 
@@ -105,6 +105,7 @@ def load() -> ctypes.CDLL:
     lib.daam_word_masks.argtypes = [c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_int, c_void_p, c_int, c_int,
                                     c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.daam_mask_overlap.argtypes =[c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.daam_mask_overlap_matrix.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.daam_profile_history.argtypes = [c_void_p, c_int, POINTER(c_float), c_int, POINTER(c_int)]
     lib.daam_last_launch.argtypes = [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
     lib.daam_last_flush.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_longlong)]

@@ -6,11 +6,17 @@ calls them once per (word, mask) pair).  Only the final ratio is formed on the h
 ``load_mask`` and the two evaluators of ``daam/evaluate.py:38-117`` (what ``daam/run/evaluate.py`` feeds with these ratios)
 are here too: host-side bookkeeping with the reference's names and results; every candidate prediction of one ``log_iou``
 call goes to the device in ONE ``daam_mask_overlap`` launch instead of one launch + one host sync per candidate.
+
+``mask_overlap_matrix`` scores two whole STACKS of masks of one size against each other (``daam_mask_overlap_matrix``, DESIGN
+3.12): uint8 / bool masks as they are -- e.g. ``Segmentation.masks`` against the truth masks of an image -- every mask byte read
+once, exact integer intersections and areas left on the device, and the IoU / IoA matrices formed from them in the reference's
+operand order.  It does not resize; the resizing route stays ``mask_overlap``.
 """
 from __future__ import annotations
 
 from collections import defaultdict
-from typing import Dict, List, Sequence, Tuple, Union
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -18,10 +24,12 @@ import torch
 from . import _native as nat
 
 __all__ = ['compute_iou', 'compute_ioa', 'mask_overlap', 'compute_iou_batch', 'compute_ioa_batch', 'load_mask',
-           'MeanEvaluator', 'UnsupervisedEvaluator']
+           'MeanEvaluator', 'UnsupervisedEvaluator', 'mask_overlap_matrix', 'MaskOverlaps']
+
+MAX_MATRIX_MASKS = 32                              # masks per stack of one daam_mask_overlap_matrix call (include/daam_hip.h)
 
 
-def _as_batch(t: torch.Tensor, name: str, device=None) -> torch.Tensor:
+def _to_hip(t: torch.Tensor, name: str, device=None) -> torch.Tensor:
     if t.device.type != 'cuda':
         # the reference's evaluation flow hands over CPU masks (load_mask, and expand_as ends in .cpu()): they are moved
         # to the HIP device (the other operand's, else the current one) -- the arithmetic still runs there and only
@@ -29,6 +37,11 @@ def _as_batch(t: torch.Tensor, name: str, device=None) -> torch.Tensor:
         if not torch.cuda.is_available():
             raise RuntimeError(f'daam_amd: {name} is a CPU tensor and no HIP device is visible (there is no CPU fallback)')
         t = t.to(device if device is not None else torch.device('cuda', torch.cuda.current_device()))
+    return t
+
+
+def _as_batch(t: torch.Tensor, name: str, device=None) -> torch.Tensor:
+    t = _to_hip(t, name, device)
     if t.dim() == 2:
         t = t.unsqueeze(0)
     if t.dim() != 3:
@@ -80,6 +93,88 @@ def compute_ioa(a: torch.Tensor, b: torch.Tensor) -> float:
     return float(compute_ioa_batch(a, b)[0])
 
 
+@dataclass
+class MaskOverlaps:
+    """Exact counts of ``mask_overlap_matrix`` (device tensors) and the two ratios of evaluate.py:14-35 formed from them."""
+    intersection: torch.Tensor                  # int32 [A, B]: pixels set in a[i] and in b[j]
+    area_a: torch.Tensor                        # int32 [A]
+    area_b: torch.Tensor                        # int32 [B]
+
+    def iou(self) -> torch.Tensor:
+        """f32 [A, B], in fp32 and in ``_ratios``' operand order (evaluate.py:20-23): inter / ((a + b - inter) + 1e-8)."""
+        inter = self.intersection.to(torch.float32)
+        union = self.area_a.to(torch.float32)[:, None] + self.area_b.to(torch.float32)[None] - inter
+        return inter / (union + 1e-8)
+
+    def ioa(self) -> torch.Tensor:
+        """f32 [A, B] (evaluate.py:32-35): inter / (a + 1e-8)."""
+        return self.intersection.to(torch.float32) / (self.area_a.to(torch.float32)[:, None] + 1e-8)
+
+    def cpu(self) -> 'MaskOverlaps':
+        return MaskOverlaps(self.intersection.cpu(), self.area_a.cpu(), self.area_b.cpu())
+
+
+def _as_masks(t: torch.Tensor, name: str, device=None) -> torch.Tensor:
+    """``[n, h, w]`` uint8, contiguous, on the device: uint8 and bool as they are, any other dtype through ``!= 0``."""
+    t = _to_hip(t, name, device)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3:
+        raise ValueError(f'{name} must be [h, w] or [n, h, w], got {tuple(t.shape)}')
+    if t.shape[0] == 0 or t.shape[1] == 0 or t.shape[2] == 0:
+        raise ValueError(f'{name} is empty: {tuple(t.shape)}')
+    if t.dtype not in (torch.uint8, torch.bool):
+        t = t != 0
+    t = t.contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def _launch_overlap_matrix(a: torch.Tensor, b: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One ``daam_mask_overlap_matrix`` call: ``a`` [A <= 32, h, w], ``b`` [B <= 32, h, w] or None (= ``a``), uint8, contiguous,
+    on one device -> (intersection int32 [A, B], area_a int32 [A], area_b int32 [B]).  The counts are below 2^31."""
+    n_a, n_b = a.shape[0], (a if b is None else b).shape[0]
+    inter = torch.empty(n_a, n_b, dtype=torch.int32, device=a.device)
+    area_a = torch.empty(n_a, dtype=torch.int32, device=a.device)
+    area_b = area_a if b is None else torch.empty(n_b, dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        nat.check(nat.load().daam_mask_overlap_matrix(
+            a.data_ptr(), n_a, None if b is None else b.data_ptr(), n_b, a.shape[1], a.shape[2], inter.data_ptr(), area_a.data_ptr(),
+            None if b is None else area_b.data_ptr(), torch.cuda.current_stream(a.device).cuda_stream))
+    return inter, area_a, area_b
+
+
+def mask_overlap_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None) -> MaskOverlaps:
+    """Every mask of ``a`` [A, h, w] (or [h, w]) against every mask of ``b`` [B, h, w] -- ``None``: of ``a`` itself -- in one launch
+    per 32 x 32 masks: where both are set, and how many pixels each sets.  uint8 and bool masks go to the kernel as they are (a
+    byte != 0 is set), other dtypes through ``!= 0``; CPU tensors are moved to the device.  The masks must have one size: there
+    is no resize here (``mask_overlap`` resizes, pair by pair)."""
+    dev = a.device if a.device.type == 'cuda' else (b.device if b is not None and b.device.type == 'cuda' else None)
+    a = _as_masks(a, 'a', dev)
+    if b is not None:
+        b = _as_masks(b, 'b', dev)
+        if a.shape[1:] != b.shape[1:]:
+            raise ValueError(f'masks of {tuple(a.shape[1:])} against masks of {tuple(b.shape[1:])}: mask_overlap_matrix does not resize')
+        if a.device != b.device:
+            raise RuntimeError('daam_amd: a and b are on different devices')
+    step = MAX_MATRIX_MASKS
+    cols = a if b is None else b
+    if a.shape[0] <= step and cols.shape[0] <= step:
+        return MaskOverlaps(*_launch_overlap_matrix(a, b))
+    # 32 x 32 blocks, stitched on the device.  With b = None the diagonal blocks are one-stack calls and a block below the
+    # diagonal is the transpose of the one above it.
+    blocks: Dict[Tuple[int, int], torch.Tensor] = {}
+    area_a: Dict[int, torch.Tensor] = {}
+    area_b: Dict[int, torch.Tensor] = {}
+    for i in range(0, a.shape[0], step):
+        for j in range(0, cols.shape[0], step):
+            if b is None and j < i:
+                blocks[i, j] = blocks[j, i].t()
+                continue
+            blocks[i, j], area_a[i], area_b[j] = _launch_overlap_matrix(a[i:i + step], None if b is None and i == j else cols[j:j + step])
+    inter = torch.cat([torch.cat([blocks[i, j] for j in range(0, cols.shape[0], step)], dim=1) for i in range(0, a.shape[0], step)])
+    return MaskOverlaps(inter, torch.cat([area_a[i] for i in sorted(area_a)]), torch.cat([area_b[j] for j in sorted(area_b)]))
+
+
 def load_mask(path: str) -> torch.Tensor:
     """A mask stored the way the reference stores them (``*.gt.png`` / ``*.pred.png``, experiment.py:160-163,218-221): an
     RGBA image whose ALPHA channel is the mask; any non-zero alpha counts (evaluate.py:38-43).  Returns a CPU float tensor
@@ -99,6 +194,11 @@ def _best_iou(preds: Union[torch.Tensor, Sequence[torch.Tensor]], truth: torch.T
     preds = list(preds)
     if not preds:
         raise ValueError('max() arg is an empty sequence')                    # what the reference's max() raises
+    if truth.dim() == 2 and all(t.dtype in (torch.uint8, torch.bool) and t.shape == truth.shape for t in [truth] + preds):
+        # masks of one size that are bytes already: nothing is resized, the pair route would widen them to f32 and count the
+        # same pixels -- one matrix launch on the bytes instead (decided by dtype: looking at the values would synchronise)
+        dev = next((t.device for t in [truth] + preds if t.device.type == 'cuda'), None)
+        return float(mask_overlap_matrix(torch.stack([_to_hip(p, 'preds', dev) for p in preds]), truth).iou().max())
     groups: Dict[tuple, List[torch.Tensor]] = defaultdict(list)
     for p in preds:
         groups[(tuple(p.shape), p.device)].append(p)
@@ -120,6 +220,15 @@ class UnsupervisedEvaluator:
 
     def log_iou(self, preds, truth: torch.Tensor, gt_idx: int = 0, pred_idx: int = 0):
         self.ious[gt_idx].append((pred_idx, _best_iou(preds, truth)))
+
+    def log_iou_matrix(self, preds: torch.Tensor, truths: torch.Tensor):
+        """What ``log_iou(preds[p], truths[g], gt_idx=g, pred_idx=p)`` logs for every ``g`` and, under it, every ``p`` -- in that
+        order -- from one ``mask_overlap_matrix`` launch and one copy to the host.  ``preds`` [P, h, w] and ``truths`` [G, h, w]
+        are masks of one size (a value != 0 is set)."""
+        iou = mask_overlap_matrix(preds, truths).iou().cpu().numpy()
+        for g in range(iou.shape[1]):
+            for p in range(iou.shape[0]):
+                self.ious[g].append((p, float(iou[p, g])))
 
     @property
     def mean_iou(self) -> float:

@@ -121,6 +121,26 @@ class Segmentation:
             raise KeyError(word)
         return self.masks[self.words.index(word)]
 
+    def overlaps(self, truth: Union[None, torch.Tensor, 'Segmentation'] = None):
+        """``evaluate.MaskOverlaps`` of the word masks against ``truth`` (a stack of masks of this size, or another
+        ``Segmentation``; ``None``: the words against each other): exact intersections and areas from one launch on the bytes
+        (``evaluate.mask_overlap_matrix``); CPU masks are moved to the device."""
+        from .evaluate import mask_overlap_matrix
+        return mask_overlap_matrix(self.masks, truth.masks if isinstance(truth, Segmentation) else truth)
+
+    def iou(self, truth: Union[torch.Tensor, 'Segmentation']) -> torch.Tensor:
+        """f32 [len(words), len(truth)]: ``compute_iou`` (evaluate.py:14-23) of every word mask with every truth mask."""
+        return self.overlaps(truth).iou()
+
+    def ioa(self, truth: Union[None, torch.Tensor, 'Segmentation'] = None) -> torch.Tensor:
+        """f32 [len(words), ...]: ``compute_ioa`` (evaluate.py:26-35); ``None``: of every word's mask with every other word's."""
+        return self.overlaps(truth).ioa()
+
+    def ioa_of(self, word_a: str, word_b: str) -> float:
+        """``WordHeatMap.compute_ioa`` (heatmap.py:95-96) of the thresholded masks of two words: |a and b| / |a|."""
+        from .evaluate import mask_overlap_matrix
+        return float(mask_overlap_matrix(self.mask(word_a), self.mask(word_b)).ioa()[0, 0])
+
     def cpu(self) -> 'Segmentation':
         maps = [WordHeatMap(m.heatmap.cpu(), m.word, m.word_idx) for m in self.word_heat_maps]
         return Segmentation(list(self.words), maps, self.masks.cpu(), None if self.labels is None else self.labels.cpu())

@@ -302,6 +302,17 @@ DAAM_API int daam_word_masks(const float* maps, int rows, int h, int w, const in
 DAAM_API int daam_mask_overlap(const float* a, int a_h, int a_w, const float* b, int b_h, int b_w, int n_pairs, float* sums,
                                void* stream);
 
+/* The overlap matrix of two stacks of u8 masks in one pass (same ABI version: additive): what compute_iou / compute_ioa
+ * (daam/evaluate.py:14-35) need for every prediction against every truth mask, and WordHeatMap.compute_ioa (daam/heatmap.py:95-96)
+ * for every pair of words of one prompt, e.g. on the masks daam_word_masks leaves on the device.
+ * a: [n_a, h, w] uint8, b: [n_b, h, w] uint8 (contiguous planes; a byte != 0 is "set"); b == NULL means b = a, n_b = n_a.
+ * inter[i * n_b + j] = #{p : a_i[p] != 0 && b_j[p] != 0}, area_a[i] = #{p : a_i[p] != 0}, area_b[j] likewise (uint32, device).
+ * 1 <= n_a, n_b <= 32, 1 <= h, w, h * w < 2^31.  The call overwrites all three outputs itself; area_b may be NULL when b is.
+ * Base pointers need no alignment beyond one byte (a plane of an odd-sized stack starts anywhere).  Counts are exact integers;
+ * every mask byte is fetched once.  The caller forms IoU = inter / (area_a + area_b - inter + 1e-8), IoA = inter / (area_a + 1e-8). */
+DAAM_API int daam_mask_overlap_matrix(const uint8_t* a, int n_a, const uint8_t* b, int n_b, int h, int w,
+                                      uint32_t* inter, uint32_t* area_a, uint32_t* area_b, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 DAAM_API int daam_abi_version(void);
 DAAM_API const char* daam_last_error(void);
