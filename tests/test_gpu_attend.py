@@ -219,6 +219,8 @@ def test_attend_declines_what_the_kernel_does_not_take():
     assert eng.attend(0, q[:, :, :128], k[:, :, :128], v[:, :, :128], 4, 32 ** -0.5, 1, True, tapped=False) is None  # strided views
     assert eng.attend(0, q, k[:, :64], v[:, :64], 4, 0.125, 1, True, tapped=False) is None                # 64 keys
     assert eng.attend(0, q.transpose(0, 1).contiguous().transpose(0, 1), k, v, 4, 0.125, 1, True, tapped=False) is None
+    for hw in (20, 988):                                                                                  # hw % 8 != 0 (988 = 26 x 38)
+        assert eng.attend(0, _inputs(2, 4, hw, seed=1)[0], k, v, 4, 0.125, 1, True, tapped=False) is None
     assert eng.attend(0, q, k, v, 4, 0.125, 1, True, tapped=False) is not None
     eng.close()
 
