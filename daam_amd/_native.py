@@ -24,7 +24,7 @@ EXPORTS = (
     'daam_tap_probs', 'daam_attend_supported', 'daam_attend', 'daam_key_offset', 'daam_finalize', 'daam_finalize_prepare', 'daam_finalize_groups', 'daam_finalize_bins', 'daam_epilogue_normalize', 'daam_word_heat_map', 'daam_mask_overlap',
     'daam_last_launch', 'daam_last_flush', 'daam_last_kernels', 'daam_profile_enable', 'daam_profile_last_ms', 'daam_profile_history', 'daam_clock_monitor_start', 'daam_clock_monitor_read',
     'daam_ctx_create_rect', 'daam_layer_configure_rect', 'daam_epilogue_normalize_rect', 'daam_word_heat_map_rect',
-    'daam_word_masks', 'daam_mask_overlap_matrix',
+    'daam_word_masks', 'daam_mask_overlap_matrix', 'daam_region_scores_workspace', 'daam_region_scores', 'daam_region_dots',
 )
 
 
@@ -106,6 +106,10 @@ def load() -> ctypes.CDLL:
                                     c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.daam_mask_overlap.argtypes =[c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.daam_mask_overlap_matrix.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.daam_region_scores_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.daam_region_scores.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]
+    lib.daam_region_dots.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.daam_profile_history.argtypes = [c_void_p, c_int, POINTER(c_float), c_int, POINTER(c_int)]
     lib.daam_last_launch.argtypes = [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
     lib.daam_last_flush.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_longlong)]
@@ -116,8 +120,9 @@ def load() -> ctypes.CDLL:
     lib.daam_clock_monitor_read.argtypes = [c_void_p, POINTER(c_float), c_int, POINTER(c_int)]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ('daam_last_error',):
+        if name not in ('daam_last_error', 'daam_region_scores_workspace'):
             fn.restype = c_int
+    lib.daam_region_scores_workspace.restype = c_size_t
     if lib.daam_abi_version() != ABI_VERSION:
         raise RuntimeError(f'{LIB_PATH}: ABI version {lib.daam_abi_version()} != {ABI_VERSION}; rebuild')
     _lib = lib

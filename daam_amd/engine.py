@@ -1207,3 +1207,75 @@ def _check_maps(maps: torch.Tensor) -> None:
         raise RuntimeError('daam_amd: heat maps must live on the HIP device (no CPU fallback)')
     if maps.dtype != torch.float32 or not maps.is_contiguous() or maps.dim() != 3:
         raise RuntimeError('daam_amd: heat maps must be a contiguous fp32 [rows, h, w] tensor')
+
+
+MAX_REGION_MASKS = 32                             # limit of one daam_region_scores call (include/daam_hip.h)
+
+
+def _check_map_sets(maps: torch.Tensor) -> torch.Tensor:
+    """``[rows, h, w]`` or ``[G, rows, h, w]`` -> the 4-d view, held to what ``_check_maps`` asks of a stack of maps."""
+    if maps.dim() == 4 and maps.device.type == 'cuda' and maps.dtype == torch.float32 and maps.is_contiguous() and maps.shape[0] >= 1:
+        sets = maps
+    else:
+        _check_maps(maps)
+        sets = maps.unsqueeze(0)
+    if sets.shape[1] < 1 or not (1 <= sets.shape[2] <= 128 and 1 <= sets.shape[3] <= 128):
+        raise ValueError(f'region scores take maps of at least one row and 1..128 cells a side, got {tuple(maps.shape)}')
+    return sets
+
+
+def region_scores(maps: torch.Tensor, masks: torch.Tensor):
+    """``daam_region_scores``: how much of every row's expanded heat map lies inside every mask.  ``maps`` is [rows, h, w] or
+    [G, rows, h, w] fp32 on the device, ``masks`` [M, H, W] (or [H, W]) uint8 / bool (a byte != 0 is set; other dtypes through
+    ``!= 0``; CPU masks are moved to the device).  Returns ``(scores, area, footprint)``: ``scores[..., m, t]`` = the sum over the set
+    pixels of mask ``m`` of ``expand_word_map(maps[..., t], H, W, absolute=True)`` as fp32 [M, rows] (or [G, M, rows]), ``area``
+    int32 [M] the exact pixel counts, ``footprint`` fp32 [M, h, w] the masks pulled back onto the maps' grid, which
+    ``region_dots`` scores further map sets against.  No plane of H x W is written; more than 32 masks run in chunks of 32."""
+    from .evaluate import _as_masks
+    sets = _check_map_sets(maps)
+    masks = _as_masks(masks, 'masks', maps.device)
+    if masks.device != maps.device:
+        raise RuntimeError('daam_amd: maps and masks are on different devices')
+    n_sets, rows, h, w = sets.shape
+    big_h, big_w = masks.shape[1:]
+    lib = nat.load()
+    out = []
+    with torch.cuda.device(maps.device):
+        stream = torch.cuda.current_stream(maps.device).cuda_stream
+        for at in range(0, masks.shape[0], MAX_REGION_MASKS):
+            chunk = masks[at:at + MAX_REGION_MASKS]
+            n = chunk.shape[0]
+            size = lib.daam_region_scores_workspace(n, big_h, big_w, h, w)
+            if size == 0:
+                raise ValueError(f'region scores: masks of {big_h} x {big_w} are outside the limits (H * W < 2^31)')
+            ws = torch.empty(size, dtype=torch.uint8, device=maps.device)
+            scores = torch.empty(n_sets, n, rows, dtype=torch.float32, device=maps.device)
+            area = torch.empty(n, dtype=torch.int32, device=maps.device)
+            footprint = torch.empty(n, h, w, dtype=torch.float32, device=maps.device)
+            nat.check(lib.daam_region_scores(chunk.data_ptr(), n, big_h, big_w, sets.data_ptr(), n_sets, rows, h, w, footprint.data_ptr(),
+                                             scores.data_ptr(), area.data_ptr(), ws.data_ptr(), stream))
+            out.append((scores, area, footprint))
+    scores, area, footprint = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out], dim=1), torch.cat([o[1] for o in out]),
+                                                           torch.cat([o[2] for o in out]))
+    return (scores if maps.dim() == 4 else scores[0]), area, footprint
+
+
+def region_dots(maps: torch.Tensor, footprint: torch.Tensor) -> torch.Tensor:
+    """``daam_region_dots``: the scores of a further map set ([rows, h, w] or [G, rows, h, w]) against the ``footprint`` [M, h, w]
+    that ``region_scores`` returned -- bit for bit what ``region_scores`` gives for these maps and the masks behind the footprint."""
+    sets = _check_map_sets(maps)
+    if footprint.device != maps.device or footprint.dtype != torch.float32 or footprint.dim() != 3 or not footprint.is_contiguous():
+        raise RuntimeError('daam_amd: footprint must be a contiguous fp32 [M, h, w] tensor on the maps\' device')
+    if footprint.shape[1:] != sets.shape[2:]:
+        raise ValueError(f'footprint of {tuple(footprint.shape[1:])} against maps of {tuple(sets.shape[2:])}')
+    n_sets, rows, h, w = sets.shape
+    out = []
+    with torch.cuda.device(maps.device):
+        for at in range(0, footprint.shape[0], MAX_REGION_MASKS):
+            chunk = footprint[at:at + MAX_REGION_MASKS]
+            scores = torch.empty(n_sets, chunk.shape[0], rows, dtype=torch.float32, device=maps.device)
+            nat.check(nat.load().daam_region_dots(chunk.data_ptr(), chunk.shape[0], sets.data_ptr(), n_sets, rows, h, w, scores.data_ptr(),
+                                                  torch.cuda.current_stream(maps.device).cuda_stream))
+            out.append(scores)
+    scores = out[0] if len(out) == 1 else torch.cat(out, dim=1)
+    return scores if maps.dim() == 4 else scores[0]

@@ -12,7 +12,8 @@ import torch
 from . import engine as _engine
 from .utils import cached_nlp, compute_token_merge_indices
 
-__all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair', 'Segmentation']
+__all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair', 'Segmentation',
+           'RegionAttribution']
 
 RawHeatMapKey = Tuple[int, int, int]  # factor, layer, head
 
@@ -146,6 +147,39 @@ class Segmentation:
         return Segmentation(list(self.words), maps, self.masks.cpu(), None if self.labels is None else self.labels.cpu())
 
 
+@dataclass
+class RegionAttribution:
+    """Which prompt tokens put their attention inside each of M image regions (``GlobalHeatMap.attribute``): the sums of every
+    token row's expanded heat map (``expand_as(absolute=True)``, no min-max, no threshold) under each region's mask.  Everything
+    lives on the device until ``cpu()`` is asked for."""
+    scores: torch.Tensor                        # f32 [M, rows]: sum over the region's pixels of row t's expanded map
+    area: torch.Tensor                          # int32 [M]: pixels of each region
+    footprint: torch.Tensor                     # f32 [M, h, w]: the masks pulled back onto the maps' grid (``engine.region_dots``)
+    tokenizer: Any = None
+    prompt: Optional[str] = None
+
+    def mean(self) -> torch.Tensor:
+        """f32 [M, rows]: the mean expanded value inside each region, ``scores / max(area, 1)``."""
+        return self.scores / self.area.clamp(min=1).to(torch.float32)[:, None]
+
+    def word_scores(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]]) -> torch.Tensor:
+        """f32 [M, len(words)]: the mean of ``scores`` over each word's token rows (``compute_token_merge_indices``) -- by
+        linearity the score of ``compute_word_heat_map(word)`` under each region."""
+        cols = []
+        for word in words:
+            w, i = (word, None) if isinstance(word, str) else (word[0], word[1])
+            idxs, _ = compute_token_merge_indices(self.tokenizer, self.prompt, w, i)
+            cols.append(self.scores[:, list(idxs)].mean(dim=1))
+        return torch.stack(cols, dim=1)
+
+    def top_words(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]], k: int = 1):
+        """``torch.topk`` of ``word_scores(words)`` along the words: ``(values, indices)``, each [M, k]."""
+        return torch.topk(self.word_scores(words), k, dim=1)
+
+    def cpu(self) -> 'RegionAttribution':
+        return RegionAttribution(self.scores.cpu(), self.area.cpu(), self.footprint.cpu(), self.tokenizer, self.prompt)
+
+
 class GlobalHeatMap:
     """reference heatmap.py:114-142."""
 
@@ -191,6 +225,16 @@ class GlobalHeatMap:
         planes = [plane for wm in word_maps for plane in wm]
         heat = [WordHeatMap(plane, w, r[1]) for plane, (w, _), r in zip(planes, pairs, resolved)]
         return Segmentation([w for w, _ in pairs], heat, masks[0] if len(masks) == 1 else torch.cat(masks), label_map)
+
+    def attribute(self, regions: Union[torch.Tensor, Segmentation]) -> RegionAttribution:
+        """The opposite question to ``segment``: for each region -- ``regions`` is a mask [H, W], a stack [M, H, W] (uint8 / bool as
+        they are, other dtypes through ``!= 0``) or a ``Segmentation`` (its ``.masks``) -- how much of every token row's expanded
+        heat map lies inside it (``engine.region_scores``: one pass over the mask bytes, no plane at image resolution).  The
+        target size is the masks' own ``[H, W]``, taken as it is, which is how ``Segmentation.masks`` is laid out: no PIL-order
+        swap happens here (``expand_as`` / ``segment`` apply theirs when they read ``image.size``)."""
+        masks = regions.masks if isinstance(regions, Segmentation) else regions
+        scores, area, footprint = _engine.region_scores(self.heat_maps, masks)
+        return RegionAttribution(scores, area, footprint, self.tokenizer, self.prompt)
 
     def parsed_heat_maps(self) -> Iterable[ParsedHeatMap]:
         """One ``ParsedHeatMap`` per token of the parsed prompt whose text is found among the prompt's tokenizer tokens

@@ -313,6 +313,30 @@ DAAM_API int daam_mask_overlap(const float* a, int a_h, int a_w, const float* b,
 DAAM_API int daam_mask_overlap_matrix(const uint8_t* a, int n_a, const uint8_t* b, int n_b, int h, int w,
                                       uint32_t* inter, uint32_t* area_a, uint32_t* area_b, void* stream);
 
+/* Region attribution (same ABI version: additive): how much of every token row's expanded heat map lies inside each of n_masks
+ * regions, scores[g][m][t] = sum over the pixels p with masks[m][p] != 0 of E_t[p], where E_t is what daam_word_heat_map[_rect]
+ * writes for the plane maps[g][t] with absolute = 1 and threshold 0 (daam/heatmap.py:77-93: the bicubic of F.interpolate to the
+ * image size, no min-max, no threshold) -- the expansion generalised from one word plane to every row, and from a picture to its sum
+ * under a mask.  A byte != 0 is "set", the convention of daam/evaluate.py (load_mask: alpha > 0; compute_iou / compute_ioa on 0 / 1
+ * masks) and of daam_mask_overlap_matrix.  The expansion is linear, so the call pulls every mask back through the transpose of the
+ * resize once -- footprint[m][i][j] = sum over set (y, x) of wy[y][i] wx[x][j], clamped taps folded onto the edge cell -- and a
+ * score is a dot product of h * w terms.  No fp32 plane of H x W is written anywhere; every mask byte is fetched once.
+ *   masks     [n_masks, H, W] uint8, contiguous planes, any byte alignment;  1 <= n_masks <= 32, H, W >= 1, H * W < 2^31
+ *   maps      [n_sets, rows, h, w] fp32 or NULL (then scores must be NULL too: footprint and area only);  1 <= h, w <= 128,
+ *             n_sets (<= 65535), rows >= 1
+ *   footprint [n_masks, h, w] fp32 (required): at H == h && W == w the mask itself as 0.0 / 1.0
+ *   scores    [n_sets, n_masks, rows] fp32;  area [n_masks] uint32: the exact count of set bytes
+ *   workspace daam_region_scores_workspace(...) bytes of device scratch, 16-byte aligned (0: the sizes are outside the limits)
+ * Anything outside the limits is DAAM_E_INVALID before any launch.  The call overwrites all its outputs itself.  No floating-point
+ * atomics: the results for mask m are bit-identical from run to run and do not depend on the other masks of the call, nor on
+ * where its plane starts in memory.  Sums are fp32 with short chains (DESIGN 3.13 counts the roundings).
+ * daam_region_dots is the last step alone: further map sets against a footprint that a daam_region_scores call left. */
+DAAM_API size_t daam_region_scores_workspace(int n_masks, int H, int W, int h, int w);
+DAAM_API int daam_region_scores(const uint8_t* masks, int n_masks, int H, int W, const float* maps, int n_sets, int rows, int h, int w,
+                                float* footprint, float* scores, uint32_t* area, void* workspace, void* stream);
+DAAM_API int daam_region_dots(const float* footprint, int n_masks, const float* maps, int n_sets, int rows, int h, int w,
+                              float* scores, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 DAAM_API int daam_abi_version(void);
 DAAM_API const char* daam_last_error(void);
