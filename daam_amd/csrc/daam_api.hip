@@ -1,5 +1,6 @@
-// Host side of libdaam_hip.so: the C ABI declared in include/daam_hip.h -- context, layers, time bins, attend, probs tap, epilogue,
-// profiling and the clock monitor (the tap entry points: daam_tap_api.hip; the finalize ones: daam_finalize_api.hip).
+// Host side of libdaam_hip.so: the C ABI declared in include/daam_hip.h -- context, layers, time bins, attend, probs tap,
+// profiling and the clock monitor (the tap entry points: daam_tap_api.hip; the finalize ones: daam_finalize_api.hip; the epilogue's:
+// daam_epilogue.hip and the three files beside it).
 // Owns no activations; owns (optionally) the running sums, the bicubic tap tables and a
 // small pinned upload ring for the per-launch device tables.
 #include "daam_ctx.h"
@@ -24,6 +25,11 @@ int fail(int code, const char* fmt, ...)
     va_end(ap);
     g_err = buf;
     return code;
+}
+
+int launched(const char* what, hipError_t e)
+{
+    return e == hipSuccess ? 0 : fail((int)e, "%s launch: %s", what, hipGetErrorString(e));
 }
 
 // torch upsample_bicubic2d, align_corners=False, antialias=False:
@@ -556,50 +562,6 @@ int daam_key_offset(DaamCtx* c, int layer, int* offset, int* total)
     }
     if (offset) *offset = off;
     if (total) *total = tot;
-    return 0;
-}
-
-
-int daam_epilogue_normalize(float* maps, int n_rows, int side, void* stream)
-{
-    return daam_epilogue_normalize_rect(maps, n_rows, side, side, stream);
-}
-
-int daam_epilogue_normalize_rect(float* maps, int n_rows, int h, int w, void* stream)
-{
-    if (!maps || n_rows <= 0 || h <= 0 || w <= 0) return fail(DAAM_E_INVALID, "bad argument");
-    hipError_t e = launch_normalize(maps, n_rows, h * w, (hipStream_t)stream);
-    if (e != hipSuccess) return fail((int)e, "normalize launch: %s", hipGetErrorString(e));
-    return 0;
-}
-
-int daam_word_heat_map(const float* maps, int side, const int32_t* idx, int n_idx, float* word_map, float* out,
-                       int out_h, int out_w, int absolute, float threshold, float* workspace, void* stream)
-{
-    return daam_word_heat_map_rect(maps, side, side, idx, n_idx, word_map, out, out_h, out_w, absolute, threshold, workspace, stream);
-}
-
-int daam_word_heat_map_rect(const float* maps, int h, int w, const int32_t* idx, int n_idx, float* word_map, float* out,
-                            int out_h, int out_w, int absolute, float threshold, float* workspace, void* stream)
-{
-    if (!maps || !idx || !word_map || !workspace) return fail(DAAM_E_INVALID, "NULL argument");
-    if (n_idx <= 0 || n_idx > kMaxTokens) return fail(DAAM_E_INVALID, "n_idx %d not in 1..%d", n_idx, kMaxTokens);
-    if (h <= 0 || w <= 0 || (out && (out_h <= 0 || out_w <= 0))) return fail(DAAM_E_INVALID, "bad size");
-    hipError_t e = launch_word(maps, h, w, idx, n_idx, word_map, out, out_h, out_w, absolute, threshold, workspace,
-                               (hipStream_t)stream);
-    if (e != hipSuccess) return fail((int)e, "word map launch: %s", hipGetErrorString(e));
-    return 0;
-}
-
-int daam_mask_overlap(const float* a, int a_h, int a_w, const float* b, int b_h, int b_w, int n_pairs, float* sums, void* stream)
-{
-    if (!a || !b || !sums) return fail(DAAM_E_INVALID, "NULL argument");
-    if (n_pairs <= 0 || n_pairs > 65535 || a_h <= 0 || a_w <= 0 || b_h <= 0 || b_w <= 0 || (long long)b_h * b_w > (1ll << 30))
-        return fail(DAAM_E_INVALID, "bad shape: %d pairs, a %dx%d, b %dx%d", n_pairs, a_h, a_w, b_h, b_w);
-    if (a_h == b_h && a_w != b_w)
-        return fail(DAAM_E_INVALID, "same heights but widths %d / %d differ (the reference's a * b would not broadcast)", a_w, b_w);
-    hipError_t e = launch_mask_overlap(a, a_h, a_w, b, b_h, b_w, n_pairs, sums, (hipStream_t)stream);
-    if (e != hipSuccess) return fail((int)e, "mask overlap launch: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -1,5 +1,6 @@
-// Host-only internals of libdaam_hip.so shared by the three parts of the C ABI (daam_api.hip: context, layers, attend, profiling;
-// daam_tap_api.hip: the tap entry points; daam_finalize_api.hip: the finalize entry points): the kernel files' host launchers, the
+// Host-only internals of libdaam_hip.so shared by the parts of the C ABI (daam_api.hip: context, layers, attend, profiling;
+// daam_tap_api.hip: the tap entry points; daam_finalize_api.hip: the finalize entry points; daam_epilogue.hip, daam_word_masks.hip,
+// daam_mask_matrix.hip, daam_region_scores.hip: the epilogue's, each beside its kernels): the kernel files' host launchers, the
 // context and its helpers.
 #pragma once
 #include "daam_types.h"
@@ -51,15 +52,11 @@ hipError_t launch_finalize_same_grouped(const FinGroupLaunch&, int n_groups, int
 hipError_t launch_finalize_up_grouped(const FinGroupLaunch&, int n_groups, int side, int acc_dtype, hipStream_t, int*);
 hipError_t launch_finalize_down2_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
 hipError_t launch_finalize_up32_pipe_grouped(const FinPipeGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
-hipError_t launch_normalize(float*, int, int, hipStream_t);
-hipError_t launch_mask_overlap(const float*, int, int, const float*, int, int, int, float*, hipStream_t);
 bool attend_d64_supported(int in_dtype, int head_dim, int tokens, const int64_t* strides, int n_strides, const void* const* ptrs, int n_ptrs);
 hipError_t launch_attend_d64(const AttendLaunch&, int in_dtype, int acc_dtype, int fast_exp, hipStream_t, int*, int*);
 hipError_t launch_clock_monitor(unsigned long long* samples, int n_samples, int period_us, hipStream_t);
 hipError_t launch_start_gate(const unsigned* counter, unsigned target, int timeout_us, unsigned* timeouts, hipStream_t);
 constexpr int kClockMaxSamples = 4096;
-hipError_t launch_word(const float*, int, int, const int32_t*, int, float*, float*, int, int, int, float, float*,
-                       hipStream_t);
 hipError_t launch_finalize_bin_sum(const BinSumLaunch&, int acc_dtype, hipStream_t);
 int bin_sum_elems_per_tile(int acc_dtype);
 }  // namespace daam
@@ -68,6 +65,8 @@ using namespace daam;
 
 // sets the calling thread's daam_last_error() text (defined in daam_api.hip) and returns `code`
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// the end of an entry point that has enqueued its kernels: 0, or fail() with "<what> launch: <the HIP error's text>"
+int launched(const char* what, hipError_t e = hipGetLastError());
 
 #define HIP_TRY(expr)                                                                  \
     do {                                                                               \

@@ -3,9 +3,9 @@
 //   * tap_generic_kernel   : softmax(scale q k^T) -> conditional half -> running sums
 //                            (reference daam/trace.py:276-294 + daam/heatmap.py:153-156)
 //   * tap_probs_kernel     : the same accumulate from materialised probabilities
-//   * finalize_kernel      : bicubic -> clamp -> mean over keys (daam/trace.py:112-126)
-//   * normalize_kernel     : daam/trace.py:129-130
-//   * word map kernels     : daam/heatmap.py:121-123, 77-93
+//   * finalize_kernel      : bicubic -> clamp -> mean over keys (daam/trace.py:112-126), and its grouped form
+//   * upload_kernel, zero_groups_kernel, clock_monitor_kernel, start_gate_kernel : the launches' plumbing
+// (normalise, word maps and the pair overlap: daam_epilogue.hip)
 #include "daam_types.h"
 
 namespace daam {
@@ -209,168 +209,6 @@ __global__ __launch_bounds__(256) void finalize_grouped_kernel(const FinGroupLau
 #include "daam_fin_kernel_body.inc"
 }
 
-// trace.py:129-130  maps[:n] / (maps[1:n-1].sum(0) + 1e-6)
-__global__ __launch_bounds__(256) void normalize_kernel(float* maps, int n_rows, int plane)
-{
-    const int px = blockIdx.x * 256 + threadIdx.x;
-    if (px >= plane) return;
-    float s = 0.f;
-    for (int t = 1; t < n_rows - 1; ++t) s += maps[(size_t)t * plane + px];
-    s += 1e-6f;
-    for (int t = 0; t < n_rows; ++t) maps[(size_t)t * plane + px] /= s;
-}
-
-// ---------------------------------------------------------------------------------------
-// Word heat map (heatmap.py:121-123) and expand_as (heatmap.py:77-93).
-// ---------------------------------------------------------------------------------------
-struct WordIdx { int32_t n; int32_t idx[kMaxTokens]; };
-
-__global__ __launch_bounds__(256) void word_mean_kernel(const float* maps, int plane, WordIdx w, float* word_map,
-                                                        float* minmax)
-{
-    const int px = blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        // order-preserving int encodings of +inf / -inf for the atomicMin / atomicMax below
-        reinterpret_cast<int*>(minmax)[0] = 0x7f800000;
-        reinterpret_cast<int*>(minmax)[1] = (int)0x80000000 ^ 0x7fffffff ^ 0x7f800000;   // enc(-inf)
-    }
-    if (px >= plane) return;
-    float s = 0.f;
-    for (int i = 0; i < w.n; ++i) s += maps[(size_t)w.idx[i] * plane + px];
-    word_map[px] = s / (float)w.n;
-}
-
-__device__ __forceinline__ int enc_ordered(float f) {
-    const int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float dec_ordered(int i) {
-    return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff);
-}
-
-__device__ __forceinline__ void cubic_coeffs(float t, float w[4]) {
-#pragma clang fp contract(off)
-    const float A = -0.75f;
-    const float x0 = t + 1.0f;
-    w[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
-    w[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
-    const float u = 1.0f - t;
-    w[2] = ((A + 2.0f) * u - (A + 3.0f)) * u * u + 1.0f;
-    const float x3 = u + 1.0f;
-    w[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
-}
-
-// Results the caller copies to the host right behind the kernel (expand_as returns a CPU tensor, heatmap.py:88) are stored write-through
-// (system scope): the copy engine reads memory, not the L2s.  Round 6 saw ONE expand_as result in ~10^5 whose 64 consecutive elements (two
-// cache lines) still held the block's previous owner's data after the copy (four test processes sharing the GPU; not reproduced in 80 000
-// calls) -- with write-through stores the result does not depend on when an L2 writes a dirty line back.
-__device__ __forceinline__ void store_for_host(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-
-__global__ __launch_bounds__(256) void word_expand_kernel(const float* word_map, int side, float* out, int out_h,
-                                                          int out_w, float* minmax)
-{
-#define SRC_H side
-#define SRC_W side
-#include "daam_word_expand_body.inc"
-#undef SRC_H
-#undef SRC_W
-}
-
-// a source plane of unequal sides (daam_word_heat_map_rect)
-__global__ __launch_bounds__(256) void word_expand_rect_kernel(const float* word_map, int src_h, int src_w, float* out, int out_h,
-                                                               int out_w, float* minmax)
-{
-#define SRC_H src_h
-#define SRC_W src_w
-#include "daam_word_expand_body.inc"
-#undef SRC_H
-#undef SRC_W
-}
-
-__global__ __launch_bounds__(256) void word_post_kernel(float* out, int n, const float* minmax, int absolute,
-                                                        float threshold)
-{
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float v = out[i];
-    if (!absolute) {
-        const float lo = dec_ordered(reinterpret_cast<const int*>(minmax)[0]);
-        const float hi = dec_ordered(reinterpret_cast<const int*>(minmax)[1]);
-        v = (v - lo) / (hi - lo + 1e-8f);
-    }
-    if (threshold != 0.f) v = v > threshold ? 1.f : 0.f;      // `if threshold:` (heatmap.py:85)
-    store_for_host(out + i, v);
-}
-
-// ---------------------------------------------------------------------------------------
-// evaluate.compute_iou / compute_ioa (reference daam/evaluate.py:14-35) for a batch of (prediction, truth) pairs.
-// One thread per pixel of the truth mask b; when the shapes differ (the reference tests shape[0] only) the prediction a is
-// resized with the bicubic of F.interpolate (align_corners=False, A = -0.75, border-clamped taps; x on the four source rows,
-// then y) and binarised (a < 1 -> 0, else 1); sums[pair] += {a*b, a, b}, one f32 atomic per wave and quantity -- exact for
-// binary masks (integer sums below 2^24), order-dependent in the last bits for soft ones.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mask_overlap_kernel(const float* a, int a_h, int a_w, const float* b, int b_h, int b_w,
-                                                           int resize, float* sums)
-{
-#pragma clang fp contract(off)
-    const int pair = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const float* ap = a + (size_t)pair * a_h * a_w;
-    float va = 0.f, vb = 0.f;
-    if (i < b_h * b_w) {
-        vb = b[(size_t)pair * b_h * b_w + i];
-        if (!resize) {
-            va = ap[i];
-        } else {
-            const int oy = i / b_w, ox = i - oy * b_w;
-            float wy[4], wx[4];
-            int iy[4], ix[4];
-            {
-                const float sc = (float)a_h / (float)b_h;
-                const float src = sc * ((float)oy + 0.5f) - 0.5f;
-                const float f = floorf(src);
-                cubic_coeffs(src - f, wy);
-                for (int t = 0; t < 4; ++t) iy[t] = min(max((int)f - 1 + t, 0), a_h - 1);
-            }
-            {
-                const float sc = (float)a_w / (float)b_w;
-                const float src = sc * ((float)ox + 0.5f) - 0.5f;
-                const float f = floorf(src);
-                cubic_coeffs(src - f, wx);
-                for (int t = 0; t < 4; ++t) ix[t] = min(max((int)f - 1 + t, 0), a_w - 1);
-            }
-            float rows[4];
-            for (int t = 0; t < 4; ++t) {
-                const float* r = ap + (size_t)iy[t] * a_w;
-                rows[t] = r[ix[0]] * wx[0] + r[ix[1]] * wx[1] + r[ix[2]] * wx[2] + r[ix[3]] * wx[3];
-            }
-            const float v = rows[0] * wy[0] + rows[1] * wy[1] + rows[2] * wy[2] + rows[3] * wy[3];
-            va = v < 1.0f ? 0.0f : (v >= 1.0f ? 1.0f : v);    // a[a < 1] = 0; a[a >= 1] = 1  (evaluate.py:17-18): a NaN stays a NaN
-        }
-    }
-    float inter = va * vb, sa = va, sb = vb;
-    for (int off = 32; off > 0; off >>= 1) {
-        inter += __shfl_xor(inter, off, 64);
-        sa += __shfl_xor(sa, off, 64);
-        sb += __shfl_xor(sb, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(sums + 3 * pair + 0, inter);
-        atomicAdd(sums + 3 * pair + 1, sa);
-        atomicAdd(sums + 3 * pair + 2, sb);
-    }
-}
-
-hipError_t launch_mask_overlap(const float* a, int a_h, int a_w, const float* b, int b_h, int b_w, int n, float* sums, hipStream_t stream)
-{
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(float) * 3 * (size_t)n, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mask_overlap_kernel, dim3((b_h * b_w + 255) / 256, n), dim3(256), 0, stream, a, a_h, a_w, b, b_h, b_w,
-                       a_h != b_h ? 1 : 0, sums);
-    return hipGetLastError();
-}
-
 // per-launch device tables: pinned host (device-mapped) -> device twin, in stream order on the
 // compute queue (16 bytes per thread; tables are a few tens of KB)
 __global__ __launch_bounds__(256) void upload_kernel(float4* dst, const float4* src, int n16, float4* zero, int z16)
@@ -567,36 +405,6 @@ __global__ __launch_bounds__(64) void start_gate_kernel(const unsigned* counter,
 hipError_t launch_start_gate(const unsigned* counter, unsigned target, int timeout_us, unsigned* timeouts, hipStream_t stream)
 {
     hipLaunchKernelGGL(start_gate_kernel, dim3(1), dim3(64), 0, stream, counter, target, timeout_us, timeouts);
-    return hipGetLastError();
-}
-
-hipError_t launch_normalize(float* maps, int n_rows, int plane, hipStream_t stream)
-{
-    hipLaunchKernelGGL(normalize_kernel, dim3((plane + 255) / 256), dim3(256), 0, stream, maps, n_rows, plane);
-    return hipGetLastError();
-}
-
-hipError_t launch_word(const float* maps, int src_h, int src_w, const int32_t* idx, int n_idx, float* word_map, float* out,
-                       int out_h, int out_w, int absolute, float threshold, float* workspace, hipStream_t stream)
-{
-    WordIdx w;
-    w.n = n_idx;
-    for (int i = 0; i < n_idx; ++i) w.idx[i] = idx[i];
-    const int plane = src_h * src_w;
-    hipLaunchKernelGGL(word_mean_kernel, dim3((plane + 255) / 256), dim3(256), 0, stream, maps, plane, w, word_map,
-                       workspace);
-    if (out) {
-        const int n = out_h * out_w;
-        if (src_h == src_w)
-            hipLaunchKernelGGL(word_expand_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, word_map, src_h, out,
-                               out_h, out_w, workspace);
-        else
-            hipLaunchKernelGGL(word_expand_rect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, word_map, src_h, src_w, out,
-                               out_h, out_w, workspace);
-        if (!absolute || threshold != 0.f)
-            hipLaunchKernelGGL(word_post_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, out, n, workspace,
-                               absolute, threshold);
-    }
     return hipGetLastError();
 }
 

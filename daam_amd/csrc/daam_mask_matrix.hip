@@ -4,12 +4,13 @@
 // (heatmap.py:95-96) for all word pairs of one prompt.  Integer counts only: no float is accumulated anywhere.
 //   * mask_matrix_zero_kernel : the three outputs to zero (the call owns them)
 //   * mask_matrix_kernel      : a workgroup of eight waves walks tiles of 1024 pixels.  Per tile a wave turns its planes into bit sets
-//                               (a lane: one aligned 16-byte load -> 16 bits) in LDS, then every lane holds a 4 x 4 block of cells
+//                               (a lane: one aligned 16-byte load -> 16 bits, mask_bits16 of daam_epilogue.h) in LDS, then every lane holds a 4 x 4 block of cells
 //                               and adds popcount(A_i & B_j) over the tile's 32-bit words.  Cells and areas are summed over the
 //                               workgroup's waves in LDS; one global atomic add per non-zero cell and workgroup, at its end.
 // The planes are flat: only h * w matters.  A plane may start at any byte: the loads are the aligned 16-byte chunks around it and the
 // bit sets are shifted into pixel order afterwards; a chunk that is not wholly inside its stack is read byte by byte behind bounds.
 #include "daam_ctx.h"
+#include "daam_epilogue.h"
 
 namespace daam {
 
@@ -20,31 +21,6 @@ constexpr int kMmThreads = kMmWaves * 64;
 constexpr int kMmSlots = 4;                    // planes a wave loads at once: 64 planes = 8 waves x 2 groups of 4
 constexpr int kMmRowWords = kMmTile / 32 + 1;       // a plane's 32 words of one tile, padded: rows 4 apart fall into banks 4 apart
 constexpr int kMmWgPerCu = 2;
-
-// bit b of the result = byte b of the 16 is not zero.  Per dword: bit 7 of every byte = "byte != 0" (the carry out of the low seven
-// bits, or the byte's own bit 7), then one dot product with the weights 1, 2, 4, ... gathers the four of them.
-__device__ __forceinline__ uint32_t mm_nonzero(uint32_t x)
-{
-    return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
-}
-__device__ __forceinline__ uint32_t mm_bits16(uint4 v)
-{
-    uint32_t lo = __builtin_amdgcn_udot4(mm_nonzero(v.x), 0x08040201u, 0u, false);
-    lo = __builtin_amdgcn_udot4(mm_nonzero(v.y), 0x80402010u, lo, false);
-    uint32_t hi = __builtin_amdgcn_udot4(mm_nonzero(v.z), 0x08040201u, 0u, false);
-    hi = __builtin_amdgcn_udot4(mm_nonzero(v.w), 0x80402010u, hi, false);
-    return (lo >> 7) | (hi << 1);              // the sums are 128 x (8 bits)
-}
-
-// the same for a chunk that reaches outside [lo, hi): bytes outside count as zero and are not read
-__device__ __forceinline__ uint32_t mm_bits16_edge(const uint8_t* p, const uint8_t* lo, const uint8_t* hi)
-{
-    uint32_t bits = 0;
-#pragma unroll 1
-    for (int b = 0; b < 16; ++b)
-        if (p + b >= lo && p + b < hi && p[b] != 0) bits |= 1u << b;
-    return bits;
-}
 
 struct MmArgs {
     const uint8_t* a;
@@ -132,11 +108,11 @@ __global__ __launch_bounds__(kMmThreads) void mask_matrix_kernel(MmArgs g)
                 if (m < n_planes) {
                     const MmPlane pl = mm_plane(g, m, p0);
                     const uint8_t* p = pl.chunk0 + 16 * lane;
-                    uint32_t c = (p >= pl.lo && p + 16 <= pl.hi) ? mm_bits16(raw[s]) : mm_bits16_edge(p, pl.lo, pl.hi);
+                    uint32_t c = (p >= pl.lo && p + 16 <= pl.hi) ? mask_bits16(raw[s]) : mask_bits16_edge(p, pl.lo, pl.hi);
                     if (kShift && pl.shift) {
                         uint32_t next = __shfl_down(c, 1, 64);
                         if (lane == 63)
-                            next = (p + 16 >= pl.lo && p + 32 <= pl.hi) ? mm_bits16(extra[s]) : mm_bits16_edge(p + 16, pl.lo, pl.hi);
+                            next = (p + 16 >= pl.lo && p + 32 <= pl.hi) ? mask_bits16(extra[s]) : mask_bits16_edge(p + 16, pl.lo, pl.hi);
                         c = ((c | (next << 16)) >> pl.shift) & 0xffffu;
                     }
                     rows[pl.row * kMmRowWords * 2 + lane] = (uint16_t)(c & valid);
@@ -224,7 +200,5 @@ int daam_mask_overlap_matrix(const uint8_t* a, int n_a, const uint8_t* b, int n_
         hipLaunchKernelGGL(mask_matrix_kernel<false>, dim3(grid), dim3(kMmThreads), 0, s, g);
     else
         hipLaunchKernelGGL(mask_matrix_kernel<true>, dim3(grid), dim3(kMmThreads), 0, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, "mask matrix launch: %s", hipGetErrorString(e));
-    return 0;
+    return launched("mask matrix");
 }

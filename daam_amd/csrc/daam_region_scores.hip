@@ -3,9 +3,9 @@
 // so sum_{p set in mask m} E_t[p] = sum_ij F[m][i][j] maps[t][i][j] with F[m] = the mask pulled back through the transpose of the
 // resize (its "footprint" on the map's own h x w grid):
 //   * region_tables_kernel    : per output row y and column x the first cell its four taps reach and their four weights, clamped taps
-//                               folded onto the edge cell (cubic_coeffs' operation order); zeroes `area`.  Once per call, for all masks.
+//                               folded onto the edge cell (cubic_taps of daam_epilogue.h); zeroes `area`.  Once per call, for all masks.
 //   * region_footprint_kernel : a workgroup takes one mask and a band of <= 32 output rows: the band's bytes -> a bit set in LDS (aligned
-//                               16-byte loads, bytes at the ends of the stack behind bounds) and the integer area; x pass: thread (row,
+//                               16-byte loads, bytes at the ends of the stack behind bounds: mask_bits16[_edge] of daam_epilogue.h) and the integer area; x pass: thread (row,
 //                               cell j) adds the weights of the row's set pixels that reach j, in ascending x; y pass: thread (cell i, j)
 //                               adds weight x row sum over the band's rows in ascending y -> the band's partial, in a window of cell rows
 //   * region_combine_kernel   : footprint[m][i][j] = the partials of the bands that reach i, in ascending band order
@@ -15,6 +15,7 @@
 // the plane starts in memory, nor on the other masks of the call.  Every product and sum is rounded on its own (contraction off): the
 // float64 oracle of tests/_region_domain.py counts the roundings on a term's path.
 #include "daam_ctx.h"
+#include "daam_epilogue.h"
 
 #include <cmath>
 
@@ -44,18 +45,6 @@ struct RsTables {              // device scratch, laid out by rs_tables()
     int* bx;                   // [W]
     float* part;               // [n_masks][n_bands][win][w]
 };
-
-__device__ __forceinline__ void rs_cubic_coeffs(float t, float w[4]) {
-#pragma clang fp contract(off)
-    const float A = -0.75f;
-    const float x0 = t + 1.0f;
-    w[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
-    w[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
-    const float u = 1.0f - t;
-    w[2] = ((A + 2.0f) * u - (A + 3.0f)) * u * u + 1.0f;
-    const float x3 = u + 1.0f;
-    w[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
-}
 
 // The output indices [lo, hi) that can reach source cell j of n from an axis of N outputs: a superset of {x : b[x] <= j <= b[x] + 3}
 // in integers (src = (n / N)(x + 0.5) - 0.5 in [j - 2, j + 2); the edge cells also take what is clamped onto them).  The passes test
@@ -87,16 +76,13 @@ __global__ __launch_bounds__(kRsThreads) void region_tables_kernel(RsGeom g, RsT
         gw[0] = 1.0f; gw[1] = 0.0f; gw[2] = 0.0f; gw[3] = 0.0f;
         return;
     }
-    const float sc = (float)n_in / (float)n_out;
-    const float src = sc * ((float)o + 0.5f) - 0.5f;
-    const float f = floorf(src);
     float wt[4];
-    rs_cubic_coeffs(src - f, wt);
-    const int base = min(max((int)f - 1, 0), n_in - 1);
+    const int first = cubic_taps((float)n_in / (float)n_out, o, wt);
+    const int base = min(max(first, 0), n_in - 1);
     float fold[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
-        const int k = min(max((int)f - 1 + a, 0), n_in - 1) - base;         // 0 .. 3: the clamp is monotone
+        const int k = min(max(first + a, 0), n_in - 1) - base;               // 0 .. 3: the clamp is monotone
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (q == k) fold[q] = fold[q] + wt[a];
@@ -104,28 +90,6 @@ __global__ __launch_bounds__(kRsThreads) void region_tables_kernel(RsGeom g, RsT
     *gb = base;
 #pragma unroll
     for (int q = 0; q < 4; ++q) gw[q] = fold[q];
-}
-
-// bit b = byte b of the 16 is not zero (the arithmetic of mm_nonzero / mm_bits16 in daam_mask_matrix.hip)
-__device__ __forceinline__ uint32_t rs_nonzero(uint32_t x)
-{
-    return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
-}
-__device__ __forceinline__ uint32_t rs_bits16(uint4 v)
-{
-    uint32_t lo = __builtin_amdgcn_udot4(rs_nonzero(v.x), 0x08040201u, 0u, false);
-    lo = __builtin_amdgcn_udot4(rs_nonzero(v.y), 0x80402010u, lo, false);
-    uint32_t hi = __builtin_amdgcn_udot4(rs_nonzero(v.z), 0x08040201u, 0u, false);
-    hi = __builtin_amdgcn_udot4(rs_nonzero(v.w), 0x80402010u, hi, false);
-    return (lo >> 7) | (hi << 1);
-}
-__device__ __forceinline__ uint32_t rs_bits16_edge(const uint8_t* p, const uint8_t* lo, const uint8_t* hi)
-{
-    uint32_t bits = 0;
-#pragma unroll 1
-    for (int b = 0; b < 16; ++b)
-        if (p + b >= lo && p + b < hi && p[b] != 0) bits |= 1u << b;
-    return bits;
 }
 
 // grid (n_bands, n_masks)
@@ -166,8 +130,8 @@ __global__ __launch_bounds__(kRsThreads) void region_footprint_kernel(const uint
         uint16_t* halves = reinterpret_cast<uint16_t*>(bits);
         for (int c = tid; c < n_chunks; c += kRsThreads) {
             const uint8_t* p = chunk0 + 16 * (size_t)c;
-            const uint32_t b = (p >= stack_lo && p + 16 <= stack_hi) ? rs_bits16(*reinterpret_cast<const uint4*>(p))
-                                                                     : rs_bits16_edge(p, stack_lo, stack_hi);
+            const uint32_t b = (p >= stack_lo && p + 16 <= stack_hi) ? mask_bits16(*reinterpret_cast<const uint4*>(p))
+                                                                     : mask_bits16_edge(p, stack_lo, stack_hi);
             // the tile's own bytes are [shift, shift + n_px) of the chunks
             const int from = max(shift - 16 * c, 0), to = min(shift + n_px - 16 * c, 16);
             count += __popc(b & ((1u << to) - 1u) & ~((1u << from) - 1u));
@@ -269,9 +233,22 @@ __global__ __launch_bounds__(kRsThreads) void region_dot_kernel(const float* foo
         scores[((size_t)set * n_masks + m0 + tid) * rows + row] = (wave_sums[tid][0] + wave_sums[tid][1]) + (wave_sums[tid][2] + wave_sums[tid][3]);
 }
 
+// the limits both entry points share: the footprints' shape, and the map sets of a dot pass (its grid.y, grid.x)
+static bool rs_footprints_ok(int n_masks, int h, int w)
+{
+    return n_masks >= 1 && n_masks <= kRsMaxMasks && h >= 1 && h <= kRsMaxSide && w >= 1 && w <= kRsMaxSide;
+}
+static bool rs_sets_ok(int n_sets, int rows) { return n_sets >= 1 && n_sets <= kRsMaxSets && rows >= 1; }
+
+static void launch_dots(const float* footprint, int n_masks, const float* maps, int n_sets, int rows, int cells, float* scores, hipStream_t s)
+{
+    hipLaunchKernelGGL(region_dot_kernel, dim3(rows, n_sets, (n_masks + kRsDotMasks - 1) / kRsDotMasks), dim3(kRsThreads), 0, s, footprint,
+                       n_masks, maps, rows, cells, scores);
+}
+
 static bool rs_geometry(int n_masks, int H, int W, int h, int w, RsGeom& g)
 {
-    if (n_masks < 1 || n_masks > kRsMaxMasks || h < 1 || h > kRsMaxSide || w < 1 || w > kRsMaxSide) return false;
+    if (!rs_footprints_ok(n_masks, h, w)) return false;
     if (H < 1 || W < 1 || (long long)H * W >= (1ll << 31)) return false;
     g.H = H; g.W = W; g.h = h; g.w = w;
     g.band = W >= kRsTilePixels ? 1 : (kRsTilePixels / W < kRsBandRows ? kRsTilePixels / W : kRsBandRows);
@@ -316,7 +293,7 @@ int daam_region_scores(const uint8_t* masks, int n_masks, int H, int W, const fl
                     n_masks, H, W, h, w, kRsMaxMasks, kRsMaxSide);
     if (!masks || !footprint || !area || !workspace) return fail(DAAM_E_INVALID, "NULL argument");
     if ((maps == nullptr) != (scores == nullptr)) return fail(DAAM_E_INVALID, "maps and scores: both or neither");
-    if (maps && (n_sets < 1 || n_sets > kRsMaxSets || rows < 1)) return fail(DAAM_E_INVALID, "%d sets of %d rows", n_sets, rows);
+    if (maps && !rs_sets_ok(n_sets, rows)) return fail(DAAM_E_INVALID, "%d sets of %d rows", n_sets, rows);
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(DAAM_E_INVALID, "workspace is not 16-byte aligned");
     if ((long long)g.n_bands > 0x7fffffffll || ((long long)H + W + kRsThreads - 1) / kRsThreads > 0x7fffffffll)
         return fail(DAAM_E_INVALID, "bad mask size %d x %d", H, W);
@@ -328,22 +305,16 @@ int daam_region_scores(const uint8_t* masks, int n_masks, int H, int W, const fl
     hipLaunchKernelGGL(region_footprint_kernel, dim3(g.n_bands, n_masks), dim3(kRsThreads), 0, s, masks, n_masks, g, t, area);
     hipLaunchKernelGGL(region_combine_kernel, dim3((n_masks * h * w + kRsThreads - 1) / kRsThreads), dim3(kRsThreads), 0, s, n_masks, g, t,
                        footprint);
-    if (maps)
-        hipLaunchKernelGGL(region_dot_kernel, dim3(rows, n_sets, (n_masks + kRsDotMasks - 1) / kRsDotMasks), dim3(kRsThreads), 0, s, footprint, n_masks, maps, rows, h * w, scores);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, "region scores launch: %s", hipGetErrorString(e));
-    return 0;
+    if (maps) launch_dots(footprint, n_masks, maps, n_sets, rows, h * w, scores, s);
+    return launched("region scores");
 }
 
 int daam_region_dots(const float* footprint, int n_masks, const float* maps, int n_sets, int rows, int h, int w, float* scores, void* stream)
 {
     if (!footprint || !maps || !scores) return fail(DAAM_E_INVALID, "NULL argument");
-    if (n_masks < 1 || n_masks > kRsMaxMasks || h < 1 || h > kRsMaxSide || w < 1 || w > kRsMaxSide)
+    if (!rs_footprints_ok(n_masks, h, w))
         return fail(DAAM_E_INVALID, "%d footprints of %d x %d: 1..%d, 1 <= h, w <= %d", n_masks, h, w, kRsMaxMasks, kRsMaxSide);
-    if (n_sets < 1 || n_sets > kRsMaxSets || rows < 1) return fail(DAAM_E_INVALID, "%d sets of %d rows", n_sets, rows);
-    hipLaunchKernelGGL(region_dot_kernel, dim3(rows, n_sets, (n_masks + kRsDotMasks - 1) / kRsDotMasks), dim3(kRsThreads), 0, (hipStream_t)stream, footprint, n_masks, maps, rows,
-                       h * w, scores);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, "region dots launch: %s", hipGetErrorString(e));
-    return 0;
+    if (!rs_sets_ok(n_sets, rows)) return fail(DAAM_E_INVALID, "%d sets of %d rows", n_sets, rows);
+    launch_dots(footprint, n_masks, maps, n_sets, rows, h * w, scores, (hipStream_t)stream);
+    return launched("region dots");
 }

@@ -1,4 +1,4 @@
-// Body of word_expand_kernel / word_expand_rect_kernel (daam_kernels.hip): one thread per output pixel of the bicubic resize of a
+// Body of word_expand_kernel / word_expand_rect_kernel (daam_epilogue.hip): one thread per output pixel of the bicubic resize of a
 // word map [SRC_H][SRC_W] (<= 128x128 f32, L1/L2 resident) to [out_h][out_w], and the min / max of the result.  The including kernel
 // defines SRC_H and SRC_W (the square kernel: both its `side`) and has word_map, out, out_h, out_w and minmax as parameters.
 #pragma clang fp contract(off)
@@ -10,27 +10,18 @@
         float wy[4], wx[4];
         int iy[4], ix[4];
         {
-            const float sc = (float)SRC_H / (float)out_h;
-            const float src = sc * ((float)oy + 0.5f) - 0.5f;
-            const float f = floorf(src);
-            cubic_coeffs(src - f, wy);
-            for (int a = 0; a < 4; ++a) iy[a] = min(max((int)f - 1 + a, 0), SRC_H - 1);
+            const int first = cubic_taps((float)SRC_H / (float)out_h, oy, wy);
+            for (int a = 0; a < 4; ++a) iy[a] = min(max(first + a, 0), SRC_H - 1);
         }
         {
-            const float sc = (float)SRC_W / (float)out_w;
-            const float src = sc * ((float)ox + 0.5f) - 0.5f;
-            const float f = floorf(src);
-            cubic_coeffs(src - f, wx);
-            for (int a = 0; a < 4; ++a) ix[a] = min(max((int)f - 1 + a, 0), SRC_W - 1);
+            const int first = cubic_taps((float)SRC_W / (float)out_w, ox, wx);
+            for (int a = 0; a < 4; ++a) ix[a] = min(max(first + a, 0), SRC_W - 1);
         }
         if (SRC_H == out_h && SRC_W == out_w) {
             v = word_map[i];
         } else {
             float rows[4];
-            for (int a = 0; a < 4; ++a) {
-                const float* r = word_map + iy[a] * SRC_W;
-                rows[a] = r[ix[0]] * wx[0] + r[ix[1]] * wx[1] + r[ix[2]] * wx[2] + r[ix[3]] * wx[3];
-            }
+            for (int a = 0; a < 4; ++a) rows[a] = cubic_row(word_map + iy[a] * SRC_W, ix, wx);
             v = rows[0] * wy[0] + rows[1] * wy[1] + rows[2] * wy[2] + rows[3] * wy[3];
         }
         store_for_host(out + i, v);

@@ -1,16 +1,17 @@
 // daam_word_masks: the word maps of up to 32 words, their thresholded masks at image resolution and the label map ("which word
 // owns this pixel") in three launches, whatever the number of words -- the batched form of daam_word_heat_map[_rect] (kernels:
-// daam_kernels.hip, daam_word_expand_body.inc), whose values it reproduces bit for bit without ever writing an f32 plane at image
+// daam_epilogue.hip, daam_word_expand_body.inc), whose values it reproduces bit for bit without ever writing an f32 plane at image
 // resolution:
 //   * word_masks_mean_kernel   : every word's mean plane, and the +inf / -inf start of every word's min / max pair
 //   * word_masks_minmax_kernel : min / max of every word's bicubic resize (stores nothing at image resolution; not launched when
 //                                `absolute`)
 //   * word_masks_out_kernel    : the same resize again -> normalise -> compare -> u8 masks, running arg-max -> u8 labels
 // The two image-resolution kernels share expand_run(): a lane owns kRun consecutive x of one output row, computes its tap indices
-// and weights once and reuses them over all words.  The arithmetic is the text of daam_word_expand_body.inc and word_post_kernel
-// (contraction off, same operand order), restated here: those kernels' machine code stays what it was.
+// and weights once and reuses them over all words.  The arithmetic is that of daam_word_expand_body.inc and word_post_kernel
+// (contraction off, same operand order) through the same helpers of daam_epilogue.h: cubic_taps, cubic_row, enc / dec_ordered.
 // The source planes ([n_words, h, w] f32, <= 2 MB) are read through L1 / L2, not staged in LDS.
 #include "daam_ctx.h"
+#include "daam_epilogue.h"
 
 #include <cmath>
 
@@ -27,26 +28,6 @@ static_assert(kRun % 4 == 0 && kRun >= 4 && kRun <= 16, "a lane's run is whole d
 // word j owns the planes idx[begin[j] .. begin[j + 1])
 struct WordTable { int32_t n_words; int32_t begin[kMaxWords + 1]; int32_t idx[kMaxWordIdx]; };
 
-__device__ __forceinline__ int wm_enc_ordered(float f) {
-    const int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float wm_dec_ordered(int i) {
-    return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff);
-}
-
-__device__ __forceinline__ void wm_cubic_coeffs(float t, float w[4]) {
-#pragma clang fp contract(off)
-    const float A = -0.75f;
-    const float x0 = t + 1.0f;
-    w[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
-    w[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
-    const float u = 1.0f - t;
-    w[2] = ((A + 2.0f) * u - (A + 3.0f)) * u * u + 1.0f;
-    const float x3 = u + 1.0f;
-    w[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
-}
-
 // grid (ceil(plane / 256), n_words): block (b, j) writes 256 pixels of word j's mean plane (the sum order and the division of
 // word_mean_kernel); block (0, j) starts word j's min / max pair
 __global__ __launch_bounds__(256) void word_masks_mean_kernel(const float* maps, int plane, WordTable t, float* word_maps, float* minmax)
@@ -54,9 +35,9 @@ __global__ __launch_bounds__(256) void word_masks_mean_kernel(const float* maps,
     const int j = blockIdx.y;
     const int px = blockIdx.x * 256 + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        // order-preserving int encodings of +inf / -inf for the atomicMin / atomicMax of word_masks_minmax_kernel
-        reinterpret_cast<int*>(minmax)[2 * j] = 0x7f800000;
-        reinterpret_cast<int*>(minmax)[2 * j + 1] = (int)0x80000000 ^ 0x7fffffff ^ 0x7f800000;   // enc(-inf)
+        // the start of the atomicMin / atomicMax pair of word_masks_minmax_kernel
+        reinterpret_cast<int*>(minmax)[2 * j] = kEncPosInf;
+        reinterpret_cast<int*>(minmax)[2 * j + 1] = kEncNegInf;
     }
     if (px >= plane) return;
     const int b = t.begin[j], e = t.begin[j + 1];
@@ -85,20 +66,14 @@ __device__ __forceinline__ void wm_run_setup(WordRun& r, int src_h, int src_w, i
     r.oy = min(row, out_h - 1);
     r.identity = src_h == out_h && src_w == out_w;
     {
-        const float sc = (float)src_h / (float)out_h;
-        const float src = sc * ((float)r.oy + 0.5f) - 0.5f;
-        const float f = floorf(src);
-        wm_cubic_coeffs(src - f, r.wy);
-        for (int a = 0; a < 4; ++a) r.iy[a] = min(max((int)f - 1 + a, 0), src_h - 1);
+        const int first = cubic_taps((float)src_h / (float)out_h, r.oy, r.wy);
+        for (int a = 0; a < 4; ++a) r.iy[a] = min(max(first + a, 0), src_h - 1);
     }
     const float sc = (float)src_w / (float)out_w;
 #pragma unroll
     for (int k = 0; k < kRun; ++k) {
-        const int ox = min(r.x0 + k, out_w - 1);
-        const float src = sc * ((float)ox + 0.5f) - 0.5f;
-        const float f = floorf(src);
-        wm_cubic_coeffs(src - f, r.wx[k]);
-        for (int a = 0; a < 4; ++a) r.ix[k][a] = min(max((int)f - 1 + a, 0), src_w - 1);
+        const int first = cubic_taps(sc, min(r.x0 + k, out_w - 1), r.wx[k]);
+        for (int a = 0; a < 4; ++a) r.ix[k][a] = min(max(first + a, 0), src_w - 1);
     }
 }
 
@@ -114,10 +89,7 @@ __device__ __forceinline__ void expand_run(const WordRun& r, const float* word_m
 #pragma unroll
     for (int k = 0; k < kRun; ++k) {
         float rows[4];
-        for (int a = 0; a < 4; ++a) {
-            const float* p = word_map + r.iy[a] * src_w;
-            rows[a] = p[r.ix[k][0]] * r.wx[k][0] + p[r.ix[k][1]] * r.wx[k][1] + p[r.ix[k][2]] * r.wx[k][2] + p[r.ix[k][3]] * r.wx[k][3];
-        }
+        for (int a = 0; a < 4; ++a) rows[a] = cubic_row(word_map + r.iy[a] * src_w, r.ix[k], r.wx[k]);
         v[k] = rows[0] * r.wy[0] + rows[1] * r.wy[1] + rows[2] * r.wy[2] + rows[3] * r.wy[3];
     }
 }
@@ -145,8 +117,8 @@ __global__ __launch_bounds__(256) void word_masks_minmax_kernel(const float* wor
             hi = fmaxf(hi, __shfl_xor(hi, off, 64));
         }
         if ((threadIdx.x & 63) == 0) {
-            atomicMin(reinterpret_cast<int*>(minmax) + 2 * j, wm_enc_ordered(lo));
-            atomicMax(reinterpret_cast<int*>(minmax) + 2 * j + 1, wm_enc_ordered(hi));
+            atomicMin(reinterpret_cast<int*>(minmax) + 2 * j, enc_ordered(lo));
+            atomicMax(reinterpret_cast<int*>(minmax) + 2 * j + 1, enc_ordered(hi));
         }
     }
 }
@@ -186,8 +158,8 @@ __global__ __launch_bounds__(256) void word_masks_out_kernel(const float* word_m
         float v[kRun];
         expand_run(r, word_maps + (size_t)j * plane, src_w, out_w, v);
         if (!absolute) {
-            const float lo = wm_dec_ordered(reinterpret_cast<const int*>(minmax)[2 * j]);
-            const float hi = wm_dec_ordered(reinterpret_cast<const int*>(minmax)[2 * j + 1]);
+            const float lo = dec_ordered(reinterpret_cast<const int*>(minmax)[2 * j]);
+            const float hi = dec_ordered(reinterpret_cast<const int*>(minmax)[2 * j + 1]);
 #pragma unroll
             for (int k = 0; k < kRun; ++k) v[k] = (v[k] - lo) / (hi - lo + 1e-8f);
         }
@@ -244,7 +216,5 @@ int daam_word_masks(const float* maps, int rows, int h, int w, const int32_t* id
         hipLaunchKernelGGL(word_masks_out_kernel, dim3((runs + 255) / 256), dim3(256), 0, s, word_maps, n_words, h, w, out_h, out_w,
                            workspace, absolute, threshold, masks, labels);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail((int)e, "word masks launch: %s", hipGetErrorString(e));
-    return 0;
+    return launched("word masks");
 }
