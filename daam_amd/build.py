@@ -8,7 +8,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ['daam_api.hip', 'daam_tap_api.hip', 'daam_finalize_api.hip', 'daam_kernels.hip', 'daam_tap_mfma.hip', 'daam_tap_d64.hip', 'daam_tap_wide.hip', 'daam_tap_chunk.hip', 'daam_tap_slab.hip', 'daam_tap_pair.hip', 'daam_tap_walk.hip', 'daam_attend_d64.hip', 'daam_finalize.hip', 'daam_finalize_pipe.hip', 'daam_fin_bins.hip', 'daam_finalize_rect.hip', 'daam_epilogue.hip', 'daam_word_masks.hip', 'daam_mask_matrix.hip', 'daam_region_scores.hip']
-HEADERS = ['daam_types.h', 'daam_fin_bins.h', 'daam_fin_rect.h', 'daam_ctx.h', 'daam_tap_common.h', 'daam_tap16.h', 'daam_tap16_softmax.h', 'daam_tap_tile64.h', 'daam_tap_walk.h', 'daam_tap_rows.h', 'daam_epilogue.h', 'daam_tap_d64_body.inc', 'daam_finalize_pipe_asm_r16.inc', 'daam_finalize_pipe_asm_bf16.inc', 'daam_finalize_pipe_asm_f32.inc',
+HEADERS = ['daam_types.h', 'daam_elem.h', 'daam_finalize.h', 'daam_fin_bins.h', 'daam_fin_rect.h', 'daam_ctx.h', 'daam_tap_common.h', 'daam_tap16.h', 'daam_tap16_softmax.h', 'daam_tap_tile64.h', 'daam_tap_walk.h', 'daam_tap_rows.h', 'daam_epilogue.h', 'daam_tap_d64_body.inc', 'daam_finalize_pipe_asm_r16.inc', 'daam_finalize_pipe_asm_bf16.inc', 'daam_finalize_pipe_asm_f32.inc',
            'daam_finalize_pipe_prefill_r16.inc', 'daam_finalize_pipe_prefill_f32.inc', 'daam_fin_kernel_body.inc', 'daam_fin_up_kernel_body.inc', 'daam_fin_down2_kernel_body.inc', 'daam_fin_pipe_kernel_body.inc', 'daam_word_expand_body.inc', os.path.join('..', '..', 'include', 'daam_hip.h')]
 OUT = os.path.join(HERE, 'libdaam_hip.so')
 

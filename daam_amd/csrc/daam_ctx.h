@@ -1,12 +1,12 @@
 // Host-only internals of libdaam_hip.so shared by the parts of the C ABI (daam_api.hip: context, layers, attend, profiling;
 // daam_tap_api.hip: the tap entry points; daam_finalize_api.hip: the finalize entry points; daam_epilogue.hip, daam_word_masks.hip,
-// daam_mask_matrix.hip, daam_region_scores.hip: the epilogue's, each beside its kernels): the kernel files' host launchers, the
-// context and its helpers.
+// daam_mask_matrix.hip, daam_region_scores.hip: the epilogue's, each beside its kernels): the tap and attend kernel files' host
+// launchers (the finalize's: daam_finalize.h, daam_fin_rect.h, daam_fin_bins.h), the context and its helpers.
 #pragma once
 #include "daam_types.h"
+#include "daam_finalize.h"
 #include "daam_fin_bins.h"
 #include "daam_fin_rect.h"
-#include "../../include/daam_hip.h"
 
 #include <deque>
 #include <string>
@@ -36,29 +36,12 @@ int tap_pair_tile_pixels();
 hipError_t launch_tap_pair(const TapLaunch&, int fast_exp, hipStream_t, int*, int*);
 
 hipError_t launch_tap_probs(const ProbsLaunch&, int, int, hipStream_t, int*, int*);
-hipError_t launch_finalize(const FinLaunch&, int, hipStream_t, int*, int*);
 hipError_t launch_upload(void* dst, const void* src_host_mapped, size_t bytes, void* zero, size_t zero_bytes, hipStream_t);
-hipError_t launch_finalize_up32_same(const FinLaunch& up, const FinLaunch& same, hipStream_t, int*);
-hipError_t launch_finalize_up32_pipe(const FinPipeLaunch&, int acc_dtype, hipStream_t, int*);
-int finalize_pipe_ring(int acc_dtype);
-hipError_t launch_finalize_same(const FinLaunch&, int, hipStream_t, int*);
-hipError_t launch_finalize_up(const FinLaunch&, int side, int, int mfma_ok, hipStream_t, int*);
-bool finalize_up_supported(int side, int out_side);
-bool finalize_down2_supported(int side, int out_side);
-hipError_t launch_finalize_down2(const FinLaunch&, int, hipStream_t, int*);
-hipError_t launch_zero_groups(float* out, size_t stride, int plane, const int* rows, int n_groups, hipStream_t);
-hipError_t launch_finalize_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*, int*);
-hipError_t launch_finalize_same_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
-hipError_t launch_finalize_up_grouped(const FinGroupLaunch&, int n_groups, int side, int acc_dtype, hipStream_t, int*);
-hipError_t launch_finalize_down2_grouped(const FinGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
-hipError_t launch_finalize_up32_pipe_grouped(const FinPipeGroupLaunch&, int n_groups, int acc_dtype, hipStream_t, int*);
 bool attend_d64_supported(int in_dtype, int head_dim, int tokens, const int64_t* strides, int n_strides, const void* const* ptrs, int n_ptrs);
 hipError_t launch_attend_d64(const AttendLaunch&, int in_dtype, int acc_dtype, int fast_exp, hipStream_t, int*, int*);
 hipError_t launch_clock_monitor(unsigned long long* samples, int n_samples, int period_us, hipStream_t);
 hipError_t launch_start_gate(const unsigned* counter, unsigned target, int timeout_us, unsigned* timeouts, hipStream_t);
 constexpr int kClockMaxSamples = 4096;
-hipError_t launch_finalize_bin_sum(const BinSumLaunch&, int acc_dtype, hipStream_t);
-int bin_sum_elems_per_tile(int acc_dtype);
 }  // namespace daam
 
 using namespace daam;

@@ -1,8 +1,7 @@
 // Window-range reduction of a time-binned context (daam_finalize_bins, include/daam_hip.h): the host side
-// (daam_finalize_api.hip) and the kernel (daam_fin_bins.hip) share this table.  Kept out of daam_types.h so that no existing
-// kernel's translation unit changes.
+// (daam_finalize_api.hip) and the kernel (daam_fin_bins.hip) share this table.
 #pragma once
-#include "daam_types.h"
+#include "daam_finalize.h"
 
 namespace daam {
 
@@ -28,5 +27,8 @@ struct BinSumLaunch {
 };
 
 constexpr int kBinSumThreads = 256;
+
+hipError_t launch_finalize_bin_sum(const BinSumLaunch& L, int dtype, hipStream_t stream);
+int bin_sum_elems_per_tile(int dtype);
 
 }  // namespace daam

@@ -65,16 +65,14 @@ __global__ __launch_bounds__(kBinSumThreads) void finalize_bin_sum_kernel(BinSum
     for (int i = 0; i < n; ++i) t.dst[e0 + i] = acc[i];
 }
 
-int bin_sum_elems_per_tile(int acc_dtype) { return kBinSumThreads * (acc_dtype == 1 /*DAAM_F32*/ ? 4 : 8); }
+int bin_sum_elems_per_tile(int dtype) { return kBinSumThreads * (dtype == DAAM_F32 ? BinVec<float>::V : BinVec<_Float16>::V); }
 
-hipError_t launch_finalize_bin_sum(const BinSumLaunch& L, int acc_dtype, hipStream_t stream)
+hipError_t launch_finalize_bin_sum(const BinSumLaunch& L, int dtype, hipStream_t stream)
 {
     if (L.n_tasks <= 0 || L.n_tiles <= 0) return hipSuccess;
-    const dim3 grid(L.n_tiles), block(kBinSumThreads);
-    if (acc_dtype == 1) hipLaunchKernelGGL(finalize_bin_sum_kernel<float>, grid, block, 0, stream, L);
-    else if (acc_dtype == 2) hipLaunchKernelGGL(finalize_bin_sum_kernel<bf16_t>, grid, block, 0, stream, L);
-    else hipLaunchKernelGGL(finalize_bin_sum_kernel<_Float16>, grid, block, 0, stream, L);
-    return hipGetLastError();
+    return fin_dispatch(dtype, [&](auto t) {
+        return fin_launch(finalize_bin_sum_kernel<typename decltype(t)::type>, dim3(L.n_tiles), kBinSumThreads, 0, stream, L);
+    });
 }
 
 }  // namespace daam

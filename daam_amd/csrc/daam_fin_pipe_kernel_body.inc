@@ -127,8 +127,8 @@
                 o1 = ident(a[j][1][1], sel[1], o1);
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
-                    accA0[v] = pipe_max_nonneg(o0[v], accA0[v]);
-                    accA1[v] = pipe_max_nonneg(o1[v], accA1[v]);
+                    accA0[v] = fin_max_nonneg(o0[v], accA0[v]);
+                    accA1[v] = fin_max_nonneg(o1[v], accA1[v]);
                 }
             }
         }

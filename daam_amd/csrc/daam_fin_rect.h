@@ -1,6 +1,6 @@
 // finalize_rect_kernel (daam_finalize_rect.hip): the launch descriptors of the finalize for planes and outputs of unequal sides.
 #pragma once
-#include "daam_types.h"
+#include "daam_finalize.h"
 
 namespace daam {
 
@@ -49,7 +49,8 @@ inline size_t fin_rect_lds_bytes(int out_h, int out_w, int plane_cap, int tmp_ca
 }
 constexpr size_t kFinRectMaxLds = 160 * 1024;   // LDS a gfx950 workgroup can have
 
-hipError_t launch_finalize_rect(const FinRectLaunch&, int tmp_cap, int acc_dtype, hipStream_t, int* grid, int* lds);
-hipError_t launch_finalize_rect_grouped(const FinRectGroupLaunch&, int n_groups, int tmp_cap, int acc_dtype, hipStream_t, int* grid, int* lds);
+// G == NULL: finalize_rect_kernel on L; otherwise L is G->L and finalize_rect_grouped_kernel runs on *G with grid z = n_groups
+hipError_t launch_finalize_rect(const FinRectLaunch& L, const FinRectGroupLaunch* G, int n_groups, int tmp_cap, int dtype,
+                                hipStream_t stream, int* grid_out, int* lds_out);
 
 }  // namespace daam

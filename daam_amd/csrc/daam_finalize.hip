@@ -1,9 +1,14 @@
-// Specialised finalize kernels (compute_global_heat_map, reference daam/trace.py:112-126) for the
-// map sizes real pipelines produce with a 64x64 target:
-//   * finalize_same_kernel : side == 64   -> clamp + mean only (pure streaming)
-//   * finalize_up_kernel   : side 32 / 16 -> bicubic x2 / x4 + clamp + mean
-// Everything else (x0.5 of SDXL-2048, 96x96 targets, odd sizes) takes the general kernel in
-// daam_kernels.hip.  All of them add their share of the mean into `out` with f32 atomics.
+// The finalize kernels for square planes and a square output (compute_global_heat_map, reference daam/trace.py:112-126) other
+// than the software-pipelined x2 kernel (daam_finalize_pipe.hip), and their launchers:
+//   * finalize_kernel           : any side -> any side, through LDS (daam_fin_kernel_body.inc)
+// and, for the map sizes real pipelines produce with a 64x64 target,
+//   * finalize_same_kernel      : side == 64   -> clamp + mean only (pure streaming)
+//   * finalize_up_kernel        : side 32 / 16 -> bicubic x2 / x4 + clamp + mean
+//   * finalize_down2_kernel     : side 128     -> bicubic x0.5 + clamp + mean
+//   * finalize_up32_mfma_kernel : x2 of fp16 planes on the matrix cores (round 2), finalize_up32_same_kernel: that and the same-size
+//                                 class in one launch
+// each with its *_grouped_kernel form (daam_finalize_groups: blockIdx.z = group), and zero_groups_kernel, which clears the
+// groups' outputs.  All of them add their share of the mean into `out` with f32 atomics.
 //
 // finalize_up_kernel: one WAVE walks a strided list of keys for one token.  Lane = output
 // column; the lane keeps its whole output column (64 rows) in registers across all its keys.
@@ -11,17 +16,47 @@
 // into a wave-private LDS tile, each lane gathers its 4 border-clamped x taps per source row
 // (x pass -> S registers), then the y pass runs on registers with compile-time row taps; weights
 // come from the host tables (bit-identical to torch's f32 coefficient arithmetic).
-#include "daam_types.h"
+#include "daam_finalize.h"
+#include "daam_elem.h"
 
 namespace daam {
 
 
+// ---------------------------------------------------------------------------------------
+// Finalize: grid (tokens, n_chunks).  Workgroup (t, c) walks keys c, c + n_chunks, ... :
+// plane -> LDS (f32) -> x pass -> y pass -> clamp -> += LDS out tile; one f32 atomicAdd per
+// output element per workgroup at the end (scaled by 1 / n_keys).
+// Separable in the same order as torch's upsample_bicubic2d (x on the 4 source rows, then y).
+// ---------------------------------------------------------------------------------------
+template <typename ACC_T>
+__global__ __launch_bounds__(256) void finalize_kernel(const FinLaunch L)
+{
+#include "daam_fin_kernel_body.inc"
+}
 
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+// daam_finalize_groups: blockIdx.z = group (FinGroupLaunch)
+template <typename ACC_T>
+__global__ __launch_bounds__(256) void finalize_grouped_kernel(const FinGroupLaunch G)
+{
+    if ((int)blockIdx.x >= G.g[blockIdx.z].rows) return;
+    const FinLaunch L = fin_group_view(G, blockIdx.z);
+#include "daam_fin_kernel_body.inc"
+}
+
+// daam_finalize_groups: clear rows [0, rows[g]) of every group's output (out + g * stride floats), plane floats per row
+struct ZeroGroups {
+    float* out;
+    int64_t stride;
+    int32_t plane;
+    int32_t rows[kFinMaxGroups];
+};
+__global__ __launch_bounds__(256) void zero_groups_kernel(const ZeroGroups Z)
+{
+    const int g = blockIdx.y;
+    const size_t n = (size_t)Z.rows[g] * Z.plane;
+    float* o = Z.out + (size_t)g * Z.stride;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) o[i] = 0.f;
+}
 
 template <typename T> struct Plane;
 template <> struct Plane<_Float16> {
@@ -36,7 +71,6 @@ template <> struct Plane<_Float16> {
         for (int i = 0; i < 8; ++i) a[i] += fmaxf((float)p[i], 0.f);
     }
 };
-typedef unsigned short ushort8 __attribute__((ext_vector_type(8)));
 template <> struct Plane<bf16_t> {                         // bf16 planes: widened by a shift
     static constexpr int kPerPiece = 8;
     using Piece = ushort8;
@@ -153,14 +187,6 @@ __device__ __forceinline__ float fin_sub_hi(float t, half2v h) {
     float r;
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(t));
     return r;
-}
-// max(a, b) for b >= 0 through the integer order of the bit patterns: one v_max_i32, no NaN canonicalisation in front
-// (fmaxf() costs a second v_max_f32), and -- unlike an inline-asm v_max_f32 -- visible to the compiler's hazard
-// recognizer, which pads the MFMA-result -> VALU-read wait states.  b >= 0: a negative a has its sign bit set and loses
-// as an integer, two non-negative floats order like their bit patterns.
-__device__ __forceinline__ float fin_max_nonneg(float a, float b) {
-    const int x = __float_as_int(a), y = __float_as_int(b);
-    return __int_as_float(x > y ? x : y);
 }
 // D = A B + C into NEW registers (C stays intact).  The builtin always comes out in the tied form (vdst = srcC) here, which
 // costs a 16-register copy of the running sums in front of every chain; the three-address form does the "copy" in the
@@ -426,14 +452,77 @@ __global__ __launch_bounds__(256, kFinWaves) void finalize_up32_same_kernel(cons
     }
 }
 
-static void same_grid(const FinLaunch& L, int acc_dtype, int* gx, int* gy)
+static void same_grid(const FinLaunch& L, int dtype, int* gx, int* gy)
 {
     const int plane = L.out_side * L.out_side;
-    const int per = acc_dtype == 1 ? 4 : 8;
+    const int per = dtype == DAAM_F32 ? Plane<float>::kPerPiece : Plane<_Float16>::kPerPiece;
     // waves never straddle token planes: per-token piece count rounded up to whole waves
     const int waves = L.tokens * ((plane / per + 63) / 64);
     *gx = (waves + 3) / 4;
     *gy = L.n_chunks;
+}
+
+// ---- launchers (daam_finalize.h: G == NULL the single-map kernel on L, else the grouped form on *G, grid z = n_groups) ----
+hipError_t launch_finalize(const FinLaunch& L, const FinGroupLaunch* G, int n_groups, int dtype, hipStream_t stream, int* grid_out,
+                           int* lds_out)
+{
+    const size_t lds = sizeof(float) * ((size_t)L.out_side * L.out_side + (size_t)L.max_side * L.max_side +
+                                        (size_t)L.max_side * L.out_side);
+    const dim3 grid(L.tokens, L.n_chunks, n_groups);
+    *grid_out = fin_workgroups(grid);
+    *lds_out = (int)lds;
+    return fin_dispatch<__half>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return G ? fin_launch(finalize_grouped_kernel<T>, grid, 256, lds, stream, *G) : fin_launch(finalize_kernel<T>, grid, 256, lds, stream, L);
+    });
+}
+
+hipError_t launch_finalize_same(const FinLaunch& L, const FinGroupLaunch* G, int n_groups, int dtype, hipStream_t stream, int* grid_out,
+                                int*)
+{
+    int gx = 0, gy = 0;
+    same_grid(L, dtype, &gx, &gy);
+    const dim3 grid(gx, gy, n_groups);
+    *grid_out = fin_workgroups(grid);
+    return fin_dispatch(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return G ? fin_launch(finalize_same_grouped_kernel<T>, grid, 256, 0, stream, *G) : fin_launch(finalize_same_kernel<T>, grid, 256, 0, stream, L);
+    });
+}
+
+bool finalize_up_supported(int side, int out_side) { return out_side == 64 && (side == 32 || side == 16); }
+bool finalize_down2_supported(int side, int out_side) { return out_side == 64 && side == 128; }
+
+hipError_t launch_finalize_down2(const FinLaunch& L, const FinGroupLaunch* G, int n_groups, int dtype, hipStream_t stream, int* grid_out,
+                                 int*)
+{
+    const dim3 grid(L.tokens, L.n_chunks, n_groups);
+    *grid_out = fin_workgroups(grid);
+    return fin_dispatch(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return G ? fin_launch(finalize_down2_grouped_kernel<T>, grid, 256, 0, stream, *G) : fin_launch(finalize_down2_kernel<T>, grid, 256, 0, stream, L);
+    });
+}
+
+template <int S>
+hipError_t launch_finalize_up(const FinLaunch& L, const FinGroupLaunch* G, int n_groups, int dtype, hipStream_t stream, int* grid_out,
+                              int*)
+{
+    const dim3 grid(L.tokens, L.n_chunks, n_groups);
+    *grid_out = fin_workgroups(grid);
+    return fin_dispatch(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return G ? fin_launch(finalize_up_grouped_kernel<T, S>, grid, 256, 0, stream, *G) : fin_launch(finalize_up_kernel<T, S>, grid, 256, 0, stream, L);
+    });
+}
+template FinClassLauncher launch_finalize_up<32>;
+template FinClassLauncher launch_finalize_up<16>;
+
+hipError_t launch_finalize_up32_mfma(const FinLaunch& L, hipStream_t stream, int* grid_out)
+{
+    const dim3 grid(L.tokens, L.n_chunks);
+    *grid_out = fin_workgroups(grid);
+    return fin_launch(finalize_up32_mfma_kernel, grid, 256, 0, stream, L);
 }
 
 // both fp16 classes of an SDXL-1024 finalize in one launch (up: x2 MFMA class, same: same-size class)
@@ -443,96 +532,26 @@ hipError_t launch_finalize_up32_same(const FinLaunch& up, const FinLaunch& same,
     P.up = up;
     P.same = same;
     P.up_blocks = up.tokens * up.n_chunks;
-    same_grid(same, 0, &P.same_gx, &P.same_gy);
+    same_grid(same, DAAM_F16, &P.same_gx, &P.same_gy);
     const int grid = P.up_blocks + P.same_gx * P.same_gy;
     *grid_out = grid;
-    hipLaunchKernelGGL(finalize_up32_same_kernel, dim3(grid), dim3(256), 0, stream, P);
-    return hipGetLastError();
+    return fin_launch(finalize_up32_same_kernel, dim3(grid), 256, 0, stream, P);
 }
 
-// ---------------------------------------------------------------------------------------
-hipError_t launch_finalize_same(const FinLaunch& L, int acc_dtype, hipStream_t stream, int* grid_out)
+hipError_t launch_zero_groups(float* out, size_t stride, int plane, const int* rows, int n_groups, hipStream_t stream)
 {
-    const int plane = L.out_side * L.out_side;
-    const int per = acc_dtype == 1 ? 4 : 8;
-    // waves never straddle token planes: per-token piece count rounded up to whole waves
-    const int waves = L.tokens * ((plane / per + 63) / 64);
-    dim3 grid((waves + 3) / 4, L.n_chunks);
-    *grid_out = grid.x * grid.y;
-    if (acc_dtype == 0) hipLaunchKernelGGL((finalize_same_kernel<_Float16>), grid, dim3(256), 0, stream, L);
-    else if (acc_dtype == 2) hipLaunchKernelGGL((finalize_same_kernel<bf16_t>), grid, dim3(256), 0, stream, L);
-    else hipLaunchKernelGGL((finalize_same_kernel<float>), grid, dim3(256), 0, stream, L);
-    return hipGetLastError();
-}
-
-bool finalize_up_supported(int side, int out_side) { return out_side == 64 && (side == 32 || side == 16); }
-bool finalize_down2_supported(int side, int out_side) { return out_side == 64 && side == 128; }
-
-hipError_t launch_finalize_down2(const FinLaunch& L, int acc_dtype, hipStream_t stream, int* grid_out)
-{
-    dim3 grid(L.tokens, L.n_chunks);
-    *grid_out = grid.x * grid.y;
-    if (acc_dtype == 0) hipLaunchKernelGGL((finalize_down2_kernel<_Float16>), grid, dim3(256), 0, stream, L);
-    else if (acc_dtype == 2) hipLaunchKernelGGL((finalize_down2_kernel<bf16_t>), grid, dim3(256), 0, stream, L);
-    else hipLaunchKernelGGL((finalize_down2_kernel<float>), grid, dim3(256), 0, stream, L);
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize_up(const FinLaunch& L, int side, int acc_dtype, int mfma_ok, hipStream_t stream, int* grid_out)
-{
-    dim3 grid(L.tokens, L.n_chunks);
-    *grid_out = grid.x * grid.y;
-    if (side == 32 && acc_dtype == 0 && mfma_ok && L.mfma_ops) {
-        hipLaunchKernelGGL(finalize_up32_mfma_kernel, grid, dim3(256), 0, stream, L);
-    } else if (side == 32) {
-        if (acc_dtype == 0) hipLaunchKernelGGL((finalize_up_kernel<_Float16, 32>), grid, dim3(256), 0, stream, L);
-        else if (acc_dtype == 2) hipLaunchKernelGGL((finalize_up_kernel<bf16_t, 32>), grid, dim3(256), 0, stream, L);
-        else hipLaunchKernelGGL((finalize_up_kernel<float, 32>), grid, dim3(256), 0, stream, L);
-    } else {
-        if (acc_dtype == 0) hipLaunchKernelGGL((finalize_up_kernel<_Float16, 16>), grid, dim3(256), 0, stream, L);
-        else if (acc_dtype == 2) hipLaunchKernelGGL((finalize_up_kernel<bf16_t, 16>), grid, dim3(256), 0, stream, L);
-        else hipLaunchKernelGGL((finalize_up_kernel<float, 16>), grid, dim3(256), 0, stream, L);
+    ZeroGroups Z;
+    Z.out = out;
+    Z.stride = (int64_t)stride;
+    Z.plane = plane;
+    int max_rows = 0;
+    for (int g = 0; g < kFinMaxGroups; ++g) {
+        Z.rows[g] = g < n_groups ? rows[g] : 0;
+        max_rows = max_rows > Z.rows[g] ? max_rows : Z.rows[g];
     }
-    return hipGetLastError();
-}
-
-// ---- daam_finalize_groups: the grouped forms (G.L.tokens = the largest row count of the groups; grid z = n_groups) ----
-hipError_t launch_finalize_same_grouped(const FinGroupLaunch& G, int n_groups, int acc_dtype, hipStream_t stream, int* grid_out)
-{
-    int gx = 0, gy = 0;
-    same_grid(G.L, acc_dtype, &gx, &gy);
-    dim3 grid(gx, gy, n_groups);
-    *grid_out = grid.x * grid.y * grid.z;
-    if (acc_dtype == 0) hipLaunchKernelGGL((finalize_same_grouped_kernel<_Float16>), grid, dim3(256), 0, stream, G);
-    else if (acc_dtype == 2) hipLaunchKernelGGL((finalize_same_grouped_kernel<bf16_t>), grid, dim3(256), 0, stream, G);
-    else hipLaunchKernelGGL((finalize_same_grouped_kernel<float>), grid, dim3(256), 0, stream, G);
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize_down2_grouped(const FinGroupLaunch& G, int n_groups, int acc_dtype, hipStream_t stream, int* grid_out)
-{
-    dim3 grid(G.L.tokens, G.L.n_chunks, n_groups);
-    *grid_out = grid.x * grid.y * grid.z;
-    if (acc_dtype == 0) hipLaunchKernelGGL((finalize_down2_grouped_kernel<_Float16>), grid, dim3(256), 0, stream, G);
-    else if (acc_dtype == 2) hipLaunchKernelGGL((finalize_down2_grouped_kernel<bf16_t>), grid, dim3(256), 0, stream, G);
-    else hipLaunchKernelGGL((finalize_down2_grouped_kernel<float>), grid, dim3(256), 0, stream, G);
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize_up_grouped(const FinGroupLaunch& G, int n_groups, int side, int acc_dtype, hipStream_t stream, int* grid_out)
-{
-    dim3 grid(G.L.tokens, G.L.n_chunks, n_groups);
-    *grid_out = grid.x * grid.y * grid.z;
-    if (side == 32) {
-        if (acc_dtype == 0) hipLaunchKernelGGL((finalize_up_grouped_kernel<_Float16, 32>), grid, dim3(256), 0, stream, G);
-        else if (acc_dtype == 2) hipLaunchKernelGGL((finalize_up_grouped_kernel<bf16_t, 32>), grid, dim3(256), 0, stream, G);
-        else hipLaunchKernelGGL((finalize_up_grouped_kernel<float, 32>), grid, dim3(256), 0, stream, G);
-    } else {
-        if (acc_dtype == 0) hipLaunchKernelGGL((finalize_up_grouped_kernel<_Float16, 16>), grid, dim3(256), 0, stream, G);
-        else if (acc_dtype == 2) hipLaunchKernelGGL((finalize_up_grouped_kernel<bf16_t, 16>), grid, dim3(256), 0, stream, G);
-        else hipLaunchKernelGGL((finalize_up_grouped_kernel<float, 16>), grid, dim3(256), 0, stream, G);
-    }
-    return hipGetLastError();
+    const size_t blocks = ((size_t)max_rows * plane + 1023) / 1024;
+    const int bx = blocks > 1024 ? 1024 : (int)blocks;
+    return fin_launch(zero_groups_kernel, dim3(bx > 0 ? bx : 1, n_groups), 256, 0, stream, Z);
 }
 
 }  // namespace daam

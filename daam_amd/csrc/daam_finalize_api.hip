@@ -284,6 +284,28 @@ FinPipeLaunch fin_pipe_launch(const DaamCtx* c, const FinPlan& P, int dtype, con
 
 std::string fin_name(const char* kernel, const std::string& what) { return std::string(kernel) + "<" + what + ">"; }
 
+// The class kernels that need nothing but their descriptor: what daam_last_kernels calls them -- stem + "_kernel" or
+// "_grouped_kernel" + targ + "<dtype>" -- and the launcher of both forms (daam_finalize.h).  The x2 class has three more kernels
+// (pipelined, round-2 MFMA, paired with the same-size class), which fin_single / fin_grouped pick ahead of this table.
+const struct FinClass {
+    const char* stem;
+    const char* targ;
+    FinClassLauncher* launch;
+} kFinClass[kFinClasses] = {
+    {"finalize_same", "", launch_finalize_same},
+    {"finalize_up", "<32>", launch_finalize_up<32>},
+    {"finalize_up", "<16>", launch_finalize_up<16>},
+    {"finalize", "", launch_finalize},
+    {"finalize_down2", "", launch_finalize_down2},
+};
+hipError_t fin_launch_class(int cls, const FinLaunch& L, const FinGroupLaunch* G, int n_groups, int dtype, hipStream_t s, int* grid,
+                            int* lds, std::string* name)
+{
+    const FinClass& k = kFinClass[cls];
+    *name = std::string(k.stem) + (G ? "_grouped_kernel" : "_kernel") + k.targ + "<" + dtype_name(dtype) + ">";
+    return k.launch(L, G, n_groups, dtype, s, grid, lds);
+}
+
 // Launches the kernel of every class in P.have: launch_class(cls, stream, &grid, &lds, &name) enqueues it and names it.
 // Several classes: the issue-bound x2 kernel keeps the caller's stream; every other class (HBM streams with few registers:
 // their waves fit beside the two heavy waves of a SIMD) goes to an auxiliary stream forked from / joined to the caller's by
@@ -434,13 +456,8 @@ int fin_rect(DaamCtx* c, Layer* layers, int n_layers, int dtype, const uint8_t* 
         G.g[g].out_off = (int64_t)((size_t)g * group_stride);
     }
     int grid = 0, lds_used = 0;
-    hipError_t e;
-    if (single) {
-        L.inv_n = G.g[0].inv_n;
-        e = launch_finalize_rect(L, tmp_cap, dtype, s, &grid, &lds_used);
-    } else {
-        e = launch_finalize_rect_grouped(G, n_groups, tmp_cap, dtype, s, &grid, &lds_used);
-    }
+    if (single) L.inv_n = G.g[0].inv_n;
+    const hipError_t e = launch_finalize_rect(L, single ? nullptr : &G, n_groups, tmp_cap, dtype, s, &grid, &lds_used);
     if (e != hipSuccess) return fail((int)e, "rectangular finalize launch: %s", hipGetErrorString(e));
     c->last_block[1] = 256;
     c->last_grid[1] = grid;
@@ -516,7 +533,7 @@ int fin_single(DaamCtx* c, const uint8_t* key_mask, const int32_t* key_group, in
             FinPipeLaunch PL = fin_pipe_launch(c, P, dtype, T.dev, out);
             PL.inv_n = inv_n;
             *name = fin_name("finalize_up32_pipe_kernel", dt + (P.fold_same ? " + same-size keys" : ""));
-            return launch_finalize_up32_pipe(PL, dtype, ks, grid);
+            return launch_finalize_up32_pipe(PL, nullptr, 1, dtype, ks, grid);
         }
         FinLaunch L = fin_class_launch(c, P, cls, T.dev, out);
         L.inv_n = inv_n;
@@ -531,17 +548,12 @@ int fin_single(DaamCtx* c, const uint8_t* key_mask, const int32_t* key_group, in
             hipError_t e = hipSuccess;
             for (size_t part = 0; part < up_parts.size() && e == hipSuccess; ++part) {
                 int g = 0;
-                e = launch_finalize_up(up_parts[part], 32, dtype, 1, ks, &g);
+                e = launch_finalize_up32_mfma(up_parts[part], ks, &g);
                 *grid += g;
             }
             return e;
         }
-        if (cls == 0) { *name = fin_name("finalize_same_kernel", dt); return launch_finalize_same(L, dtype, ks, grid); }
-        if (cls == 3) { *name = fin_name("finalize_kernel", dt); return launch_finalize(L, dtype, ks, grid, lds); }
-        if (cls == 4) { *name = fin_name("finalize_down2_kernel", dt); return launch_finalize_down2(L, dtype, ks, grid); }
-        const int side = P.keys(cls)[0].side;
-        *name = fin_name(side == 32 ? "finalize_up_kernel<32>" : "finalize_up_kernel<16>", dt);
-        return launch_finalize_up(L, side, dtype, 0, ks, grid);
+        return fin_launch_class(cls, L, nullptr, 1, dtype, ks, grid, lds, name);
     });
 }
 
@@ -594,18 +606,13 @@ int fin_grouped(DaamCtx* c, Layer* layers, int n_layers, int dtype, const int32_
             PG.L = fin_pipe_launch(c, P, dtype, T.dev, out);
             groups_of(1, PG.g);
             *name = fin_name("finalize_up32_pipe_grouped_kernel", dt + (P.fold_same ? " + same-size keys" : ""));
-            return launch_finalize_up32_pipe_grouped(PG, n_groups, dtype, ks, grid);
+            return launch_finalize_up32_pipe(PG.L, &PG, n_groups, dtype, ks, grid);
         }
         FinGroupLaunch G;
         memset(&G, 0, sizeof G);
         G.L = fin_class_launch(c, P, cls, T.dev, out);
         groups_of(cls, G.g);
-        if (cls == 0) { *name = fin_name("finalize_same_grouped_kernel", dt); return launch_finalize_same_grouped(G, n_groups, dtype, ks, grid); }
-        if (cls == 3) { *name = fin_name("finalize_grouped_kernel", dt); return launch_finalize_grouped(G, n_groups, dtype, ks, grid, lds); }
-        if (cls == 4) { *name = fin_name("finalize_down2_grouped_kernel", dt); return launch_finalize_down2_grouped(G, n_groups, dtype, ks, grid); }
-        const int side = P.keys(cls)[0].side;
-        *name = fin_name(side == 32 ? "finalize_up_grouped_kernel<32>" : "finalize_up_grouped_kernel<16>", dt);
-        return launch_finalize_up_grouped(G, n_groups, side, dtype, ks, grid);
+        return fin_launch_class(cls, G.L, &G, n_groups, dtype, ks, grid, lds, name);
     });
 }
 

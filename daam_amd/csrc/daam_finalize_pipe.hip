@@ -33,25 +33,14 @@
 //     VALU instructions per plane.  The 16-byte pieces of a 128-byte plane row sit XOR-swizzled in the ring (piece ^ ((row >> 1) & 7), done
 //     on the DMA's per-lane SOURCE address): the four ds_read_b128 of an A operand are conflict-free.  The folded same-size keys take the
 //     VALU (every lane loads the elements it owns in the C/D layout, acc += max(P, 0)).
-#include "daam_types.h"
-#include "../../include/daam_hip.h"       // DAAM_F16 / DAAM_F32 / DAAM_BF16
+#include "daam_finalize.h"
 
 namespace daam {
-
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kPipeRing = 16;              // planes per workgroup ring (the generated schedule is per depth: tools/gen_fin_pipe.py)
 constexpr int kSameBatch = 8;           // same-size keys whose pieces are fetched together (32 loads in flight per lane)
 constexpr int kSameBatchF32 = 4;        // ... of f32 planes (128 dword loads in flight per lane)
 constexpr int kPipePlane = 32 * 32 * 2; // bytes
-
-// max(a, b) for b >= 0 through the integer order of the bit patterns (daam_finalize.hip: fin_max_nonneg)
-__device__ __forceinline__ float pipe_max_nonneg(float a, float b) {
-    const int x = __float_as_int(a), y = __float_as_int(b);
-    return __int_as_float(x > y ? x : y);
-}
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
@@ -79,29 +68,20 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #include "daam_fin_pipe_kernel_body.inc"
 }
 
-// acc_dtype: dtype of the planes (DAAM_F16 / DAAM_BF16 / DAAM_F32); L.mfma_ops must be the operand set of that dtype (bf16 planes: Wx in bf16)
-hipError_t launch_finalize_up32_pipe(const FinPipeLaunch& L, int acc_dtype, hipStream_t stream, int* grid_out)
+// G == NULL: the single-map kernel on L; otherwise L is G->L and the grouped form runs on *G with grid z = n_groups
+hipError_t launch_finalize_up32_pipe(const FinPipeLaunch& L, const FinPipeGroupLaunch* G, int n_groups, int dtype, hipStream_t stream,
+                                     int* grid_out)
 {
-    dim3 grid(L.tokens, L.n_chunks);
-    *grid_out = grid.x * grid.y;
-    if (acc_dtype == DAAM_F32) hipLaunchKernelGGL(finalize_up32_pipe_kernel<DAAM_F32>, grid, dim3(128), 0, stream, L);
-    else if (acc_dtype == DAAM_BF16) hipLaunchKernelGGL(finalize_up32_pipe_kernel<DAAM_BF16>, grid, dim3(128), 0, stream, L);
-    else hipLaunchKernelGGL(finalize_up32_pipe_kernel<DAAM_F16>, grid, dim3(128), 0, stream, L);
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize_up32_pipe_grouped(const FinPipeGroupLaunch& G, int n_groups, int acc_dtype, hipStream_t stream, int* grid_out)
-{
-    dim3 grid(G.L.tokens, G.L.n_chunks, n_groups);
-    *grid_out = grid.x * grid.y * grid.z;
-    if (acc_dtype == DAAM_F32) hipLaunchKernelGGL(finalize_up32_pipe_grouped_kernel<DAAM_F32>, grid, dim3(128), 0, stream, G);
-    else if (acc_dtype == DAAM_BF16) hipLaunchKernelGGL(finalize_up32_pipe_grouped_kernel<DAAM_BF16>, grid, dim3(128), 0, stream, G);
-    else hipLaunchKernelGGL(finalize_up32_pipe_grouped_kernel<DAAM_F16>, grid, dim3(128), 0, stream, G);
-    return hipGetLastError();
+    const dim3 grid(L.tokens, L.n_chunks, n_groups);
+    *grid_out = fin_workgroups(grid);
+    return fin_dispatch(dtype, [&](auto t) {
+        constexpr int DT = decltype(t)::dt;
+        return G ? fin_launch(finalize_up32_pipe_grouped_kernel<DT>, grid, 128, 0, stream, *G) : fin_launch(finalize_up32_pipe_kernel<DT>, grid, 128, 0, stream, L);
+    });
 }
 
 // planes the ring prefetches past a chunk's last one (pointer-table padding): 16 planes of 2 KiB, 8 of 4 KiB
-int finalize_pipe_ring(int acc_dtype) { return acc_dtype == DAAM_F32 ? kPipeRing / 2 : kPipeRing; }
+int finalize_pipe_ring(int dtype) { return dtype == DAAM_F32 ? kPipeRing / 2 : kPipeRing; }
 
 }  // namespace daam
 

@@ -17,10 +17,6 @@ namespace daam {
 
 namespace {
 
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef unsigned short ushort8 __attribute__((ext_vector_type(8)));
-
 // a plane element type: its 16-byte piece, and the element as f32
 template <typename T> struct RectPlane;
 template <> struct RectPlane<_Float16> {
@@ -109,12 +105,6 @@ __device__ __forceinline__ void finalize_rect_body(const FinRectLaunch& L)
     for (int i = tid; i < on; i += 256) atomicAdd(out + i, outt[i] * L.inv_n);
 }
 
-template <typename K> hipError_t allow_lds(K kernel, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 }  // namespace
 
 template <typename ACC_T>
@@ -131,46 +121,18 @@ __global__ __launch_bounds__(256) void finalize_rect_grouped_kernel(const FinRec
     finalize_rect_body<ACC_T>(fin_rect_group_view(G, blockIdx.z));
 }
 
-hipError_t launch_finalize_rect(const FinRectLaunch& L, int tmp_cap, int acc_dtype, hipStream_t stream, int* grid_out, int* lds_out)
+hipError_t launch_finalize_rect(const FinRectLaunch& L, const FinRectGroupLaunch* G, int n_groups, int tmp_cap, int dtype,
+                                hipStream_t stream, int* grid_out, int* lds_out)
 {
     const size_t lds = fin_rect_lds_bytes(L.out_h, L.out_w, L.plane_cap, tmp_cap);
     if (lds > kFinRectMaxLds) return hipErrorInvalidValue;     // (the caller has checked: never a launch that cannot fit)
-    const dim3 grid(L.tokens, L.n_chunks);
-    *grid_out = grid.x * grid.y;
-    *lds_out = (int)lds;
-    hipError_t e;
-#define DAAM_LAUNCH(T)                                                                   \
-    do {                                                                                 \
-        if ((e = allow_lds(finalize_rect_kernel<T>, lds)) != hipSuccess) return e;       \
-        hipLaunchKernelGGL((finalize_rect_kernel<T>), grid, dim3(256), lds, stream, L);  \
-    } while (0)
-    if (acc_dtype == 0) DAAM_LAUNCH(_Float16);
-    else if (acc_dtype == 2) DAAM_LAUNCH(bf16_t);
-    else DAAM_LAUNCH(float);
-#undef DAAM_LAUNCH
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize_rect_grouped(const FinRectGroupLaunch& G, int n_groups, int tmp_cap, int acc_dtype, hipStream_t stream,
-                                        int* grid_out, int* lds_out)
-{
-    const FinRectLaunch& L = G.L;
-    const size_t lds = fin_rect_lds_bytes(L.out_h, L.out_w, L.plane_cap, tmp_cap);
-    if (lds > kFinRectMaxLds) return hipErrorInvalidValue;
     const dim3 grid(L.tokens, L.n_chunks, n_groups);
-    *grid_out = grid.x * grid.y * grid.z;
+    *grid_out = fin_workgroups(grid);
     *lds_out = (int)lds;
-    hipError_t e;
-#define DAAM_LAUNCH(T)                                                                           \
-    do {                                                                                         \
-        if ((e = allow_lds(finalize_rect_grouped_kernel<T>, lds)) != hipSuccess) return e;       \
-        hipLaunchKernelGGL((finalize_rect_grouped_kernel<T>), grid, dim3(256), lds, stream, G);  \
-    } while (0)
-    if (acc_dtype == 0) DAAM_LAUNCH(_Float16);
-    else if (acc_dtype == 2) DAAM_LAUNCH(bf16_t);
-    else DAAM_LAUNCH(float);
-#undef DAAM_LAUNCH
-    return hipGetLastError();
+    return fin_dispatch(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return G ? fin_launch(finalize_rect_grouped_kernel<T>, grid, 256, lds, stream, *G) : fin_launch(finalize_rect_kernel<T>, grid, 256, lds, stream, L);
+    });
 }
 
 }  // namespace daam

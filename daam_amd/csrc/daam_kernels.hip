@@ -1,37 +1,13 @@
-// Baseline (any head_dim, any dtype combo) kernels of the DAAM heat-map extraction path for
-// gfx950.  The fp16 MFMA tap lives in daam_tap_mfma.hip; this file holds
+// Baseline (any head_dim, any dtype combo) tap kernels of the DAAM heat-map extraction path for
+// gfx950, and the launches' plumbing.  The fp16 MFMA tap lives in daam_tap_mfma.hip; this file holds
 //   * tap_generic_kernel   : softmax(scale q k^T) -> conditional half -> running sums
 //                            (reference daam/trace.py:276-294 + daam/heatmap.py:153-156)
 //   * tap_probs_kernel     : the same accumulate from materialised probabilities
-//   * finalize_kernel      : bicubic -> clamp -> mean over keys (daam/trace.py:112-126), and its grouped form
-//   * upload_kernel, zero_groups_kernel, clock_monitor_kernel, start_gate_kernel : the launches' plumbing
-// (normalise, word maps and the pair overlap: daam_epilogue.hip)
-#include "daam_types.h"
+//   * upload_kernel (the tap's and the finalize's device tables), clock_monitor_kernel, start_gate_kernel
+// (every finalize kernel: daam_finalize*.hip, daam_fin_bins.hip; normalise, word maps and the pair overlap: daam_epilogue.hip)
+#include "daam_elem.h"
 
 namespace daam {
-
-// ---------------------------------------------------------------------------------------
-// dtype helpers.  "round_to<T>" reproduces the rounding point of a tensor that the reference
-// pipeline materialises in dtype T (fp16 logits / probabilities), returning the value as f32.
-// ---------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ float ld(const T* p);
-template <> __device__ __forceinline__ float ld<__half>(const __half* p) { return __half2float(*p); }
-template <> __device__ __forceinline__ float ld<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ld<bf16_t>(const bf16_t* p) { return bf16_to_f32(*p); }
-
-template <typename T> __device__ __forceinline__ float round_to(float x);
-template <> __device__ __forceinline__ float round_to<__half>(float x) { return __half2float(__float2half_rn(x)); }
-template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
-template <> __device__ __forceinline__ float round_to<bf16_t>(float x) { return bf16_to_f32(f32_to_bf16(x)); }
-
-// acc = acc + x in the accumulator dtype.  For fp16 the f32 add of two fp16 values followed by
-// one RNE rounding is the correctly rounded fp16 add (24 >= 2*11+2 bits), i.e. exactly what
-// torch's / numpy's half add does (heatmap.py:156).
-template <typename T> __device__ __forceinline__ void st(T* p, float v);
-template <> __device__ __forceinline__ void st<__half>(__half* p, float v) { *p = __float2half_rn(v); }
-template <> __device__ __forceinline__ void st<float>(float* p, float v) { *p = v; }
-// bf16: f32 add of two bf16 values + one RNE rounding = the correctly rounded bf16 add (24 >= 2*8+2 bits)
-template <> __device__ __forceinline__ void st<bf16_t>(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 
 // XCD-aware block remap: hardware places block b on XCD b % 8; give each XCD a contiguous
 // range of logical tiles so the tiles of one (layer, head) - which share K - share an L2.
@@ -188,27 +164,6 @@ __global__ __launch_bounds__(256) void tap_probs_kernel(const ProbsLaunch L)
     }
 }
 
-// ---------------------------------------------------------------------------------------
-// Finalize: grid (tokens, n_chunks).  Workgroup (t, c) walks keys c, c + n_chunks, ... :
-// plane -> LDS (f32) -> x pass -> y pass -> clamp -> += LDS out tile; one f32 atomicAdd per
-// output element per workgroup at the end (scaled by 1 / n_keys).
-// Separable in the same order as torch's upsample_bicubic2d (x on the 4 source rows, then y).
-// ---------------------------------------------------------------------------------------
-template <typename ACC_T>
-__global__ __launch_bounds__(256) void finalize_kernel(const FinLaunch L)
-{
-#include "daam_fin_kernel_body.inc"
-}
-
-// daam_finalize_groups: blockIdx.z = group (daam_types.h FinGroupLaunch)
-template <typename ACC_T>
-__global__ __launch_bounds__(256) void finalize_grouped_kernel(const FinGroupLaunch G)
-{
-    if ((int)blockIdx.x >= G.g[blockIdx.z].rows) return;
-    const FinLaunch L = fin_group_view(G, blockIdx.z);
-#include "daam_fin_kernel_body.inc"
-}
-
 // per-launch device tables: pinned host (device-mapped) -> device twin, in stream order on the
 // compute queue (16 bytes per thread; tables are a few tens of KB)
 __global__ __launch_bounds__(256) void upload_kernel(float4* dst, const float4* src, int n16, float4* zero, int z16)
@@ -230,30 +185,9 @@ hipError_t launch_upload(void* dst, const void* src_host_mapped, size_t bytes, v
     return hipGetLastError();
 }
 
-// daam_finalize_groups: clear rows [0, rows[g]) of every group's output (out + g * stride floats), plane floats per row
-struct ZeroGroups {
-    float* out;
-    int64_t stride;
-    int32_t plane;
-    int32_t rows[kFinMaxGroups];
-};
-__global__ __launch_bounds__(256) void zero_groups_kernel(const ZeroGroups Z)
-{
-    const int g = blockIdx.y;
-    const size_t n = (size_t)Z.rows[g] * Z.plane;
-    float* o = Z.out + (size_t)g * Z.stride;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) o[i] = 0.f;
-}
-
 // ---------------------------------------------------------------------------------------
 // host-callable launchers (called from daam_api.hip / daam_tap_api.hip)
 // ---------------------------------------------------------------------------------------
-template <typename K> static hipError_t allow_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)bytes);
-}
-
 hipError_t launch_tap_generic(const TapLaunch& L, int in_dtype, int acc_dtype, int max_d, hipStream_t stream,
                               int* grid_out, int* lds_out)
 {
@@ -264,7 +198,9 @@ hipError_t launch_tap_generic(const TapLaunch& L, int in_dtype, int acc_dtype, i
     hipError_t e;
 #define DAAM_LAUNCH(IN, ACC)                                                            \
     do {                                                                                \
-        if ((e = allow_lds(tap_generic_kernel<IN, ACC>, lds)) != hipSuccess) return e;  \
+        if (lds > 64 * 1024 &&                                                          \
+            (e = hipFuncSetAttribute(reinterpret_cast<const void*>(tap_generic_kernel<IN, ACC>),                     \
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e; \
         hipLaunchKernelGGL((tap_generic_kernel<IN, ACC>), dim3(grid), dim3(256), lds, stream, L); \
     } while (0)
     if (in_dtype == 0 && acc_dtype == 0) DAAM_LAUNCH(__half, __half);
@@ -296,65 +232,6 @@ hipError_t launch_tap_probs(const ProbsLaunch& L, int in_dtype, int acc_dtype, h
         hipLaunchKernelGGL((tap_probs_kernel<float, float>), dim3(grid), dim3(256), lds, stream, L);
     else
         return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize(const FinLaunch& L, int acc_dtype, hipStream_t stream, int* grid_out, int* lds_out)
-{
-    const size_t lds = sizeof(float) * ((size_t)L.out_side * L.out_side + (size_t)L.max_side * L.max_side +
-                                        (size_t)L.max_side * L.out_side);
-    *grid_out = L.tokens * L.n_chunks;
-    *lds_out = (int)lds;
-    hipError_t e;
-    if (acc_dtype == 0) {
-        if ((e = allow_lds(finalize_kernel<__half>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((finalize_kernel<__half>), dim3(L.tokens, L.n_chunks), dim3(256), lds, stream, L);
-    } else if (acc_dtype == 2) {
-        if ((e = allow_lds(finalize_kernel<bf16_t>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((finalize_kernel<bf16_t>), dim3(L.tokens, L.n_chunks), dim3(256), lds, stream, L);
-    } else {
-        if ((e = allow_lds(finalize_kernel<float>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((finalize_kernel<float>), dim3(L.tokens, L.n_chunks), dim3(256), lds, stream, L);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_zero_groups(float* out, size_t stride, int plane, const int* rows, int n_groups, hipStream_t stream)
-{
-    ZeroGroups Z;
-    Z.out = out;
-    Z.stride = (int64_t)stride;
-    Z.plane = plane;
-    int max_rows = 0;
-    for (int g = 0; g < kFinMaxGroups; ++g) {
-        Z.rows[g] = g < n_groups ? rows[g] : 0;
-        max_rows = max_rows > Z.rows[g] ? max_rows : Z.rows[g];
-    }
-    const size_t blocks = ((size_t)max_rows * plane + 1023) / 1024;
-    const int bx = blocks > 1024 ? 1024 : (int)blocks;
-    hipLaunchKernelGGL(zero_groups_kernel, dim3(bx > 0 ? bx : 1, n_groups), dim3(256), 0, stream, Z);
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize_grouped(const FinGroupLaunch& G, int n_groups, int acc_dtype, hipStream_t stream, int* grid_out, int* lds_out)
-{
-    const FinLaunch& L = G.L;
-    const size_t lds = sizeof(float) * ((size_t)L.out_side * L.out_side + (size_t)L.max_side * L.max_side +
-                                        (size_t)L.max_side * L.out_side);
-    const dim3 grid(L.tokens, L.n_chunks, n_groups);
-    *grid_out = grid.x * grid.y * grid.z;
-    *lds_out = (int)lds;
-    hipError_t e;
-    if (acc_dtype == 0) {
-        if ((e = allow_lds(finalize_grouped_kernel<__half>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((finalize_grouped_kernel<__half>), grid, dim3(256), lds, stream, G);
-    } else if (acc_dtype == 2) {
-        if ((e = allow_lds(finalize_grouped_kernel<bf16_t>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((finalize_grouped_kernel<bf16_t>), grid, dim3(256), lds, stream, G);
-    } else {
-        if ((e = allow_lds(finalize_grouped_kernel<float>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((finalize_grouped_kernel<float>), grid, dim3(256), lds, stream, G);
-    }
     return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-// Device-visible tables shared by the host API (daam_api.hip, daam_tap_api.hip, daam_finalize_api.hip) and the kernels.
+// Device-visible tables shared by the host API (daam_api.hip, daam_tap_api.hip) and the tap / attend kernels; the finalize's are in
+// daam_finalize.h.
 // gfx950 only; no other architecture is targeted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -93,81 +94,6 @@ struct AttendLaunch {       // daam_attend: one cross-attention call, every (bat
     int64_t v_sb, v_sh, v_st;
     int64_t o_sb, o_sh, o_sp;
 };
-
-constexpr int kFinMaxChunks = 31;
-
-// One selected (layer, head) key of a finalize launch.
-struct FinKey {
-    const void* base;       // plane of token 0: [tokens, side, side] follows
-    int32_t side;
-    int32_t tab;            // bicubic table index (-1: side == out_side, identity)
-};
-
-struct FinLaunch {
-    const FinKey* keys;
-    const int16_t* tab_idx; // [n_tabs][out_side][4] border-clamped tap indices
-    const float* tab_w;     // [n_tabs][out_side][4] weights (A = -0.75)
-    float* out;             // [tokens, out_side, out_side]
-    int32_t n_keys;
-    int32_t n_chunks;
-    int32_t tokens;
-    int32_t out_side;
-    float inv_n;
-    int32_t max_side;       // largest non-identity side among the keys (LDS carve-up)
-    const void* mfma_ops;   // x2 MFMA finalize: [2 nt][64 lanes][6] 16-byte operand pieces (host-built), or NULL
-    // x2 MFMA finalize: chunk c covers the keys [chunk_begin[c], chunk_begin[c + 1]) (even boundaries; its two key lanes take
-    // them alternately); see finalize_chunk_ranges() in daam_finalize_api.hip.
-    int16_t chunk_begin[kFinMaxChunks + 1];
-};
-
-// x2 finalize, software-pipelined kernel (daam_finalize_pipe.hip): workgroup (token, chunk) walks the plane pointers
-// key_ptrs[chunk * ptr_stride + 0 .. nk_pad) (token 0's plane of each key, or the all-zero plane as padding; nk_pad even, >= 4,
-// the same for every chunk; the ring prefetches kPipeRing + 1 entries past nk_pad, which must be valid pointers too).
-struct FinPipeLaunch {
-    const unsigned long long* key_ptrs;
-    const unsigned long long* same_ptrs;   // [n_chunks][same_per] planes of token 0 of the 64 x 64 keys folded in (0 = padding), or NULL
-    int32_t same_per;
-    const void* mfma_ops;   // as FinLaunch::mfma_ops
-    float* out;             // [tokens, 64, 64]
-    int32_t n_chunks;
-    int32_t nk_pad;
-    int32_t ptr_stride;     // entries per chunk in key_ptrs
-    int32_t tokens;
-    float inv_n;
-};
-
-// daam_finalize_groups: one launch per class for N global heat maps.  blockIdx.z = group; the group fixes its key range
-// (keys of one group are contiguous in the class's FinKey array / pointer tables), the row limit, 1/N and the output base.
-// Workgroups with blockIdx.x past the group's rows exit at once (grid x is the largest row count).
-constexpr int kFinMaxGroups = 64;
-struct FinGroup {
-    int32_t key_begin;      // first FinKey of the group in the class's array (general / same / up / x0.5 kernels)
-    int32_t n_keys;
-    int32_t rows;           // token rows of this group's output
-    float inv_n;            // 1 / (keys of the group over every class)
-    int64_t out_off;        // floats from FinLaunch::out / FinPipeLaunch::out to the group's [rows, O, O]
-    int32_t ptr_off;        // pipelined x2 kernel: entries from key_ptrs / same_ptrs to the group's first chunk
-    int32_t same_off;
-};
-struct FinGroupLaunch {
-    FinLaunch L;            // shared fields; keys / n_keys / tokens / inv_n / out are per group
-    FinGroup g[kFinMaxGroups];
-};
-struct FinPipeGroupLaunch {
-    FinPipeLaunch L;
-    FinGroup g[kFinMaxGroups];
-};
-// the group's view of a grouped launch
-__host__ __device__ inline FinLaunch fin_group_view(const FinGroupLaunch& G, int g)
-{
-    FinLaunch L = G.L;
-    L.keys += G.g[g].key_begin;
-    L.n_keys = G.g[g].n_keys;
-    L.tokens = G.g[g].rows;
-    L.inv_n = G.g[g].inv_n;
-    L.out += G.g[g].out_off;
-    return L;
-}
 
 // bfloat16 storage type (no arithmetic): values cross to f32 by a shift, back by round-to-nearest-even
 struct bf16_t { uint16_t bits; };
