@@ -135,5 +135,47 @@ def check(rc: int) -> None:
         raise DaamError(rc, msg.decode() if msg else '')
 
 
+# ---- libdaam_analysis.so (C ABI: include/daam_analysis.h) -------------------------------------------------------------------------
+ANALYSIS_LIB_NAME = 'libdaam_analysis.so'
+ANALYSIS_LIB_PATH = os.environ.get('DAAM_ANALYSIS_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), ANALYSIS_LIB_NAME)
+ANALYSIS_ABI_VERSION = 1
+ANALYSIS_EXPORTS = ('daam_key_scores', 'daam_analysis_abi_version', 'daam_analysis_last_error')
+
+
+class KeyPlanes(Structure):
+    """``DaamKeyPlanes`` (include/daam_analysis.h), 32 bytes."""
+    _fields_ = [('base', c_void_p), ('win_stride', c_int64), ('h', c_int32), ('w', c_int32), ('n_win', c_int32), ('pad', c_int32)]
+
+
+_analysis = None
+
+
+def load_analysis() -> ctypes.CDLL:
+    """The head-analysis library; like ``load`` it has no fallback: missing or stale is an error."""
+    global _analysis
+    if _analysis is not None:
+        return _analysis
+    if not os.path.exists(ANALYSIS_LIB_PATH):
+        raise RuntimeError(f'{ANALYSIS_LIB_PATH} is missing: per-key scores have no fallback. Build it with `python -m daam_amd.build`.')
+    lib = ctypes.CDLL(ANALYSIS_LIB_PATH)
+    missing = [name for name in ANALYSIS_EXPORTS if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError(f'{ANALYSIS_LIB_PATH}: lacks {", ".join(missing)} (stale build); rebuild')
+    lib.daam_key_scores.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
+    lib.daam_key_scores.restype = c_int
+    lib.daam_analysis_abi_version.restype = c_int
+    lib.daam_analysis_last_error.restype = c_char_p
+    if lib.daam_analysis_abi_version() != ANALYSIS_ABI_VERSION:
+        raise RuntimeError(f'{ANALYSIS_LIB_PATH}: ABI version {lib.daam_analysis_abi_version()} != {ANALYSIS_ABI_VERSION}; rebuild')
+    _analysis = lib
+    return lib
+
+
+def check_analysis(rc: int) -> None:
+    if rc != 0:
+        msg = load_analysis().daam_analysis_last_error()
+        raise DaamError(rc, msg.decode() if msg else '')
+
+
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

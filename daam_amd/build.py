@@ -11,6 +11,12 @@ SOURCES = ['daam_api.hip', 'daam_tap_api.hip', 'daam_finalize_api.hip', 'daam_ke
 HEADERS = ['daam_types.h', 'daam_elem.h', 'daam_finalize.h', 'daam_fin_bins.h', 'daam_fin_rect.h', 'daam_ctx.h', 'daam_tap_common.h', 'daam_tap16.h', 'daam_tap16_softmax.h', 'daam_tap_tile64.h', 'daam_tap_walk.h', 'daam_tap_rows.h', 'daam_epilogue.h', 'daam_tap_d64_body.inc', 'daam_finalize_pipe_asm_r16.inc', 'daam_finalize_pipe_asm_bf16.inc', 'daam_finalize_pipe_asm_f32.inc',
            'daam_finalize_pipe_prefill_r16.inc', 'daam_finalize_pipe_prefill_f32.inc', 'daam_fin_kernel_body.inc', 'daam_fin_up_kernel_body.inc', 'daam_fin_down2_kernel_body.inc', 'daam_fin_pipe_kernel_body.inc', 'daam_word_expand_body.inc', os.path.join('..', '..', 'include', 'daam_hip.h')]
 OUT = os.path.join(HERE, 'libdaam_hip.so')
+# libdaam_analysis.so (include/daam_analysis.h): a second library with no context, kept out of SOURCES / HEADERS so that csrc_sha()
+# and the kernels of libdaam_hip.so stay what the committed profiles were measured on.  Its source reads the first library's headers.
+ANALYSIS_SOURCES = ['daam_key_scores.hip']
+ANALYSIS_HEADERS = ['daam_key_scores.h', 'daam_finalize.h', 'daam_epilogue.h', 'daam_elem.h', 'daam_types.h',
+                    os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_analysis.h')]
+ANALYSIS_OUT = os.path.join(HERE, 'libdaam_analysis.so')
 
 
 def csrc_sha() -> str:
@@ -89,6 +95,25 @@ def stale() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def analysis_stale() -> bool:
+    if not os.path.exists(ANALYSIS_OUT):
+        return True
+    t = os.path.getmtime(ANALYSIS_OUT)
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in ANALYSIS_SOURCES + ANALYSIS_HEADERS)
+
+
+def build_analysis(force: bool = False, verbose: bool = True) -> str:
+    """``libdaam_analysis.so``: one hipcc command (one source), when it is missing or older than what it is made of."""
+    if not force and not analysis_stale():
+        return ANALYSIS_OUT
+    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
+           *[os.path.join(HERE, 'csrc', f) for f in ANALYSIS_SOURCES], '-o', ANALYSIS_OUT]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return ANALYSIS_OUT
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -141,6 +166,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     ``kernel_shas()`` of the library is what ties profiles to a build."""
     from concurrent.futures import ThreadPoolExecutor
     build_fastpath(force, verbose)
+    build_analysis(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

@@ -294,6 +294,7 @@ class HeatMapEngine:
         self._att_cache: List[Optional[CallShape]] = [None] * self.n_layers   # attend(): per-layer call descriptors
         self._touched_flag: List[bool] = [False] * self.n_layers
         self._mask_cache: Dict[tuple, tuple] = {}        # finalize key tables per selection (_select)
+        self._ks_cache: Dict[tuple, tuple] = {}          # key_scores: (keys, DaamKeyPlanes tensor) per selection and buffer addresses
         # deferred mode: the per-call bookkeeping runs in the C++ recorder (csrc/daam_fastpath.cpp) when
         # that extension is built; the Python implementation below is the same logic and stays the
         # slow path (first call of a layer, shape changes) and the fallback.  Both only record host-side
@@ -1097,6 +1098,84 @@ class HeatMapEngine:
                                                self.stream)
         return self._finalize_chunks(len(groups), call)
 
+    def key_scores(self, footprint: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                   factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None, layer_idx: Optional[int] = None,
+                   n_prompts: int = 1, prompt: int = 0, bins: Optional[Tuple[int, int]] = None):
+        """Head analysis (``daam_key_scores`` of ``libdaam_analysis.so``): per selected key the finalize's arithmetic -- bicubic to the
+        map's size, clamp at 0 -- ending in a dot product with each ``footprint`` [M, out_h, out_w] (fp32, what ``region_scores`` /
+        ``RegionAttribution.footprint`` hold; ``None``: the total clamped mass, one column) instead of the sum over keys.  Returns
+        ``(keys, scores)``: ``keys`` the ``(factor, layer, head)`` of prompt ``prompt``'s selection in the library's key order
+        (``head`` counts inside the prompt's block, like ``head_idx``), ``scores`` fp32 ``[len(keys), max(M, 1), rows]`` on the device.
+        One launch per 32 footprints reads the running sums once and writes no map; the filters, ``n_rows`` and ``bins`` mean what they
+        mean in ``global_heat_maps``.  The mean of ``scores`` over the keys is, by linearity, ``region_dots`` of the global map."""
+        binned = self._binned(bins)
+        rows = self.tokens if n_rows is None else self._rows(n_rows)
+        n_prompts, prompt = int(n_prompts), int(prompt)
+        if not 0 <= prompt < n_prompts:
+            raise ValueError(f'prompt {prompt} of {n_prompts}')
+        factors = None if factors is None else set(factors)
+        table, _ = self._select(n_prompts, factors, head_idx, layer_idx, used=(prompt,))
+        self.flush()
+        b0, b1 = (bins if bins is not None else (0, self.n_bins)) if binned else (0, 1)
+        if footprint is not None:
+            if footprint.dtype != torch.float32 or footprint.dim() != 3 or tuple(footprint.shape[1:]) != (self.out_h, self.out_w) \
+                    or footprint.shape[0] < 1:
+                raise ValueError(f'footprint must be fp32 [M, {self.out_h}, {self.out_w}], got {tuple(footprint.shape)} {footprint.dtype}')
+            if footprint.device != self.device:
+                raise RuntimeError('daam_amd: the footprint is not on the engine\'s device')
+            footprint = footprint.contiguous()
+        keys, desc = self._key_planes(table, n_prompts, prompt, factors, head_idx, layer_idx, b0, b1, binned)
+        lib = nat.load_analysis()
+        parts = []
+        chunks = [None] if footprint is None else [footprint[at:at + MAX_REGION_MASKS] for at in range(0, footprint.shape[0], MAX_REGION_MASKS)]
+        with torch.cuda.device(self.device):
+            for chunk in chunks:
+                m = 0 if chunk is None else chunk.shape[0]
+                scores = torch.empty(len(keys), max(m, 1), rows, dtype=torch.float32, device=self.device)
+                nat.check_analysis(lib.daam_key_scores(desc.data_ptr(), len(keys), _DTYPE_CODE[self.acc_dtype], rows, self.out_h, self.out_w,
+                                                       None if chunk is None else chunk.data_ptr(), m, scores.data_ptr(), self.stream))
+                parts.append(scores)
+        return keys, parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+    def _key_planes(self, table, n_prompts, prompt, factors, head_idx, layer_idx, b0, b1, binned):
+        """``(keys, DaamKeyPlanes[len(keys)] as a uint8 device tensor)`` of prompt ``prompt``'s keys in ``table``, in the library's key
+        order.  Base pointers are those of the views ``items()`` / ``window_items(b0)`` yield (the sums are addressed nowhere else);
+        a window range is ``n_win = b1 - b0`` and the distance of a key's views in two windows.  Cached per selection, window range and
+        buffer addresses: 1100 ``data_ptr()`` calls cost more host time than the kernel takes."""
+        sel = (n_prompts, prompt, None if factors is None else tuple(sorted(factors)), head_idx, layer_idx, b0, b1, tuple(self.touched),
+               tuple(self.acc[layer].data_ptr() for layer in self.touched))
+        cached = self._ks_cache.get(sel)
+        if cached is not None:
+            if binned:
+                self._zero_unreached_windows()
+            return cached
+        views_out = self._views_out                        # the views stay in here: the buffers may still be parked for reuse
+        windows = self.time_bins is not None               # one window is still laid out [1, heads, ...]
+        first = self.window_items(b0) if windows else dict(self.items())
+        second = self.window_items(b0 + 1) if b1 - b0 > 1 else None
+        self._views_out = views_out
+        _, offs = self._key_layout(self.touched)
+        picked = []
+        for layer, off in zip(self.touched, offs):
+            factor, heads, _ = self.layer_info[layer]
+            block = heads // n_prompts
+            for h in range(heads):
+                if table[off + h] == prompt:
+                    view = first[(factor, layer, h)]
+                    if not view.is_contiguous():
+                        raise RuntimeError('daam_amd: a running sum is not contiguous')
+                    stride = 0 if second is None else (second[(factor, layer, h)].data_ptr() - view.data_ptr()) // view.element_size()
+                    picked.append((off + h, (factor, layer, h - prompt * block), view, stride))
+        picked.sort(key=lambda e: e[0])
+        arr = (nat.KeyPlanes * len(picked))()
+        for i, (_, _, view, stride) in enumerate(picked):
+            arr[i] = nat.KeyPlanes(base=view.data_ptr(), win_stride=stride, h=view.shape[-2], w=view.shape[-1], n_win=b1 - b0, pad=0)
+        desc = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device, copy=True)
+        if len(self._ks_cache) > 16:
+            self._ks_cache.clear()
+        cached = self._ks_cache[sel] = ([key for _, key, _, _ in picked], desc)
+        return cached
+
     def normalize_(self, maps: torch.Tensor) -> torch.Tensor:
         """trace.py:129-130, in place on ``maps`` [n_rows, x, x] -- or [n_rows, out_h, out_w] -- (contiguous fp32)."""
         h, w = maps.shape[-2:]
@@ -1224,40 +1303,66 @@ def _check_map_sets(maps: torch.Tensor) -> torch.Tensor:
     return sets
 
 
-def region_scores(maps: torch.Tensor, masks: torch.Tensor):
-    """``daam_region_scores``: how much of every row's expanded heat map lies inside every mask.  ``maps`` is [rows, h, w] or
+def region_scores(maps: Optional[torch.Tensor], masks: torch.Tensor, map_hw: Optional[Tuple[int, int]] = None):
+    """``daam_region_scores``: how much of every row's expanded heat map lies inside every mask.  ``maps=None`` with ``map_hw=(h, w)``:
+    the footprints alone (``region_footprint``), scores ``None``.  ``maps`` is [rows, h, w] or
     [G, rows, h, w] fp32 on the device, ``masks`` [M, H, W] (or [H, W]) uint8 / bool (a byte != 0 is set; other dtypes through
     ``!= 0``; CPU masks are moved to the device).  Returns ``(scores, area, footprint)``: ``scores[..., m, t]`` = the sum over the set
     pixels of mask ``m`` of ``expand_word_map(maps[..., t], H, W, absolute=True)`` as fp32 [M, rows] (or [G, M, rows]), ``area``
     int32 [M] the exact pixel counts, ``footprint`` fp32 [M, h, w] the masks pulled back onto the maps' grid, which
     ``region_dots`` scores further map sets against.  No plane of H x W is written; more than 32 masks run in chunks of 32."""
     from .evaluate import _as_masks
+    if maps is None:
+        return region_footprint(masks, *map_hw) if map_hw is not None else _no_map_hw()
     sets = _check_map_sets(maps)
     masks = _as_masks(masks, 'masks', maps.device)
     if masks.device != maps.device:
         raise RuntimeError('daam_amd: maps and masks are on different devices')
-    n_sets, rows, h, w = sets.shape
+    out = _region_chunks(masks, sets.shape[2], sets.shape[3], sets)
+    scores, area, footprint = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out], dim=1), torch.cat([o[1] for o in out]),
+                                                           torch.cat([o[2] for o in out]))
+    return (scores if maps.dim() == 4 else scores[0]), area, footprint
+
+
+def _no_map_hw():
+    raise ValueError('region_scores(None, masks) needs map_hw=(h, w): the grid the footprints are pulled back onto')
+
+
+def region_footprint(masks: torch.Tensor, h: int, w: int, device=None):
+    """``region_scores`` without maps (``daam_region_scores`` with ``maps == NULL``): ``(None, area, footprint)`` of ``masks`` on an
+    ``h x w`` grid, for ``region_dots`` / ``HeatMapEngine.key_scores``.  CPU masks are moved to ``device`` (default: the current one)."""
+    from .evaluate import _as_masks
+    h, w = int(h), int(w)
+    if not (1 <= h <= 128 and 1 <= w <= 128):
+        raise ValueError(f'region footprints take a grid of 1..128 cells a side, got {h} x {w}')
+    masks = _as_masks(masks, 'masks', device)
+    out = _region_chunks(masks, h, w, None)
+    return (None, *(out[0][1:] if len(out) == 1 else (torch.cat([o[1] for o in out]), torch.cat([o[2] for o in out]))))
+
+
+def _region_chunks(masks: torch.Tensor, h: int, w: int, sets: Optional[torch.Tensor]) -> list:
+    """``daam_region_scores`` per 32 masks: ``[(scores or None, area, footprint)]``; ``sets`` [G, rows, h, w] or None (footprints only)."""
+    n_sets, rows = (0, 0) if sets is None else sets.shape[:2]
     big_h, big_w = masks.shape[1:]
     lib = nat.load()
     out = []
-    with torch.cuda.device(maps.device):
-        stream = torch.cuda.current_stream(maps.device).cuda_stream
+    with torch.cuda.device(masks.device):
+        stream = torch.cuda.current_stream(masks.device).cuda_stream
         for at in range(0, masks.shape[0], MAX_REGION_MASKS):
             chunk = masks[at:at + MAX_REGION_MASKS]
             n = chunk.shape[0]
             size = lib.daam_region_scores_workspace(n, big_h, big_w, h, w)
             if size == 0:
                 raise ValueError(f'region scores: masks of {big_h} x {big_w} are outside the limits (H * W < 2^31)')
-            ws = torch.empty(size, dtype=torch.uint8, device=maps.device)
-            scores = torch.empty(n_sets, n, rows, dtype=torch.float32, device=maps.device)
-            area = torch.empty(n, dtype=torch.int32, device=maps.device)
-            footprint = torch.empty(n, h, w, dtype=torch.float32, device=maps.device)
-            nat.check(lib.daam_region_scores(chunk.data_ptr(), n, big_h, big_w, sets.data_ptr(), n_sets, rows, h, w, footprint.data_ptr(),
-                                             scores.data_ptr(), area.data_ptr(), ws.data_ptr(), stream))
+            ws = torch.empty(size, dtype=torch.uint8, device=masks.device)
+            scores = None if sets is None else torch.empty(n_sets, n, rows, dtype=torch.float32, device=masks.device)
+            area = torch.empty(n, dtype=torch.int32, device=masks.device)
+            footprint = torch.empty(n, h, w, dtype=torch.float32, device=masks.device)
+            nat.check(lib.daam_region_scores(chunk.data_ptr(), n, big_h, big_w, None if sets is None else sets.data_ptr(), n_sets, rows, h, w,
+                                             footprint.data_ptr(), None if sets is None else scores.data_ptr(), area.data_ptr(),
+                                             ws.data_ptr(), stream))
             out.append((scores, area, footprint))
-    scores, area, footprint = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out], dim=1), torch.cat([o[1] for o in out]),
-                                                           torch.cat([o[2] for o in out]))
-    return (scores if maps.dim() == 4 else scores[0]), area, footprint
+    return out
 
 
 def region_dots(maps: torch.Tensor, footprint: torch.Tensor) -> torch.Tensor:

@@ -13,7 +13,7 @@ from . import engine as _engine
 from .utils import cached_nlp, compute_token_merge_indices
 
 __all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair', 'Segmentation',
-           'RegionAttribution']
+           'RegionAttribution', 'KeyScores']
 
 RawHeatMapKey = Tuple[int, int, int]  # factor, layer, head
 
@@ -178,6 +178,52 @@ class RegionAttribution:
 
     def cpu(self) -> 'RegionAttribution':
         return RegionAttribution(self.scores.cpu(), self.area.cpu(), self.footprint.cpu(), self.tokenizer, self.prompt)
+
+
+@dataclass
+class KeyScores:
+    """Head analysis (``DiffusionHeatMapHooker.compute_key_scores``): for every selected ``(factor, layer, head)`` key what
+    ``compute_global_heat_map(head_idx=, layer_idx=)`` + ``attribute(regions)`` would give for that key alone -- the sum of every token
+    row's clamped, resized map under each region -- from one pass over the running sums.  On the device until ``cpu()``."""
+    keys: List[RawHeatMapKey]                   # (factor, layer, head), in the library's key order
+    scores: torch.Tensor                        # f32 [K, M, rows]; M = 1 without regions (the total clamped mass)
+    area: Optional[torch.Tensor]                # int32 [M] pixels of each region; None without masks at image resolution
+    layer_names: Optional[List[str]] = None     # the trace's layer names, indexed by a key's layer
+    tokenizer: Any = None
+    prompt: Optional[str] = None
+
+    def mean(self) -> torch.Tensor:
+        """f32 [M, rows]: the mean over the keys -- by linearity ``GlobalHeatMap.attribute(regions).scores`` of the same selection."""
+        return self.scores.mean(dim=0)
+
+    def word_scores(self, word: str, word_idx: Optional[int] = None) -> torch.Tensor:
+        """f32 [K, M]: the mean over the word's token rows (the merge indices of ``compute_word_heat_map``)."""
+        idxs, _ = compute_token_merge_indices(self.tokenizer, self.prompt, word, word_idx)
+        return self.scores[:, :, list(idxs)].mean(dim=2)
+
+    def top_keys(self, word: str, region: int = 0, k: int = 10, word_idx: Optional[int] = None):
+        """The ``k`` keys that put most of ``word`` into ``region``: ``[((factor, layer, head), score)]``, highest first; equal
+        scores keep the key order."""
+        col = self.word_scores(word, word_idx)[:, region].cpu()
+        order = torch.sort(col, descending=True, stable=True).indices[:k].tolist()
+        return [(self.keys[i], float(col[i])) for i in order]
+
+    def _grouped(self, pos: int):
+        labels = sorted({key[pos] for key in self.keys})
+        rows = [self.scores[[i for i, key in enumerate(self.keys) if key[pos] == label]].mean(dim=0) for label in labels]
+        return labels, torch.stack(rows)
+
+    def by_layer(self):
+        """``(layers, f32 [len(layers), M, rows])``: the mean over each layer's heads, layers ascending."""
+        return self._grouped(1)
+
+    def by_head(self):
+        """``(heads, f32 [len(heads), M, rows])``: the mean over the layers that have the head, heads ascending."""
+        return self._grouped(2)
+
+    def cpu(self) -> 'KeyScores':
+        return KeyScores(list(self.keys), self.scores.cpu(), None if self.area is None else self.area.cpu(), self.layer_names,
+                         self.tokenizer, self.prompt)
 
 
 class GlobalHeatMap:

@@ -25,8 +25,8 @@ from typing import Any, List, Optional, Type, Union
 import torch
 import torch.nn.functional as F
 
-from .engine import HeatMapEngine, check_probes, check_time_bins, map_geometry
-from .heatmap import GlobalHeatMap, RawHeatMapCollection
+from .engine import HeatMapEngine, check_probes, check_time_bins, map_geometry, region_scores
+from .heatmap import GlobalHeatMap, KeyScores, RawHeatMapCollection, RegionAttribution, Segmentation
 from .hook import AggregateHooker, ObjectHooker, UNetCrossAttentionLocator
 from .utils import cache_dir
 
@@ -416,6 +416,41 @@ class DiffusionHeatMapHooker(AggregateHooker):
         except LookupError:
             raise _no_maps(head_idx is not None or layer_idx is not None) from None
         return self._wrap(maps, n_rows, prompt, normalize)
+
+    # -- head analysis -----------------------------------------------------------------------------------
+    def compute_key_scores(self, regions=None, prompt=None, factors=None, head_idx=None, layer_idx=None,
+                           prompt_idx: Optional[int] = None, time_bin=None) -> KeyScores:
+        """Which heads and layers carry a word: for every selected ``(factor, layer, head)`` key the scores that
+        ``compute_global_heat_map(head_idx=, layer_idx=).attribute(regions)`` gives for that key alone, from ONE device pass over the
+        running sums (``HeatMapEngine.key_scores``) instead of one finalize per key.  ``regions``: ``None`` (one column: each token
+        row's total clamped mass), a uint8 / bool mask or stack of masks at image resolution, a ``Segmentation`` (its masks), or a
+        ``RegionAttribution`` (its footprint is reused).  Rows are cropped to ``len(tokenize(prompt)) + 2``; ``factors`` /
+        ``head_idx`` / ``layer_idx`` / ``prompt_idx`` / ``time_bin`` mean what they mean in ``compute_global_heat_map`` and fail as
+        they do there; non-square traces work.  Probes are out of scope: the scores are those of the generation's own prompt."""
+        n = len(self.last_prompts)
+        if prompt_idx is not None:
+            prompt_idx = self._check_prompt_idx(prompt_idx)
+        rng = self._bin_range(time_bin)
+        if n > 1 and prompt_idx is None:
+            raise ValueError(f'the last generation traced {n} prompts: pass prompt_idx')
+        if prompt is None:
+            prompt = self.last_prompts[prompt_idx] if n > 1 else self.last_prompt
+        n_rows = self._n_rows(prompt)
+        self._check_bin_steps(rng)
+        eng = self.engine
+        area = footprint = None
+        if isinstance(regions, RegionAttribution):
+            area, footprint = regions.area, regions.footprint
+        elif regions is not None:
+            masks = regions.masks if isinstance(regions, Segmentation) else regions
+            _, area, footprint = region_scores(None, masks, map_hw=(eng.out_h, eng.out_w))
+        try:
+            kw = {} if rng is None else dict(bins=rng)
+            keys, scores = eng.key_scores(footprint, n_rows=n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx,
+                                          n_prompts=max(n, 1), prompt=prompt_idx or 0, **kw)
+        except LookupError:
+            raise _no_maps(head_idx is not None or layer_idx is not None) from None
+        return KeyScores(keys, scores, area, list(self.layer_names), self.pipe.tokenizer, prompt)
 
     # -- probes (open-vocabulary heat maps) ----------------------------------------------------------
     def _check_probe(self, probe) -> int:
