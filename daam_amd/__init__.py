@@ -4,6 +4,7 @@
 from .hook import *          # noqa: F401,F403
 from .utils import *         # noqa: F401,F403
 from .heatmap import *       # noqa: F401,F403
+from .coattention import *   # noqa: F401,F403
 from .trace import *         # noqa: F401,F403
 from .experiment import *    # noqa: F401,F403
 from .evaluate import compute_iou, compute_ioa, load_mask, MeanEvaluator, UnsupervisedEvaluator  # noqa: F401

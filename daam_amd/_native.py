@@ -177,5 +177,43 @@ def check_analysis(rc: int) -> None:
         raise DaamError(rc, msg.decode() if msg else '')
 
 
+# ---- libdaam_gram.so (C ABI: include/daam_gram.h) ----------------------------------------------------------------------------------
+GRAM_LIB_NAME = 'libdaam_gram.so'
+GRAM_LIB_PATH = os.environ.get('DAAM_GRAM_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), GRAM_LIB_NAME)
+GRAM_ABI_VERSION = 1
+GRAM_EXPORTS = ('daam_token_gram', 'daam_token_gram_scratch_bytes', 'daam_gram_abi_version', 'daam_gram_last_error')
+
+_gram = None
+
+
+def load_gram() -> ctypes.CDLL:
+    """The token co-attention library; like ``load`` it has no fallback: missing or stale is an error."""
+    global _gram
+    if _gram is not None:
+        return _gram
+    if not os.path.exists(GRAM_LIB_PATH):
+        raise RuntimeError(f'{GRAM_LIB_PATH} is missing: token Gram matrices have no fallback. Build it with `python -m daam_amd.build`.')
+    lib = ctypes.CDLL(GRAM_LIB_PATH)
+    missing = [name for name in GRAM_EXPORTS if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError(f'{GRAM_LIB_PATH}: lacks {", ".join(missing)} (stale build); rebuild')
+    lib.daam_token_gram.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.daam_token_gram.restype = c_int
+    lib.daam_token_gram_scratch_bytes.argtypes = [c_int, c_int, c_int]
+    lib.daam_token_gram_scratch_bytes.restype = c_size_t
+    lib.daam_gram_abi_version.restype = c_int
+    lib.daam_gram_last_error.restype = c_char_p
+    if lib.daam_gram_abi_version() != GRAM_ABI_VERSION:
+        raise RuntimeError(f'{GRAM_LIB_PATH}: ABI version {lib.daam_gram_abi_version()} != {GRAM_ABI_VERSION}; rebuild')
+    _gram = lib
+    return lib
+
+
+def check_gram(rc: int) -> None:
+    if rc != 0:
+        msg = load_gram().daam_gram_last_error()
+        raise DaamError(rc, msg.decode() if msg else '')
+
+
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -17,6 +17,11 @@ ANALYSIS_SOURCES = ['daam_key_scores.hip']
 ANALYSIS_HEADERS = ['daam_key_scores.h', 'daam_finalize.h', 'daam_epilogue.h', 'daam_elem.h', 'daam_types.h',
                     os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_analysis.h')]
 ANALYSIS_OUT = os.path.join(HERE, 'libdaam_analysis.so')
+# libdaam_gram.so (include/daam_gram.h): the third library, token co-attention; built the way the second one is, for the same reason
+GRAM_SOURCES = ['daam_token_gram.hip']
+GRAM_HEADERS = ['daam_token_gram.h', 'daam_finalize.h', 'daam_elem.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'),
+                os.path.join('..', '..', 'include', 'daam_analysis.h'), os.path.join('..', '..', 'include', 'daam_gram.h')]
+GRAM_OUT = os.path.join(HERE, 'libdaam_gram.so')
 
 
 def csrc_sha() -> str:
@@ -114,6 +119,25 @@ def build_analysis(force: bool = False, verbose: bool = True) -> str:
     return ANALYSIS_OUT
 
 
+def gram_stale() -> bool:
+    if not os.path.exists(GRAM_OUT):
+        return True
+    t = os.path.getmtime(GRAM_OUT)
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in GRAM_SOURCES + GRAM_HEADERS)
+
+
+def build_gram(force: bool = False, verbose: bool = True) -> str:
+    """``libdaam_gram.so``: one hipcc command (one source), when it is missing or older than what it is made of."""
+    if not force and not gram_stale():
+        return GRAM_OUT
+    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
+           *[os.path.join(HERE, 'csrc', f) for f in GRAM_SOURCES], '-o', GRAM_OUT]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return GRAM_OUT
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -167,6 +191,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     from concurrent.futures import ThreadPoolExecutor
     build_fastpath(force, verbose)
     build_analysis(force, verbose)
+    build_gram(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

@@ -295,6 +295,7 @@ class HeatMapEngine:
         self._touched_flag: List[bool] = [False] * self.n_layers
         self._mask_cache: Dict[tuple, tuple] = {}        # finalize key tables per selection (_select)
         self._ks_cache: Dict[tuple, tuple] = {}          # key_scores: (keys, DaamKeyPlanes tensor) per selection and buffer addresses
+        self._gram_scratch: Optional[torch.Tensor] = None    # token_gram: the partial matrices of keys of more than one chunk
         # deferred mode: the per-call bookkeeping runs in the C++ recorder (csrc/daam_fastpath.cpp) when
         # that extension is built; the Python implementation below is the same logic and stays the
         # slow path (first call of a layer, shape changes) and the fallback.  Both only record host-side
@@ -1137,6 +1138,38 @@ class HeatMapEngine:
                 parts.append(scores)
         return keys, parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
 
+    def token_gram(self, n_rows: Optional[int] = None, factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None,
+                   layer_idx: Optional[int] = None, n_prompts: int = 1, prompt: int = 0, bins: Optional[Tuple[int, int]] = None):
+        """Token co-attention (``daam_token_gram`` of ``libdaam_gram.so``): per selected key the Gram matrix of its token planes,
+        ``gram[k][i][j] = sum_p plane_i[p] * plane_j[p]``, at the key's own resolution from the raw running sums (no bicubic, no
+        clamp), from one pass over the sums that ends on the matrix cores.  ``key_scores`` without footprints: the same selection,
+        key order, ``n_rows`` crop, ``bins`` and ``LookupError``.  Returns ``(keys, gram)`` with ``gram`` fp32
+        ``[len(keys), rows, rows]`` on the device.  The scratch of the keys' partial matrices is the engine's, grown on demand."""
+        binned = self._binned(bins)
+        rows = self.tokens if n_rows is None else self._rows(n_rows)
+        n_prompts, prompt = int(n_prompts), int(prompt)
+        if not 0 <= prompt < n_prompts:
+            raise ValueError(f'prompt {prompt} of {n_prompts}')
+        factors = None if factors is None else set(factors)
+        table, _ = self._select(n_prompts, factors, head_idx, layer_idx, used=(prompt,))
+        self.flush()
+        b0, b1 = (bins if bins is not None else (0, self.n_bins)) if binned else (0, 1)
+        keys, desc = self._key_planes(table, n_prompts, prompt, factors, head_idx, layer_idx, b0, b1, binned)
+        lib = nat.load_gram()
+        # sized for the largest touched layer, selected or not (60 layers to look at, not 1100 keys; more scratch changes no bit)
+        sides = {self.layer_info[layer][2] for layer in self.touched}
+        max_hw = max(s[0] * s[1] if isinstance(s, tuple) else s * s for s in sides)
+        need = lib.daam_token_gram_scratch_bytes(len(keys), rows, max_hw)
+        if need == 0:
+            raise ValueError(f'daam_token_gram takes 1..96 token rows and up to 2^20 keys, got {rows} rows of {len(keys)} keys')
+        with torch.cuda.device(self.device):
+            if self._gram_scratch is None or self._gram_scratch.numel() < need:
+                self._gram_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            gram = torch.empty(len(keys), rows, rows, dtype=torch.float32, device=self.device)
+            nat.check_gram(lib.daam_token_gram(desc.data_ptr(), len(keys), _DTYPE_CODE[self.acc_dtype], rows, gram.data_ptr(),
+                                               self._gram_scratch.data_ptr(), self._gram_scratch.numel(), self.stream))
+        return keys, gram
+
     def _key_planes(self, table, n_prompts, prompt, factors, head_idx, layer_idx, b0, b1, binned):
         """``(keys, DaamKeyPlanes[len(keys)] as a uint8 device tensor)`` of prompt ``prompt``'s keys in ``table``, in the library's key
         order.  Base pointers are those of the views ``items()`` / ``window_items(b0)`` yield (the sums are addressed nowhere else);
@@ -1322,6 +1355,24 @@ def region_scores(maps: Optional[torch.Tensor], masks: torch.Tensor, map_hw: Opt
     scores, area, footprint = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out], dim=1), torch.cat([o[1] for o in out]),
                                                            torch.cat([o[2] for o in out]))
     return (scores if maps.dim() == 4 else scores[0]), area, footprint
+
+
+def map_gram(maps: torch.Tensor) -> torch.Tensor:
+    """``daam_token_gram`` on one set of maps as a single f32 key: ``maps`` [rows, h, w] fp32 on the device (1..96 rows, 1..128 cells a
+    side) -> fp32 ``[rows, rows]``, ``out[i][j] = sum_p maps[i][p] * maps[j][p]`` (``GlobalHeatMap.coattention``)."""
+    _check_maps(maps)
+    rows, h, w = maps.shape
+    if not (1 <= rows <= 96 and 1 <= h <= 128 and 1 <= w <= 128):
+        raise ValueError(f'a Gram matrix takes 1..96 rows of 1..128 cells a side, got {tuple(maps.shape)}')
+    lib = nat.load_gram()
+    key = (nat.KeyPlanes * 1)(nat.KeyPlanes(base=maps.data_ptr(), win_stride=0, h=h, w=w, n_win=1, pad=0))
+    with torch.cuda.device(maps.device):
+        desc = torch.frombuffer(bytearray(bytes(key)), dtype=torch.uint8).to(maps.device, copy=True)
+        scratch = torch.empty(lib.daam_token_gram_scratch_bytes(1, rows, h * w), dtype=torch.uint8, device=maps.device)
+        gram = torch.empty(1, rows, rows, dtype=torch.float32, device=maps.device)
+        nat.check_gram(lib.daam_token_gram(desc.data_ptr(), 1, nat.DAAM_F32, rows, gram.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                           torch.cuda.current_stream(maps.device).cuda_stream))
+    return gram[0]
 
 
 def _no_map_hw():

@@ -282,6 +282,22 @@ class GlobalHeatMap:
         scores, area, footprint = _engine.region_scores(self.heat_maps, masks)
         return RegionAttribution(scores, area, footprint, self.tokenizer, self.prompt)
 
+    def coattention(self) -> torch.Tensor:
+        """f32 [rows, rows]: the Gram matrix of the map's token rows, ``out[i][j] = sum_p heat_maps[i][p] * heat_maps[j][p]``
+        (``engine.map_gram``: the library call of ``compute_key_coattention`` on the global map as one key)."""
+        return _engine.map_gram(self.heat_maps)
+
+    def word_cosine(self, word_a: str, word_b: str, eps: float = 1e-12) -> float:
+        """The cosine of two words' maps (``compute_word_heat_map``: the mean of the word's token rows) from block means of
+        ``coattention()``: a threshold-free companion of ``WordHeatMap.compute_ioa``.  A word whose map is all zeros gives 0."""
+        a, _ = compute_token_merge_indices(self.tokenizer, self.prompt, word_a, None)
+        b, _ = compute_token_merge_indices(self.tokenizer, self.prompt, word_b, None)
+        g = self.coattention().double()
+
+        def block(r, c):
+            return float(g[list(r)][:, list(c)].mean())
+        return block(a, b) / (block(a, a) * block(b, b) + eps) ** 0.5
+
     def parsed_heat_maps(self) -> Iterable[ParsedHeatMap]:
         """One ``ParsedHeatMap`` per token of the parsed prompt whose text is found among the prompt's tokenizer tokens
         (heatmap.py:125-131; the others are skipped)."""

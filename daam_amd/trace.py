@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from .engine import HeatMapEngine, check_probes, check_time_bins, map_geometry, region_scores
+from .coattention import KeyCoattention
 from .heatmap import GlobalHeatMap, KeyScores, RawHeatMapCollection, RegionAttribution, Segmentation
 from .hook import AggregateHooker, ObjectHooker, UNetCrossAttentionLocator
 from .utils import cache_dir
@@ -451,6 +452,31 @@ class DiffusionHeatMapHooker(AggregateHooker):
         except LookupError:
             raise _no_maps(head_idx is not None or layer_idx is not None) from None
         return KeyScores(keys, scores, area, list(self.layer_names), self.pipe.tokenizer, prompt)
+
+    def compute_key_coattention(self, prompt=None, factors=None, head_idx=None, layer_idx=None, prompt_idx: Optional[int] = None,
+                                time_bin=None) -> KeyCoattention:
+        """Which heads and layers entangle two words: for every selected ``(factor, layer, head)`` key the Gram matrix of its token
+        planes, from ONE device pass over the raw running sums (``HeatMapEngine.token_gram``; no bicubic, no clamp, no threshold).
+        ``KeyCoattention.of('dog', 'cat')`` is then the cosine of the two word maps per key.  Rows are cropped to
+        ``len(tokenize(prompt)) + 2``; every argument means what it means in ``compute_key_scores`` and fails as it fails there;
+        batched prompts, time windows and non-square traces work.  Probes are out of scope."""
+        n = len(self.last_prompts)
+        if prompt_idx is not None:
+            prompt_idx = self._check_prompt_idx(prompt_idx)
+        rng = self._bin_range(time_bin)
+        if n > 1 and prompt_idx is None:
+            raise ValueError(f'the last generation traced {n} prompts: pass prompt_idx')
+        if prompt is None:
+            prompt = self.last_prompts[prompt_idx] if n > 1 else self.last_prompt
+        n_rows = self._n_rows(prompt)
+        self._check_bin_steps(rng)
+        try:
+            kw = {} if rng is None else dict(bins=rng)
+            keys, gram = self.engine.token_gram(n_rows=n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx,
+                                                n_prompts=max(n, 1), prompt=prompt_idx or 0, **kw)
+        except LookupError:
+            raise _no_maps(head_idx is not None or layer_idx is not None) from None
+        return KeyCoattention(keys, gram, list(self.layer_names), self.pipe.tokenizer, prompt)
 
     # -- probes (open-vocabulary heat maps) ----------------------------------------------------------
     def _check_probe(self, probe) -> int:
