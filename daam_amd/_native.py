@@ -56,20 +56,29 @@ class AttendDesc(Structure):
 _lib = None
 
 
+def _open(path: str, what: str, exports, version_fn: str, version: int) -> ctypes.CDLL:
+    """Open a library of the project: it exists, has every symbol of ``exports`` and reports ``version``, or RuntimeError (there is
+    no fallback: missing or stale is an error that names the file and the remedy)."""
+    if not os.path.exists(path):
+        raise RuntimeError(f'{path} is missing: {what} has no fallback. '
+                           f'Build it with `python -m daam_amd.build` (needs hipcc, --offload-arch=gfx950).')
+    lib = ctypes.CDLL(path)
+    # a library built before an entry point was added: same ABI version, fewer symbols -- as stale as a version mismatch
+    missing = [name for name in exports if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError(f'{path}: lacks {", ".join(missing)} (stale build); rebuild')
+    built = getattr(lib, version_fn)
+    built.restype = c_int
+    if built() != version:
+        raise RuntimeError(f'{path}: ABI version {built()} != {version}; rebuild')
+    return lib
+
+
 def load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f'{LIB_PATH} is missing: the MI355X heat-map path has no fallback. '
-            f'Build it with `python -m daam_amd.build` (needs hipcc, --offload-arch=gfx950).')
-    lib = ctypes.CDLL(LIB_PATH)
-    # a library built before an entry point was added: same ABI version, fewer symbols -- as stale as a version mismatch
-    missing = [name for name in EXPORTS if not hasattr(lib, name)]
-    if missing:
-        raise RuntimeError(f'{LIB_PATH}: lacks {", ".join(missing)} (stale build); rebuild')
-    lib.daam_abi_version.restype = c_int
+    lib = _open(LIB_PATH, 'the MI355X heat-map path', EXPORTS, 'daam_abi_version', ABI_VERSION)
     lib.daam_last_error.restype = c_char_p
     lib.daam_ctx_create.argtypes = [c_int, c_int, c_int, c_int, POINTER(c_void_p)]
     lib.daam_ctx_destroy.argtypes = [c_void_p]
@@ -123,8 +132,6 @@ def load() -> ctypes.CDLL:
         if name not in ('daam_last_error', 'daam_region_scores_workspace'):
             fn.restype = c_int
     lib.daam_region_scores_workspace.restype = c_size_t
-    if lib.daam_abi_version() != ABI_VERSION:
-        raise RuntimeError(f'{LIB_PATH}: ABI version {lib.daam_abi_version()} != {ABI_VERSION}; rebuild')
     _lib = lib
     return lib
 
@@ -138,8 +145,9 @@ def check(rc: int) -> None:
 # ---- libdaam_analysis.so (C ABI: include/daam_analysis.h) -------------------------------------------------------------------------
 ANALYSIS_LIB_NAME = 'libdaam_analysis.so'
 ANALYSIS_LIB_PATH = os.environ.get('DAAM_ANALYSIS_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), ANALYSIS_LIB_NAME)
-ANALYSIS_ABI_VERSION = 1
-ANALYSIS_EXPORTS = ('daam_key_scores', 'daam_analysis_abi_version', 'daam_analysis_last_error')
+ANALYSIS_ABI_VERSION = 2
+ANALYSIS_EXPORTS = ('daam_key_scores', 'daam_token_gram', 'daam_token_gram_scratch_bytes', 'daam_analysis_abi_version',
+                    'daam_analysis_last_error')
 
 
 class KeyPlanes(Structure):
@@ -151,22 +159,18 @@ _analysis = None
 
 
 def load_analysis() -> ctypes.CDLL:
-    """The head-analysis library; like ``load`` it has no fallback: missing or stale is an error."""
+    """The per-key analysis library (key scores, token Gram matrices); like ``load`` it has no fallback."""
     global _analysis
     if _analysis is not None:
         return _analysis
-    if not os.path.exists(ANALYSIS_LIB_PATH):
-        raise RuntimeError(f'{ANALYSIS_LIB_PATH} is missing: per-key scores have no fallback. Build it with `python -m daam_amd.build`.')
-    lib = ctypes.CDLL(ANALYSIS_LIB_PATH)
-    missing = [name for name in ANALYSIS_EXPORTS if not hasattr(lib, name)]
-    if missing:
-        raise RuntimeError(f'{ANALYSIS_LIB_PATH}: lacks {", ".join(missing)} (stale build); rebuild')
+    lib = _open(ANALYSIS_LIB_PATH, 'per-key analysis', ANALYSIS_EXPORTS, 'daam_analysis_abi_version', ANALYSIS_ABI_VERSION)
     lib.daam_key_scores.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
     lib.daam_key_scores.restype = c_int
-    lib.daam_analysis_abi_version.restype = c_int
+    lib.daam_token_gram.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.daam_token_gram.restype = c_int
+    lib.daam_token_gram_scratch_bytes.argtypes = [c_int, c_int, c_int]
+    lib.daam_token_gram_scratch_bytes.restype = c_size_t
     lib.daam_analysis_last_error.restype = c_char_p
-    if lib.daam_analysis_abi_version() != ANALYSIS_ABI_VERSION:
-        raise RuntimeError(f'{ANALYSIS_LIB_PATH}: ABI version {lib.daam_analysis_abi_version()} != {ANALYSIS_ABI_VERSION}; rebuild')
     _analysis = lib
     return lib
 
@@ -174,44 +178,6 @@ def load_analysis() -> ctypes.CDLL:
 def check_analysis(rc: int) -> None:
     if rc != 0:
         msg = load_analysis().daam_analysis_last_error()
-        raise DaamError(rc, msg.decode() if msg else '')
-
-
-# ---- libdaam_gram.so (C ABI: include/daam_gram.h) ----------------------------------------------------------------------------------
-GRAM_LIB_NAME = 'libdaam_gram.so'
-GRAM_LIB_PATH = os.environ.get('DAAM_GRAM_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), GRAM_LIB_NAME)
-GRAM_ABI_VERSION = 1
-GRAM_EXPORTS = ('daam_token_gram', 'daam_token_gram_scratch_bytes', 'daam_gram_abi_version', 'daam_gram_last_error')
-
-_gram = None
-
-
-def load_gram() -> ctypes.CDLL:
-    """The token co-attention library; like ``load`` it has no fallback: missing or stale is an error."""
-    global _gram
-    if _gram is not None:
-        return _gram
-    if not os.path.exists(GRAM_LIB_PATH):
-        raise RuntimeError(f'{GRAM_LIB_PATH} is missing: token Gram matrices have no fallback. Build it with `python -m daam_amd.build`.')
-    lib = ctypes.CDLL(GRAM_LIB_PATH)
-    missing = [name for name in GRAM_EXPORTS if not hasattr(lib, name)]
-    if missing:
-        raise RuntimeError(f'{GRAM_LIB_PATH}: lacks {", ".join(missing)} (stale build); rebuild')
-    lib.daam_token_gram.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.daam_token_gram.restype = c_int
-    lib.daam_token_gram_scratch_bytes.argtypes = [c_int, c_int, c_int]
-    lib.daam_token_gram_scratch_bytes.restype = c_size_t
-    lib.daam_gram_abi_version.restype = c_int
-    lib.daam_gram_last_error.restype = c_char_p
-    if lib.daam_gram_abi_version() != GRAM_ABI_VERSION:
-        raise RuntimeError(f'{GRAM_LIB_PATH}: ABI version {lib.daam_gram_abi_version()} != {GRAM_ABI_VERSION}; rebuild')
-    _gram = lib
-    return lib
-
-
-def check_gram(rc: int) -> None:
-    if rc != 0:
-        msg = load_gram().daam_gram_last_error()
         raise DaamError(rc, msg.decode() if msg else '')
 
 

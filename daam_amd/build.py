@@ -11,17 +11,13 @@ SOURCES = ['daam_api.hip', 'daam_tap_api.hip', 'daam_finalize_api.hip', 'daam_ke
 HEADERS = ['daam_types.h', 'daam_elem.h', 'daam_finalize.h', 'daam_fin_bins.h', 'daam_fin_rect.h', 'daam_ctx.h', 'daam_tap_common.h', 'daam_tap16.h', 'daam_tap16_softmax.h', 'daam_tap_tile64.h', 'daam_tap_walk.h', 'daam_tap_rows.h', 'daam_epilogue.h', 'daam_tap_d64_body.inc', 'daam_finalize_pipe_asm_r16.inc', 'daam_finalize_pipe_asm_bf16.inc', 'daam_finalize_pipe_asm_f32.inc',
            'daam_finalize_pipe_prefill_r16.inc', 'daam_finalize_pipe_prefill_f32.inc', 'daam_fin_kernel_body.inc', 'daam_fin_up_kernel_body.inc', 'daam_fin_down2_kernel_body.inc', 'daam_fin_pipe_kernel_body.inc', 'daam_word_expand_body.inc', os.path.join('..', '..', 'include', 'daam_hip.h')]
 OUT = os.path.join(HERE, 'libdaam_hip.so')
-# libdaam_analysis.so (include/daam_analysis.h): a second library with no context, kept out of SOURCES / HEADERS so that csrc_sha()
-# and the kernels of libdaam_hip.so stay what the committed profiles were measured on.  Its source reads the first library's headers.
-ANALYSIS_SOURCES = ['daam_key_scores.hip']
-ANALYSIS_HEADERS = ['daam_key_scores.h', 'daam_finalize.h', 'daam_epilogue.h', 'daam_elem.h', 'daam_types.h',
-                    os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_analysis.h')]
+# libdaam_analysis.so (include/daam_analysis.h): the one side library, every per-key analysis, with no context.  It is kept out of
+# SOURCES / HEADERS so that csrc_sha() and the kernels of libdaam_hip.so stay what the committed profiles were measured on.  Its
+# sources read the first library's headers.
+ANALYSIS_SOURCES = ['daam_key_scores.hip', 'daam_token_gram.hip']
+ANALYSIS_HEADERS = ['daam_key_planes.h', 'daam_key_scores.h', 'daam_token_gram.h', 'daam_finalize.h', 'daam_epilogue.h', 'daam_elem.h',
+                    'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_analysis.h')]
 ANALYSIS_OUT = os.path.join(HERE, 'libdaam_analysis.so')
-# libdaam_gram.so (include/daam_gram.h): the third library, token co-attention; built the way the second one is, for the same reason
-GRAM_SOURCES = ['daam_token_gram.hip']
-GRAM_HEADERS = ['daam_token_gram.h', 'daam_finalize.h', 'daam_elem.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'),
-                os.path.join('..', '..', 'include', 'daam_analysis.h'), os.path.join('..', '..', 'include', 'daam_gram.h')]
-GRAM_OUT = os.path.join(HERE, 'libdaam_gram.so')
 
 
 def csrc_sha() -> str:
@@ -108,7 +104,7 @@ def analysis_stale() -> bool:
 
 
 def build_analysis(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_analysis.so``: one hipcc command (one source), when it is missing or older than what it is made of."""
+    """``libdaam_analysis.so``: one hipcc command, when it is missing or older than what it is made of."""
     if not force and not analysis_stale():
         return ANALYSIS_OUT
     cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
@@ -117,25 +113,6 @@ def build_analysis(force: bool = False, verbose: bool = True) -> str:
         print(' '.join(cmd), flush=True)
     subprocess.run(cmd, check=True)
     return ANALYSIS_OUT
-
-
-def gram_stale() -> bool:
-    if not os.path.exists(GRAM_OUT):
-        return True
-    t = os.path.getmtime(GRAM_OUT)
-    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in GRAM_SOURCES + GRAM_HEADERS)
-
-
-def build_gram(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_gram.so``: one hipcc command (one source), when it is missing or older than what it is made of."""
-    if not force and not gram_stale():
-        return GRAM_OUT
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
-           *[os.path.join(HERE, 'csrc', f) for f in GRAM_SOURCES], '-o', GRAM_OUT]
-    if verbose:
-        print(' '.join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return GRAM_OUT
 
 
 def fastpath_out() -> str:
@@ -191,7 +168,6 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     from concurrent.futures import ThreadPoolExecutor
     build_fastpath(force, verbose)
     build_analysis(force, verbose)
-    build_gram(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

@@ -1,32 +1,31 @@
 """Token co-attention (``DiffusionHeatMapHooker.compute_key_coattention``): which heads and layers entangle two words and which keep
 them apart -- the reference's cohyponym / adjectival entanglement question (``heatmap.py:95-96`` on thresholded masks of the global
 map), asked per ``(factor, layer, head)`` key and without a threshold.  The container holds one Gram matrix of token planes per key
-(``daam_token_gram`` of ``libdaam_gram.so``); everything below is small arithmetic on it."""
+(``daam_token_gram`` of ``libdaam_analysis.so``); everything below is small arithmetic on it."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, List, Optional, Tuple
+from typing import List, Optional
 
 import torch
 
+from .heatmap import KeyAnalysis
 from .utils import compute_token_merge_indices
 
 __all__ = ['KeyCoattention']
 
-RawHeatMapKey = Tuple[int, int, int]  # factor, layer, head
 
-
-@dataclass
-class KeyCoattention:
+@dataclass(init=False)
+class KeyCoattention(KeyAnalysis):
     """``gram[k][i][j] = sum_p plane_k,i[p] * plane_k,j[p]`` of every selected key's raw running sums, at the key's own resolution (no
     bicubic, no clamp).  A word map is the mean of its token rows, so the Gram of two words is the mean of a block of ``gram``,
     exactly: one matrix per key answers every word pair.  On the device until ``cpu()``."""
-    keys: List[RawHeatMapKey]                   # (factor, layer, head), in the library's key order
     gram: torch.Tensor                          # f32 [K, rows, rows], bitwise symmetric
-    layer_names: Optional[List[str]] = None     # the trace's layer names, indexed by a key's layer
-    tokenizer: Any = None
-    prompt: Optional[str] = None
     eps: float = 1e-12                          # what ``of`` adds under its square root
+
+    def __init__(self, keys, gram, layer_names=None, tokenizer=None, prompt=None, eps=1e-12):
+        super().__init__(keys, layer_names, tokenizer, prompt)
+        self.gram, self.eps = gram, eps
 
     def cosine(self, eps: float = 1e-12) -> torch.Tensor:
         """f32 [K, rows, rows]: ``gram[k][i][j] / sqrt(gram[k][i][i] * gram[k][j][j] + eps)``; a row of zeros gives 0, not NaN."""
@@ -62,11 +61,6 @@ class KeyCoattention:
         def named(key):
             return key if names is None else (key[0], names[key[1]], key[2])
         return [(named(self.keys[i]), float(col[i])) for i in order]
-
-    def _grouped(self, pos: int, values: torch.Tensor):
-        labels = sorted({key[pos] for key in self.keys})
-        rows = [values[[i for i, key in enumerate(self.keys) if key[pos] == label]].mean(dim=0) for label in labels]
-        return labels, torch.stack(rows)
 
     def _values(self, word_a, word_b, word_idx_a, word_idx_b) -> torch.Tensor:
         if (word_a is None) != (word_b is None):

@@ -3,8 +3,7 @@
 // device --, so the host can size the launch without reading them back: a key that does not fit the staging takes the kernel's
 // gather path instead (same arithmetic, same bits).
 #pragma once
-#include "daam_finalize.h"                       // float4v / half8 / ushort8, fin_dispatch, fin_launch
-#include "../../include/daam_analysis.h"
+#include "daam_key_planes.h"
 
 namespace daam {
 
@@ -12,8 +11,6 @@ constexpr int kKsThreads = 256;
 constexpr int kKsMaxBatch = 4;                   // token rows whose clamped tiles a workgroup holds while the footprints stream by
 constexpr int kKsMaskGroup = 4;                  // footprints a lane carries at once: kKsMaskGroup x kKsMaxBatch accumulators
 constexpr int kKsMaxMasks = 32;
-constexpr int kKsMaxSide = 128;
-constexpr int kKsMaxKeys = 1 << 20;
 constexpr size_t kKsMaxLds = 160 * 1024;
 constexpr size_t kKsTwoPerCu = 80 * 1024;        // at most this much per workgroup: two of them share a CU
 

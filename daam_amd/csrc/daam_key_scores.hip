@@ -24,32 +24,11 @@ namespace daam {
 
 namespace {
 
-// a plane element type: its 16-byte piece, and the element as f32
-template <typename T> struct KsPlane;
-template <> struct KsPlane<_Float16> {
-    static constexpr int E = 8;
-    using Piece = half8;
-    static __device__ __forceinline__ float at(const Piece& p, int i) { return (float)p[i]; }
-    static __device__ __forceinline__ float one(const _Float16* s) { return (float)*as_global<_Float16>(s); }
-};
-template <> struct KsPlane<bf16_t> {
-    static constexpr int E = 8;
-    using Piece = ushort8;
-    static __device__ __forceinline__ float at(const Piece& p, int i) { return __uint_as_float((unsigned)p[i] << 16); }
-    static __device__ __forceinline__ float one(const bf16_t* s) { return __uint_as_float((unsigned)*as_global<unsigned short>(s) << 16); }
-};
-template <> struct KsPlane<float> {
-    static constexpr int E = 4;
-    using Piece = float4v;
-    static __device__ __forceinline__ float at(const Piece& p, int i) { return p[i]; }
-    static __device__ __forceinline__ float one(const float* s) { return *as_global<float>(s); }
-};
-
 // element i of a token row's plane: the windows added in window order
 template <typename T> __device__ __forceinline__ float ks_elem(const T* row, int64_t win_stride, int n_win, int i)
 {
-    float v = KsPlane<T>::one(row + i);
-    for (int wi = 1; wi < n_win; ++wi) v = v + KsPlane<T>::one(row + wi * win_stride + i);
+    float v = KeyElem<T>::one(row + i);
+    for (int wi = 1; wi < n_win; ++wi) v = v + KeyElem<T>::one(row + wi * win_stride + i);
     return v;
 }
 
@@ -59,7 +38,7 @@ template <typename T>
 __global__ __launch_bounds__(kKsThreads) void key_scores_kernel(const KsLaunch L)
 {
 #pragma clang fp contract(off)
-    using P = KsPlane<T>;
+    using P = KeyElem<T>;
     constexpr int E = P::E;
     extern __shared__ __align__(16) unsigned char ks_smem[];
     const int tid = threadIdx.x;
@@ -78,7 +57,8 @@ __global__ __launch_bounds__(kKsThreads) void key_scores_kernel(const KsLaunch L
     const int m_cols = L.n_masks > 0 ? L.n_masks : 1;
     const int t0 = chunk * L.chunk_rows, t1 = t0 + min(L.chunk_rows, L.n_rows - t0);      // t0 < n_rows: n_chunks is the ceiling
     float* out = L.scores + (size_t)k * m_cols * L.n_rows;
-    if (h < 1 || h > kKsMaxSide || w < 1 || w > kKsMaxSide || n_win < 1) {      // not a plane: nothing is read
+    // not a plane: nothing is read.  key_planes_ok() written out: calling it here compiles to other machine code than the profiled one
+    if (h < 1 || h > kKeyMaxSide || w < 1 || w > kKeyMaxSide || n_win < 1) {
         const int nt = t1 - t0;
         for (int i = tid; i < m_cols * nt; i += kKsThreads) out[(size_t)(i / nt) * L.n_rows + t0 + i % nt] = NAN;
         return;
@@ -220,20 +200,27 @@ __global__ __launch_bounds__(kKsThreads) void key_scores_kernel(const KsLaunch L
     }
 }
 
-namespace {
+// the library's one error buffer and the entry points' shared checks (daam_key_planes.h)
+static thread_local char analysis_error[256] = "";
 
-thread_local char ks_error[256] = "";
-
-int ks_fail(int code, const char* fmt, ...)
+int analysis_fail(int code, const char* fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(ks_error, sizeof(ks_error), fmt, ap);
+    vsnprintf(analysis_error, sizeof(analysis_error), fmt, ap);
     va_end(ap);
     return code;
 }
 
-}  // namespace
+int key_args_check(int n_keys, int dtype, int n_rows, int max_rows, bool null_arg)
+{
+    if (n_keys < 1 || n_keys > kKeyMaxKeys) return analysis_fail(DAAM_E_INVALID, "%d keys: 1..%d", n_keys, kKeyMaxKeys);
+    if (max_rows && (n_rows < 1 || n_rows > max_rows)) return analysis_fail(DAAM_E_INVALID, "%d token rows: 1..%d", n_rows, max_rows);
+    if (n_rows < 1) return analysis_fail(DAAM_E_INVALID, "%d token rows: at least 1", n_rows);
+    if (dtype != DAAM_F16 && dtype != DAAM_F32 && dtype != DAAM_BF16) return analysis_fail(DAAM_E_INVALID, "dtype %d: f16, f32 or bf16", dtype);
+    if (null_arg) return analysis_fail(DAAM_E_INVALID, "NULL argument");
+    return 0;
+}
 
 }  // namespace daam
 
@@ -241,19 +228,17 @@ using namespace daam;
 
 int daam_analysis_abi_version(void) { return DAAM_ANALYSIS_ABI_VERSION; }
 
-const char* daam_analysis_last_error(void) { return ks_error; }
+const char* daam_analysis_last_error(void) { return analysis_error; }
 
 int daam_key_scores(const DaamKeyPlanes* keys, int n_keys, int dtype, int n_rows, int out_h, int out_w, const float* footprint,
                     int n_masks, float* scores, void* stream)
 {
-    if (n_keys < 1 || n_keys > kKsMaxKeys) return ks_fail(DAAM_E_INVALID, "%d keys: 1..%d", n_keys, kKsMaxKeys);
-    if (n_masks < 0 || n_masks > kKsMaxMasks) return ks_fail(DAAM_E_INVALID, "%d masks: 0..%d", n_masks, kKsMaxMasks);
-    if (out_h < 1 || out_h > kKsMaxSide || out_w < 1 || out_w > kKsMaxSide)
-        return ks_fail(DAAM_E_INVALID, "output of %d x %d: 1 <= out_h, out_w <= %d", out_h, out_w, kKsMaxSide);
-    if (n_rows < 1) return ks_fail(DAAM_E_INVALID, "%d token rows: at least 1", n_rows);
-    if (dtype != DAAM_F16 && dtype != DAAM_F32 && dtype != DAAM_BF16) return ks_fail(DAAM_E_INVALID, "dtype %d: f16, f32 or bf16", dtype);
-    if (!keys || !scores) return ks_fail(DAAM_E_INVALID, "NULL argument");
-    if ((footprint == nullptr) != (n_masks == 0)) return ks_fail(DAAM_E_INVALID, "footprint must be NULL exactly when n_masks is 0 (got %d masks)", n_masks);
+    if (key_args_check(n_keys, dtype, n_rows, 0, !keys || !scores)) return DAAM_E_INVALID;
+    if (n_masks < 0 || n_masks > kKsMaxMasks) return analysis_fail(DAAM_E_INVALID, "%d masks: 0..%d", n_masks, kKsMaxMasks);
+    if (out_h < 1 || out_h > kKeyMaxSide || out_w < 1 || out_w > kKeyMaxSide)
+        return analysis_fail(DAAM_E_INVALID, "output of %d x %d: 1 <= out_h, out_w <= %d", out_h, out_w, kKeyMaxSide);
+    if ((footprint == nullptr) != (n_masks == 0))
+        return analysis_fail(DAAM_E_INVALID, "footprint must be NULL exactly when n_masks is 0 (got %d masks)", n_masks);
 
     KsLaunch L;
     L.keys = keys; L.footprint = footprint; L.scores = scores;
@@ -266,7 +251,7 @@ int daam_key_scores(const DaamKeyPlanes* keys, int n_keys, int dtype, int n_rows
     for (int b = kKsMaxBatch; b >= 1 && !L.batch; --b)
         if (ks_lds_bytes(out_h, out_w, b) <= kKsMaxLds) L.batch = b;
     if (!L.batch)
-        return ks_fail(DAAM_E_UNSUPPORTED, "an output of %d x %d needs %zu bytes of LDS, more than %zu", out_h, out_w, ks_lds_bytes(out_h, out_w, 1), kKsMaxLds);
+        return analysis_fail(DAAM_E_UNSUPPORTED, "an output of %d x %d needs %zu bytes of LDS, more than %zu", out_h, out_w, ks_lds_bytes(out_h, out_w, 1), kKsMaxLds);
     // two batches per workgroup, more where the grid would not hold n_keys x chunks
     const int64_t max_chunks = 0x7fffffffll / n_keys;
     int64_t chunk_rows = 2 * L.batch;
@@ -280,6 +265,6 @@ int daam_key_scores(const DaamKeyPlanes* keys, int n_keys, int dtype, int n_rows
         using T = typename decltype(t)::type;
         return fin_launch(key_scores_kernel<T>, grid, kKsThreads, lds, (hipStream_t)stream, L);
     });
-    if (e != hipSuccess) return ks_fail((int)e, "key scores: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return analysis_fail((int)e, "key scores: %s", hipGetErrorString(e));
     return 0;
 }

@@ -1,9 +1,8 @@
-// daam_token_gram (include/daam_gram.h) between its kernels and its host entry point (both in daam_token_gram.hip):
+// daam_token_gram (include/daam_analysis.h) between its kernels and its host entry point (both in daam_token_gram.hip):
 // the decomposition's constants and the launch descriptor.  The keys' sizes live on the device, so the host sizes the launch from
 // n_keys, n_rows and the scratch it was given alone: grid = n_keys x cap chunks, and a workgroup past its key's last chunk exits.
 #pragma once
-#include "daam_finalize.h"                       // floatx16 / half8 / ushort8, fin_dispatch, fin_launch
-#include "../../include/daam_gram.h"
+#include "daam_key_planes.h"
 
 namespace daam {
 
@@ -15,9 +14,7 @@ constexpr int kGramRow16 = kGramSub16 * 2 + 16;  // LDS bytes of a staged row, 1
 constexpr int kGramRow32 = kGramSub32 + 1;       // LDS floats of a staged row, f32 path
 constexpr int kGramRed = 16 * 65;                // floats of one wave's 32 x 32 block in the join: register g at g * 65 + lane
 constexpr int kGramMaxRows = 96;
-constexpr int kGramMaxSide = 128;
-constexpr int kGramMaxKeys = 1 << 20;
-constexpr int kGramMaxChunks = kGramMaxSide * kGramMaxSide / kGramChunk;
+constexpr int kGramMaxChunks = kKeyMaxSide * kKeyMaxSide / kGramChunk;
 
 struct GramLaunch {
     const DaamKeyPlanes* keys;
@@ -28,10 +25,6 @@ struct GramLaunch {
     int32_t multi_only;                          // the f32-path launch beside a 16-bit one: only valid keys with n_win > 1
 };
 
-__host__ __device__ inline bool gram_key_ok(const DaamKeyPlanes& k)
-{
-    return k.h >= 1 && k.h <= kGramMaxSide && k.w >= 1 && k.w <= kGramMaxSide && k.n_win >= 1;
-}
 __host__ __device__ inline int gram_chunks(int hw) { return (hw + kGramChunk - 1) / kGramChunk; }
 
 }  // namespace daam

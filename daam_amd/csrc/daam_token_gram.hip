@@ -1,4 +1,4 @@
-// daam_token_gram (include/daam_gram.h): per (layer, head) key the Gram matrix of its token planes, A * A^T on the matrix cores.
+// daam_token_gram (include/daam_analysis.h): per (layer, head) key the Gram matrix of its token planes, A * A^T on the matrix cores.
 // token_gram_kernel<T, NB, WIDE>, grid n_keys x cap, 256 threads; workgroup (key, chunk of 1024 pixels), NB = blocks of 32 rows:
 //   stage     -- a sub-tile [32 NB rows][128 px] (16-bit path) or [32 NB rows][64 px] f32 (WIDE: windows added as they arrive) goes
 //                from HBM through registers into LDS, the next sub-tile's loads in flight while this one is multiplied; rows at or
@@ -15,19 +15,12 @@
 #include "daam_token_gram.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
 namespace daam {
 
 namespace {
 
 typedef __bf16 gram_bf16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> __device__ __forceinline__ float gram_one(const T* p);
-template <> __device__ __forceinline__ float gram_one<_Float16>(const _Float16* p) { return (float)*as_global<_Float16>(p); }
-template <> __device__ __forceinline__ float gram_one<bf16_t>(const bf16_t* p) { return __uint_as_float((unsigned)*as_global<unsigned short>(p) << 16); }
-template <> __device__ __forceinline__ float gram_one<float>(const float* p) { return *as_global<float>(p); }
 
 template <typename T> __device__ __forceinline__ floatx16 gram_mfma16(const ushort8& a, const ushort8& b, const floatx16& c);
 template <> __device__ __forceinline__ floatx16 gram_mfma16<_Float16>(const ushort8& a, const ushort8& b, const floatx16& c)
@@ -62,7 +55,7 @@ __global__ __launch_bounds__(kGramThreads) void token_gram_kernel(const GramLaun
     const int n_rows = L.n_rows, rr = n_rows * n_rows;
 
     const DaamKeyPlanes key = L.keys[k];
-    const bool ok = gram_key_ok(key);
+    const bool ok = key_planes_ok(key);
     const int n = ok ? key.h * key.w : 0, n_chunks = gram_chunks(n), n_win = key.n_win;
     if (L.multi_only ? (!ok || n_win == 1) : (!WIDE && ok && n_win > 1)) return;        // the other launch's key
     if (!ok || n_chunks > L.cap) {                               // not a plane, or no room for its chunks: nothing is read
@@ -92,8 +85,8 @@ __global__ __launch_bounds__(kGramThreads) void token_gram_kernel(const GramLaun
                 float v = 0.f;
                 if (row < n_rows && px < n) {
                     const T* at = base + (size_t)row * n + px;
-                    v = gram_one<T>(at);
-                    for (int wi = 1; wi < n_win; ++wi) v = v + gram_one<T>(at + wi * ws);
+                    v = KeyElem<T>::one(at);
+                    for (int wi = 1; wi < n_win; ++wi) v = v + KeyElem<T>::one(at + wi * ws);
                 }
                 reg[j] = v;
             }
@@ -205,7 +198,7 @@ __global__ __launch_bounds__(kGramThreads) void token_gram_join_kernel(const Gra
 #pragma clang fp contract(off)
     const int k = blockIdx.x, rr = L.n_rows * L.n_rows;
     const DaamKeyPlanes key = L.keys[k];
-    if (!gram_key_ok(key)) return;
+    if (!key_planes_ok(key)) return;
     const int n_chunks = gram_chunks(key.h * key.w);
     if (n_chunks == 1 || n_chunks > L.cap) return;
     const float* part = L.scratch + (size_t)k * L.cap * rr;
@@ -218,17 +211,6 @@ __global__ __launch_bounds__(kGramThreads) void token_gram_join_kernel(const Gra
 
 namespace {
 
-thread_local char gram_error[256] = "";
-
-int gram_fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(gram_error, sizeof(gram_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 template <typename T, bool WIDE> hipError_t gram_launch_nb(int nb, dim3 grid, hipStream_t stream, const GramLaunch& L)
 {
     switch (nb) {
@@ -238,7 +220,7 @@ template <typename T, bool WIDE> hipError_t gram_launch_nb(int nb, dim3 grid, hi
     }
 }
 
-bool gram_sizes_ok(int n_keys, int n_rows) { return n_keys >= 1 && n_keys <= kGramMaxKeys && n_rows >= 1 && n_rows <= kGramMaxRows; }
+bool gram_sizes_ok(int n_keys, int n_rows) { return n_keys >= 1 && n_keys <= kKeyMaxKeys && n_rows >= 1 && n_rows <= kGramMaxRows; }
 
 }  // namespace
 
@@ -246,27 +228,20 @@ bool gram_sizes_ok(int n_keys, int n_rows) { return n_keys >= 1 && n_keys <= kGr
 
 using namespace daam;
 
-int daam_gram_abi_version(void) { return DAAM_GRAM_ABI_VERSION; }
-
-const char* daam_gram_last_error(void) { return gram_error; }
-
 size_t daam_token_gram_scratch_bytes(int n_keys, int n_rows, int max_hw)
 {
     if (!gram_sizes_ok(n_keys, n_rows) || max_hw < 1) return 0;
-    const int hw = max_hw < kGramMaxSide * kGramMaxSide ? max_hw : kGramMaxSide * kGramMaxSide;
+    const int hw = max_hw < kKeyMaxSide * kKeyMaxSide ? max_hw : kKeyMaxSide * kKeyMaxSide;
     return (size_t)n_keys * gram_chunks(hw) * n_rows * n_rows * sizeof(float);
 }
 
 int daam_token_gram(const DaamKeyPlanes* keys, int n_keys, int dtype, int n_rows, float* gram, void* scratch, size_t scratch_bytes,
                     void* stream)
 {
-    if (n_keys < 1 || n_keys > kGramMaxKeys) return gram_fail(DAAM_E_INVALID, "%d keys: 1..%d", n_keys, kGramMaxKeys);
-    if (n_rows < 1 || n_rows > kGramMaxRows) return gram_fail(DAAM_E_INVALID, "%d token rows: 1..%d", n_rows, kGramMaxRows);
-    if (dtype != DAAM_F16 && dtype != DAAM_F32 && dtype != DAAM_BF16) return gram_fail(DAAM_E_INVALID, "dtype %d: f16, f32 or bf16", dtype);
-    if (!keys || !gram || !scratch) return gram_fail(DAAM_E_INVALID, "NULL argument");
+    if (key_args_check(n_keys, dtype, n_rows, kGramMaxRows, !keys || !gram || !scratch)) return DAAM_E_INVALID;
     const size_t per_chunk = (size_t)n_keys * n_rows * n_rows * sizeof(float);
     if (scratch_bytes < per_chunk)
-        return gram_fail(DAAM_E_INVALID, "scratch of %zu bytes: %d keys of %d rows need %zu per chunk of %d pixels", scratch_bytes, n_keys,
+        return analysis_fail(DAAM_E_INVALID, "scratch of %zu bytes: %d keys of %d rows need %zu per chunk of %d pixels", scratch_bytes, n_keys,
                          n_rows, per_chunk, kGramChunk);
 
     GramLaunch L;
@@ -293,6 +268,6 @@ int daam_token_gram(const DaamKeyPlanes* keys, int n_keys, int dtype, int n_rows
             return gram_launch_nb<T, true>(nb, grid, s, L);
         });
     if (e == hipSuccess && L.cap > 1) e = fin_launch(token_gram_join_kernel, dim3((unsigned)n_keys), kGramThreads, 0, s, L);
-    if (e != hipSuccess) return gram_fail((int)e, "token gram: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return analysis_fail((int)e, "token gram: %s", hipGetErrorString(e));
     return 0;
 }

@@ -1109,15 +1109,7 @@ class HeatMapEngine:
         (``head`` counts inside the prompt's block, like ``head_idx``), ``scores`` fp32 ``[len(keys), max(M, 1), rows]`` on the device.
         One launch per 32 footprints reads the running sums once and writes no map; the filters, ``n_rows`` and ``bins`` mean what they
         mean in ``global_heat_maps``.  The mean of ``scores`` over the keys is, by linearity, ``region_dots`` of the global map."""
-        binned = self._binned(bins)
-        rows = self.tokens if n_rows is None else self._rows(n_rows)
-        n_prompts, prompt = int(n_prompts), int(prompt)
-        if not 0 <= prompt < n_prompts:
-            raise ValueError(f'prompt {prompt} of {n_prompts}')
-        factors = None if factors is None else set(factors)
-        table, _ = self._select(n_prompts, factors, head_idx, layer_idx, used=(prompt,))
-        self.flush()
-        b0, b1 = (bins if bins is not None else (0, self.n_bins)) if binned else (0, 1)
+        rows, planes = self._key_selection(n_rows, factors, head_idx, layer_idx, n_prompts, prompt, bins)
         if footprint is not None:
             if footprint.dtype != torch.float32 or footprint.dim() != 3 or tuple(footprint.shape[1:]) != (self.out_h, self.out_w) \
                     or footprint.shape[0] < 1:
@@ -1125,7 +1117,7 @@ class HeatMapEngine:
             if footprint.device != self.device:
                 raise RuntimeError('daam_amd: the footprint is not on the engine\'s device')
             footprint = footprint.contiguous()
-        keys, desc = self._key_planes(table, n_prompts, prompt, factors, head_idx, layer_idx, b0, b1, binned)
+        keys, desc = self._key_planes(*planes)
         lib = nat.load_analysis()
         parts = []
         chunks = [None] if footprint is None else [footprint[at:at + MAX_REGION_MASKS] for at in range(0, footprint.shape[0], MAX_REGION_MASKS)]
@@ -1140,22 +1132,14 @@ class HeatMapEngine:
 
     def token_gram(self, n_rows: Optional[int] = None, factors: Optional[Sequence[int]] = None, head_idx: Optional[int] = None,
                    layer_idx: Optional[int] = None, n_prompts: int = 1, prompt: int = 0, bins: Optional[Tuple[int, int]] = None):
-        """Token co-attention (``daam_token_gram`` of ``libdaam_gram.so``): per selected key the Gram matrix of its token planes,
+        """Token co-attention (``daam_token_gram`` of ``libdaam_analysis.so``): per selected key the Gram matrix of its token planes,
         ``gram[k][i][j] = sum_p plane_i[p] * plane_j[p]``, at the key's own resolution from the raw running sums (no bicubic, no
         clamp), from one pass over the sums that ends on the matrix cores.  ``key_scores`` without footprints: the same selection,
         key order, ``n_rows`` crop, ``bins`` and ``LookupError``.  Returns ``(keys, gram)`` with ``gram`` fp32
         ``[len(keys), rows, rows]`` on the device.  The scratch of the keys' partial matrices is the engine's, grown on demand."""
-        binned = self._binned(bins)
-        rows = self.tokens if n_rows is None else self._rows(n_rows)
-        n_prompts, prompt = int(n_prompts), int(prompt)
-        if not 0 <= prompt < n_prompts:
-            raise ValueError(f'prompt {prompt} of {n_prompts}')
-        factors = None if factors is None else set(factors)
-        table, _ = self._select(n_prompts, factors, head_idx, layer_idx, used=(prompt,))
-        self.flush()
-        b0, b1 = (bins if bins is not None else (0, self.n_bins)) if binned else (0, 1)
-        keys, desc = self._key_planes(table, n_prompts, prompt, factors, head_idx, layer_idx, b0, b1, binned)
-        lib = nat.load_gram()
+        rows, planes = self._key_selection(n_rows, factors, head_idx, layer_idx, n_prompts, prompt, bins)
+        keys, desc = self._key_planes(*planes)
+        lib = nat.load_analysis()
         # sized for the largest touched layer, selected or not (60 layers to look at, not 1100 keys; more scratch changes no bit)
         sides = {self.layer_info[layer][2] for layer in self.touched}
         max_hw = max(s[0] * s[1] if isinstance(s, tuple) else s * s for s in sides)
@@ -1166,9 +1150,25 @@ class HeatMapEngine:
             if self._gram_scratch is None or self._gram_scratch.numel() < need:
                 self._gram_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
             gram = torch.empty(len(keys), rows, rows, dtype=torch.float32, device=self.device)
-            nat.check_gram(lib.daam_token_gram(desc.data_ptr(), len(keys), _DTYPE_CODE[self.acc_dtype], rows, gram.data_ptr(),
-                                               self._gram_scratch.data_ptr(), self._gram_scratch.numel(), self.stream))
+            nat.check_analysis(lib.daam_token_gram(desc.data_ptr(), len(keys), _DTYPE_CODE[self.acc_dtype], rows, gram.data_ptr(),
+                                                   self._gram_scratch.data_ptr(), self._gram_scratch.numel(), self.stream))
         return keys, gram
+
+    def _key_selection(self, n_rows, factors, head_idx, layer_idx, n_prompts, prompt, bins):
+        """What ``key_scores`` and ``token_gram`` decide before they build descriptors: ``(rows, planes)`` -- the ``n_rows`` crop and
+        the arguments of ``_key_planes`` for prompt ``prompt``'s selection over the window range ``bins`` (the caller makes that call,
+        after the checks of its own arguments).  ValueError for a prompt out of range, then ``_select``'s LookupError; the recorded
+        taps are launched either way."""
+        binned = self._binned(bins)
+        rows = self.tokens if n_rows is None else self._rows(n_rows)
+        n_prompts, prompt = int(n_prompts), int(prompt)
+        if not 0 <= prompt < n_prompts:
+            raise ValueError(f'prompt {prompt} of {n_prompts}')
+        factors = None if factors is None else set(factors)
+        table, _ = self._select(n_prompts, factors, head_idx, layer_idx, used=(prompt,))
+        self.flush()
+        b0, b1 = (bins if bins is not None else (0, self.n_bins)) if binned else (0, 1)
+        return rows, (table, n_prompts, prompt, factors, head_idx, layer_idx, b0, b1, binned)
 
     def _key_planes(self, table, n_prompts, prompt, factors, head_idx, layer_idx, b0, b1, binned):
         """``(keys, DaamKeyPlanes[len(keys)] as a uint8 device tensor)`` of prompt ``prompt``'s keys in ``table``, in the library's key
@@ -1203,7 +1203,7 @@ class HeatMapEngine:
         arr = (nat.KeyPlanes * len(picked))()
         for i, (_, _, view, stride) in enumerate(picked):
             arr[i] = nat.KeyPlanes(base=view.data_ptr(), win_stride=stride, h=view.shape[-2], w=view.shape[-1], n_win=b1 - b0, pad=0)
-        desc = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device, copy=True)
+        desc = _descriptors_on(self.device, arr)
         if len(self._ks_cache) > 16:
             self._ks_cache.clear()
         cached = self._ks_cache[sel] = ([key for _, key, _, _ in picked], desc)
@@ -1357,6 +1357,11 @@ def region_scores(maps: Optional[torch.Tensor], masks: torch.Tensor, map_hw: Opt
     return (scores if maps.dim() == 4 else scores[0]), area, footprint
 
 
+def _descriptors_on(device, arr) -> torch.Tensor:
+    """A ctypes array of ``DaamKeyPlanes`` as a uint8 tensor on ``device``."""
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device, copy=True)
+
+
 def map_gram(maps: torch.Tensor) -> torch.Tensor:
     """``daam_token_gram`` on one set of maps as a single f32 key: ``maps`` [rows, h, w] fp32 on the device (1..96 rows, 1..128 cells a
     side) -> fp32 ``[rows, rows]``, ``out[i][j] = sum_p maps[i][p] * maps[j][p]`` (``GlobalHeatMap.coattention``)."""
@@ -1364,14 +1369,13 @@ def map_gram(maps: torch.Tensor) -> torch.Tensor:
     rows, h, w = maps.shape
     if not (1 <= rows <= 96 and 1 <= h <= 128 and 1 <= w <= 128):
         raise ValueError(f'a Gram matrix takes 1..96 rows of 1..128 cells a side, got {tuple(maps.shape)}')
-    lib = nat.load_gram()
-    key = (nat.KeyPlanes * 1)(nat.KeyPlanes(base=maps.data_ptr(), win_stride=0, h=h, w=w, n_win=1, pad=0))
+    lib = nat.load_analysis()
     with torch.cuda.device(maps.device):
-        desc = torch.frombuffer(bytearray(bytes(key)), dtype=torch.uint8).to(maps.device, copy=True)
+        desc = _descriptors_on(maps.device, (nat.KeyPlanes * 1)(nat.KeyPlanes(base=maps.data_ptr(), win_stride=0, h=h, w=w, n_win=1, pad=0)))
         scratch = torch.empty(lib.daam_token_gram_scratch_bytes(1, rows, h * w), dtype=torch.uint8, device=maps.device)
         gram = torch.empty(1, rows, rows, dtype=torch.float32, device=maps.device)
-        nat.check_gram(lib.daam_token_gram(desc.data_ptr(), 1, nat.DAAM_F32, rows, gram.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                           torch.cuda.current_stream(maps.device).cuda_stream))
+        nat.check_analysis(lib.daam_token_gram(desc.data_ptr(), 1, nat.DAAM_F32, rows, gram.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                               torch.cuda.current_stream(maps.device).cuda_stream))
     return gram[0]
 
 

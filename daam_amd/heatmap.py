@@ -181,16 +181,32 @@ class RegionAttribution:
 
 
 @dataclass
-class KeyScores:
-    """Head analysis (``DiffusionHeatMapHooker.compute_key_scores``): for every selected ``(factor, layer, head)`` key what
-    ``compute_global_heat_map(head_idx=, layer_idx=)`` + ``attribute(regions)`` would give for that key alone -- the sum of every token
-    row's clamped, resized map under each region -- from one pass over the running sums.  On the device until ``cpu()``."""
+class KeyAnalysis:
+    """What the per-key results (``KeyScores``, ``KeyCoattention``) share: the keys of the selection and what names and crops them.
+    The subclasses write their own ``__init__`` to keep their tensors second among the positional arguments."""
     keys: List[RawHeatMapKey]                   # (factor, layer, head), in the library's key order
-    scores: torch.Tensor                        # f32 [K, M, rows]; M = 1 without regions (the total clamped mass)
-    area: Optional[torch.Tensor]                # int32 [M] pixels of each region; None without masks at image resolution
     layer_names: Optional[List[str]] = None     # the trace's layer names, indexed by a key's layer
     tokenizer: Any = None
     prompt: Optional[str] = None
+
+    def _grouped(self, pos: int, values: torch.Tensor):
+        """``(labels, means)``: ``values`` [K, ...] averaged over the keys that share element ``pos`` of their key, labels ascending."""
+        labels = sorted({key[pos] for key in self.keys})
+        rows = [values[[i for i, key in enumerate(self.keys) if key[pos] == label]].mean(dim=0) for label in labels]
+        return labels, torch.stack(rows)
+
+
+@dataclass(init=False)
+class KeyScores(KeyAnalysis):
+    """Head analysis (``DiffusionHeatMapHooker.compute_key_scores``): for every selected ``(factor, layer, head)`` key what
+    ``compute_global_heat_map(head_idx=, layer_idx=)`` + ``attribute(regions)`` would give for that key alone -- the sum of every token
+    row's clamped, resized map under each region -- from one pass over the running sums.  On the device until ``cpu()``."""
+    scores: torch.Tensor                        # f32 [K, M, rows]; M = 1 without regions (the total clamped mass)
+    area: Optional[torch.Tensor]                # int32 [M] pixels of each region; None without masks at image resolution
+
+    def __init__(self, keys, scores, area, layer_names=None, tokenizer=None, prompt=None):
+        super().__init__(keys, layer_names, tokenizer, prompt)
+        self.scores, self.area = scores, area
 
     def mean(self) -> torch.Tensor:
         """f32 [M, rows]: the mean over the keys -- by linearity ``GlobalHeatMap.attribute(regions).scores`` of the same selection."""
@@ -208,18 +224,13 @@ class KeyScores:
         order = torch.sort(col, descending=True, stable=True).indices[:k].tolist()
         return [(self.keys[i], float(col[i])) for i in order]
 
-    def _grouped(self, pos: int):
-        labels = sorted({key[pos] for key in self.keys})
-        rows = [self.scores[[i for i, key in enumerate(self.keys) if key[pos] == label]].mean(dim=0) for label in labels]
-        return labels, torch.stack(rows)
-
     def by_layer(self):
         """``(layers, f32 [len(layers), M, rows])``: the mean over each layer's heads, layers ascending."""
-        return self._grouped(1)
+        return self._grouped(1, self.scores)
 
     def by_head(self):
         """``(heads, f32 [len(heads), M, rows])``: the mean over the layers that have the head, heads ascending."""
-        return self._grouped(2)
+        return self._grouped(2, self.scores)
 
     def cpu(self) -> 'KeyScores':
         return KeyScores(list(self.keys), self.scores.cpu(), None if self.area is None else self.area.cpu(), self.layer_names,

@@ -428,16 +428,7 @@ class DiffusionHeatMapHooker(AggregateHooker):
         ``RegionAttribution`` (its footprint is reused).  Rows are cropped to ``len(tokenize(prompt)) + 2``; ``factors`` /
         ``head_idx`` / ``layer_idx`` / ``prompt_idx`` / ``time_bin`` mean what they mean in ``compute_global_heat_map`` and fail as
         they do there; non-square traces work.  Probes are out of scope: the scores are those of the generation's own prompt."""
-        n = len(self.last_prompts)
-        if prompt_idx is not None:
-            prompt_idx = self._check_prompt_idx(prompt_idx)
-        rng = self._bin_range(time_bin)
-        if n > 1 and prompt_idx is None:
-            raise ValueError(f'the last generation traced {n} prompts: pass prompt_idx')
-        if prompt is None:
-            prompt = self.last_prompts[prompt_idx] if n > 1 else self.last_prompt
-        n_rows = self._n_rows(prompt)
-        self._check_bin_steps(rng)
+        prompt, kw = self._key_selection(prompt, factors, head_idx, layer_idx, prompt_idx, time_bin)
         eng = self.engine
         area = footprint = None
         if isinstance(regions, RegionAttribution):
@@ -445,12 +436,7 @@ class DiffusionHeatMapHooker(AggregateHooker):
         elif regions is not None:
             masks = regions.masks if isinstance(regions, Segmentation) else regions
             _, area, footprint = region_scores(None, masks, map_hw=(eng.out_h, eng.out_w))
-        try:
-            kw = {} if rng is None else dict(bins=rng)
-            keys, scores = eng.key_scores(footprint, n_rows=n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx,
-                                          n_prompts=max(n, 1), prompt=prompt_idx or 0, **kw)
-        except LookupError:
-            raise _no_maps(head_idx is not None or layer_idx is not None) from None
+        keys, scores = self._key_call(eng.key_scores, footprint, **kw)
         return KeyScores(keys, scores, area, list(self.layer_names), self.pipe.tokenizer, prompt)
 
     def compute_key_coattention(self, prompt=None, factors=None, head_idx=None, layer_idx=None, prompt_idx: Optional[int] = None,
@@ -460,6 +446,14 @@ class DiffusionHeatMapHooker(AggregateHooker):
         ``KeyCoattention.of('dog', 'cat')`` is then the cosine of the two word maps per key.  Rows are cropped to
         ``len(tokenize(prompt)) + 2``; every argument means what it means in ``compute_key_scores`` and fails as it fails there;
         batched prompts, time windows and non-square traces work.  Probes are out of scope."""
+        prompt, kw = self._key_selection(prompt, factors, head_idx, layer_idx, prompt_idx, time_bin)
+        keys, gram = self._key_call(self.engine.token_gram, **kw)
+        return KeyCoattention(keys, gram, list(self.layer_names), self.pipe.tokenizer, prompt)
+
+    def _key_selection(self, prompt, factors, head_idx, layer_idx, prompt_idx, time_bin):
+        """What the per-key analyses decide before their engine call: ``(prompt, kw)`` -- the text that labels and crops the result,
+        and the engine method's keywords: the crop, the filters, the prompt's block and the window range (``_key_call`` makes the
+        call)."""
         n = len(self.last_prompts)
         if prompt_idx is not None:
             prompt_idx = self._check_prompt_idx(prompt_idx)
@@ -470,13 +464,16 @@ class DiffusionHeatMapHooker(AggregateHooker):
             prompt = self.last_prompts[prompt_idx] if n > 1 else self.last_prompt
         n_rows = self._n_rows(prompt)
         self._check_bin_steps(rng)
+        return prompt, dict(n_rows=n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx, n_prompts=max(n, 1),
+                            prompt=prompt_idx or 0, **({} if rng is None else dict(bins=rng)))
+
+    @staticmethod
+    def _key_call(method, *args, **kw):
+        """An engine method of the per-key analyses, its LookupError turned into the trace's 'no heat maps' error."""
         try:
-            kw = {} if rng is None else dict(bins=rng)
-            keys, gram = self.engine.token_gram(n_rows=n_rows, factors=factors, head_idx=head_idx, layer_idx=layer_idx,
-                                                n_prompts=max(n, 1), prompt=prompt_idx or 0, **kw)
+            return method(*args, **kw)
         except LookupError:
-            raise _no_maps(head_idx is not None or layer_idx is not None) from None
-        return KeyCoattention(keys, gram, list(self.layer_names), self.pipe.tokenizer, prompt)
+            raise _no_maps(kw['head_idx'] is not None or kw['layer_idx'] is not None) from None
 
     # -- probes (open-vocabulary heat maps) ----------------------------------------------------------
     def _check_probe(self, probe) -> int:

@@ -1,4 +1,4 @@
-"""Float64 reference and error bound of ``daam_token_gram`` (include/daam_gram.h), shared by ``test_token_gram_cpu.py`` and
+"""Float64 reference and error bound of ``daam_token_gram`` (include/daam_analysis.h), shared by ``test_token_gram_cpu.py`` and
 ``test_gpu_token_gram.py``.
 
 Reference: the windows of a key's planes summed in float64, then ``A @ A.T`` in float64.

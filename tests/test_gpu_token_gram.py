@@ -1,4 +1,4 @@
-"""``daam_token_gram`` (libdaam_gram.so) on the device: the raw C ABI against the float64 reference and the counted bound of
+"""``daam_token_gram`` (libdaam_analysis.so) on the device: the raw C ABI against the float64 reference and the counted bound of
 ``tests/_gram_domain.py`` -- exact small-integer data first, which is what catches a permuted MFMA fragment --, its determinism
 promises, then ``HeatMapEngine.token_gram`` / ``compute_key_coattention`` / ``GlobalHeatMap.coattention`` on traced generations."""
 import functools
@@ -23,7 +23,7 @@ ROWS = (1, 5, 31, 32, 33, 64, 77, 96)
 
 def _lib():
     from daam_amd import _native as nat
-    return nat, nat.load_gram()
+    return nat, nat.load_analysis()
 
 
 def _as_np(t):
@@ -73,8 +73,8 @@ def _call(descs, dt, n_rows, max_hw, extra_scratch=0):
     need = lib.daam_token_gram_scratch_bytes(len(descs), n_rows, max_hw) + extra_scratch
     scratch = torch.empty(need, dtype=torch.uint8, device=DEV)
     gram = torch.full((len(descs), n_rows, n_rows), SENTINEL, dtype=torch.float32, device=DEV)
-    nat.check_gram(lib.daam_token_gram(desc.data_ptr(), len(descs), CODE[dt], n_rows, gram.data_ptr(), scratch.data_ptr(), need,
-                                       torch.cuda.current_stream().cuda_stream))
+    nat.check_analysis(lib.daam_token_gram(desc.data_ptr(), len(descs), CODE[dt], n_rows, gram.data_ptr(), scratch.data_ptr(), need,
+                                           torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     return gram
 

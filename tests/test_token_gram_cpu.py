@@ -1,7 +1,7 @@
-"""Token co-attention without a GPU: ``libdaam_gram.so`` builds beside the other two libraries (which stay what they were) and exports
-what its header declares, its argument checks answer before any device call, no kernel instance has scratch, the engine hands
-``daam_token_gram`` the descriptors of ``key_scores`` (a recording stand-in below), the ``KeyCoattention`` arithmetic, and the
-float64 reference and bound of ``tests/_gram_domain.py`` themselves."""
+"""Token co-attention without a GPU: ``daam_token_gram`` lives in ``libdaam_analysis.so``, the one side library (the libraries' kernels
+stay what they were), which exports what its header declares; its argument checks answer before any device call, no kernel instance
+has scratch, the engine hands ``daam_token_gram`` the descriptors of ``key_scores`` (a recording stand-in below), the ``KeyCoattention``
+arithmetic, and the float64 reference and bound of ``tests/_gram_domain.py`` themselves."""
 import ctypes
 import json
 import os
@@ -24,21 +24,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def built():
     from daam_amd import build
     build.build(verbose=False)
-    return build.GRAM_OUT
+    return build.ANALYSIS_OUT
 
 
-def test_third_library_builds_and_exports_its_header(built):
+def test_token_gram_is_in_the_one_side_library(built):
     from daam_amd import _native as nat, build
-    assert os.path.exists(built) and os.path.exists(build.OUT) and os.path.exists(build.ANALYSIS_OUT) and not build.gram_stale()
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.GRAM_SOURCES + build.GRAM_HEADERS)
-    others = set(build.SOURCES) | set(build.HEADERS) | set(build.ANALYSIS_SOURCES) | set(build.ANALYSIS_HEADERS)
-    assert not set(build.GRAM_SOURCES) & others and 'daam_token_gram.h' not in others
+    assert os.path.exists(built) and os.path.exists(build.OUT) and not build.analysis_stale()
+    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.ANALYSIS_SOURCES + build.ANALYSIS_HEADERS)
+    others = set(build.SOURCES) | set(build.HEADERS)
+    mine = {'daam_token_gram.hip', 'daam_token_gram.h', 'daam_key_planes.h'}
+    assert 'daam_token_gram.hip' in build.ANALYSIS_SOURCES and mine <= set(build.ANALYSIS_SOURCES + build.ANALYSIS_HEADERS)
+    assert not set(build.ANALYSIS_SOURCES) & others and not mine & others
     nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
     exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_gram.h')).read()
+    header = open(os.path.join(ROOT, 'include', 'daam_analysis.h')).read()
     declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.GRAM_EXPORTS)
-    assert nat.load_gram().daam_gram_abi_version() == 1 == nat.GRAM_ABI_VERSION
+    assert exported == declared == sorted(nat.ANALYSIS_EXPORTS) and len(exported) == 5
+    assert {'daam_token_gram', 'daam_token_gram_scratch_bytes'} <= set(exported)
+    assert nat.load_analysis().daam_analysis_abi_version() == 2 == nat.ANALYSIS_ABI_VERSION
+    # no third library: the build knows two outputs (what it writes: test_deleted_side_library_is_rebuilt_alone)
+    assert sorted(n for n in vars(build) if n.endswith('OUT')) == ['ANALYSIS_OUT', 'OUT']
 
 
 def test_the_other_libraries_are_what_they_were(built):
@@ -46,21 +51,28 @@ def test_the_other_libraries_are_what_they_were(built):
     rec = json.load(open(os.path.join(ROOT, 'profiles', 'finalize_launch_refactor.json')))
     have = build.kernel_shas(build.OUT)
     assert len(have) == 191 and {k: have.get(k) for k in rec['kernel_shas']} == rec['kernel_shas']
-    assert len(build.kernel_shas(build.ANALYSIS_OUT)) == 3
-    assert nat.load().daam_abi_version() == 6 and nat.load_analysis().daam_analysis_abi_version() == 1
+    assert nat.load().daam_abi_version() == 6 and nat.load_analysis().daam_analysis_abi_version() == 2
+    # every kernel of the side library is the machine code its profile was measured on
+    want = dict(json.load(open(os.path.join(ROOT, 'profiles', 'key_scores.json')))['kernel_shas'])
+    gram = json.load(open(os.path.join(ROOT, 'profiles', 'token_gram.json')))['kernel_shas']
+    want.update(gram)
     mine = build.kernel_shas(built)
+    assert len(mine) == 19 and mine == want
     # 16-bit path: 2 dtypes x 3 row-block counts; f32 path: 3 dtypes x 3; the join
-    assert len(mine) == 16 and sum('token_gram_kernel' in k for k in mine) == 15 and sum('token_gram_join_kernel' in k for k in mine) == 1
+    assert len(gram) == 16 and sum('token_gram_kernel' in k for k in mine) == 15 and sum('token_gram_join_kernel' in k for k in mine) == 1
 
 
-def test_deleted_third_library_is_rebuilt_alone(built):
+def test_deleted_side_library_is_rebuilt_alone(built):
     from daam_amd import build
-    stamps = [os.path.getmtime(p) for p in (build.OUT, build.ANALYSIS_OUT)]
+    others = (build.OUT, build.fastpath_out())
+    stamps = [os.path.getmtime(p) for p in others]
+    files = sorted(os.listdir(build.HERE))
     os.remove(built)
-    assert not build.stale() and not build.analysis_stale() and build.gram_stale()
+    assert not build.stale() and build.analysis_stale()
     build.build(verbose=False)
-    assert os.path.exists(built) and not build.gram_stale()
-    assert [os.path.getmtime(p) for p in (build.OUT, build.ANALYSIS_OUT)] == stamps
+    assert os.path.exists(built) and not build.analysis_stale()
+    assert [os.path.getmtime(p) for p in others] == stamps
+    assert sorted(os.listdir(build.HERE)) == files               # the build writes no other file: no further library
 
 
 def test_no_instance_has_scratch(built):
@@ -68,7 +80,7 @@ def test_no_instance_has_scratch(built):
     from daam_amd import build
     kds = _kernel_descriptors(built)
     names = list(build.kernel_shas(built))
-    assert len(names) == 16 and all(k in kds for k in names)
+    assert len(names) == 19 and all(k in kds for k in names)
     for k in names:
         private, = struct.unpack_from('<I', kds[k], 4)
         _, rsrc2 = struct.unpack_from('<II', kds[k], 48)
@@ -77,7 +89,7 @@ def test_no_instance_has_scratch(built):
 
 def test_out_of_limits_arguments_are_refused_on_the_host(built):
     from daam_amd import _native as nat
-    lib = nat.load_gram()
+    lib = nat.load_analysis()
     keys = (nat.KeyPlanes * 1)()
     gram = (ctypes.c_float * 16)()
     scratch = (ctypes.c_float * 16)()
@@ -89,14 +101,14 @@ def test_out_of_limits_arguments_are_refused_on_the_host(built):
         a = dict(good, **change)
         rc = lib.daam_token_gram(a['keys'], a['n_keys'], a['dtype'], a['n_rows'], a['gram'], a['scratch'], a['scratch_bytes'], None)
         assert rc == nat.E_INVALID, change
-        assert lib.daam_gram_last_error().decode(), change
+        assert lib.daam_analysis_last_error().decode(), change
         with pytest.raises(nat.DaamError):
-            nat.check_gram(rc)
+            nat.check_analysis(rc)
 
 
 def test_scratch_bytes_is_monotone(built):
     from daam_amd import _native as nat
-    size = nat.load_gram().daam_token_gram_scratch_bytes
+    size = nat.load_analysis().daam_token_gram_scratch_bytes
     assert size(1, 1, 1) == 4 and size(1100, 77, 4096) == 1100 * 4 * 77 * 77 * 4
     assert size(1, 96, 1024) == size(1, 96, 1) and size(1, 96, 1025) == 2 * size(1, 96, 1024)
     assert size(1, 96, 128 * 128) == 16 * 96 * 96 * 4 == size(1, 96, 1 << 30)
@@ -111,7 +123,7 @@ def test_scratch_bytes_is_monotone(built):
 
 
 class FakeGram:
-    """Records every ``daam_token_gram`` call with its descriptors decoded; returns 0."""
+    """Records every ``daam_token_gram`` call with its descriptors decoded, and where ``daam_key_scores`` was given its own; returns 0."""
 
     def __init__(self):
         self.calls = []
@@ -122,7 +134,11 @@ class FakeGram:
     def daam_token_gram(self, keys, n_keys, dtype, n_rows, gram, scratch, scratch_bytes, stream):
         from daam_amd import _native as nat
         desc = [(d.base, d.win_stride, d.h, d.w, d.n_win) for d in (nat.KeyPlanes * n_keys).from_address(keys)]
-        self.calls.append(dict(desc=desc, dtype=dtype, n_rows=n_rows, gram=gram, scratch=scratch, scratch_bytes=scratch_bytes))
+        self.calls.append(dict(keys=keys, desc=desc, dtype=dtype, n_rows=n_rows, gram=gram, scratch=scratch, scratch_bytes=scratch_bytes))
+        return 0
+
+    def daam_key_scores(self, keys, n_keys, dtype, n_rows, out_h, out_w, footprint, n_masks, scores, stream):
+        self.calls.append(dict(keys=keys, n_keys=n_keys))
         return 0
 
 
@@ -137,7 +153,7 @@ def _tapped(E, time_bins=None, layers=(1, 0), batch=2):
 def test_engine_descriptors_are_those_of_key_scores(fake_engine, monkeypatch):
     E, lib = fake_engine
     fake = FakeGram()
-    monkeypatch.setattr(E.nat, 'load_gram', lambda: fake)
+    monkeypatch.setattr(E.nat, 'load_analysis', lambda: fake)
     eng = _tapped(E)
     keys, gram = eng.token_gram(n_rows=5)
     assert keys == [(8, 0, 0), (8, 0, 1), (8, 1, 0), (8, 1, 1)] and gram.shape == (4, 5, 5) and gram.dtype == torch.float32
@@ -153,7 +169,10 @@ def test_engine_descriptors_are_those_of_key_scores(fake_engine, monkeypatch):
     grown = eng._gram_scratch
     eng.token_gram(n_rows=5)
     assert eng._gram_scratch is grown and held is not None      # ... and is kept
-    # the selection and its cache are key_scores'
+    # the selection and its cache are key_scores': one library, one preamble, the same descriptors on the device
+    eng.key_scores(n_rows=5)
+    eng.token_gram(n_rows=5)
+    assert fake.calls[-1]['keys'] == fake.calls[-2]['keys'] != 0 and fake.calls[-2]['n_keys'] == len(fake.calls[-1]['desc']) == 4
     assert eng.token_gram(head_idx=1, layer_idx=1)[0] == [(8, 1, 1)]
     n = len(eng._ks_cache)
     eng.token_gram(head_idx=1, layer_idx=1)

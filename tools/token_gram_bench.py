@@ -65,7 +65,7 @@ def torch_route(eng):
 
 def wide_route(eng, keys):
     """The same keys with n_win = 2, win_stride = 0 through the raw ABI: the f32 path on the fp16 planes."""
-    lib = nat.load_gram()
+    lib = nat.load_analysis()
     views = dict(eng.items())
     arr = (nat.KeyPlanes * len(keys))(*[nat.KeyPlanes(base=views[k].data_ptr(), win_stride=0, h=views[k].shape[-2], w=views[k].shape[-1],
                                                       n_win=2, pad=0) for k in keys])
@@ -75,8 +75,8 @@ def wide_route(eng, keys):
     gram = torch.empty(len(keys), ROWS, ROWS, dtype=torch.float32, device='cuda:0')
 
     def call():
-        nat.check_gram(lib.daam_token_gram(desc.data_ptr(), len(keys), nat.DAAM_F16, ROWS, gram.data_ptr(), scratch.data_ptr(), need,
-                                           torch.cuda.current_stream().cuda_stream))
+        nat.check_analysis(lib.daam_token_gram(desc.data_ptr(), len(keys), nat.DAAM_F16, ROWS, gram.data_ptr(), scratch.data_ptr(), need,
+                                               torch.cuda.current_stream().cuda_stream))
         return gram
     return call, (desc, scratch)
 
@@ -112,7 +112,7 @@ def main():
         with open(args.out) as f:
             res['results'] = json.load(f).get('results', {})
     res['device'] = torch.cuda.get_device_name(0)
-    res['kernel_shas'] = build.kernel_shas(build.GRAM_OUT)
+    res['kernel_shas'] = {k: v for k, v in build.kernel_shas(build.ANALYSIS_OUT).items() if 'token_gram' in k}
     res['results'][args.topology] = row
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, 'w') as f:
