@@ -181,5 +181,36 @@ def check_analysis(rc: int) -> None:
         raise DaamError(rc, msg.decode() if msg else '')
 
 
+# ---- libdaam_blend.so (C ABI: include/daam_blend.h) -------------------------------------------------------------------------------
+BLEND_LIB_NAME = 'libdaam_blend.so'
+BLEND_LIB_PATH = os.environ.get('DAAM_BLEND_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), BLEND_LIB_NAME)
+BLEND_ABI_VERSION = 1
+BLEND_EXPORTS = ('daam_key_blend', 'daam_key_blend_scratch_bytes', 'daam_blend_abi_version', 'daam_blend_last_error')
+
+_blend = None
+
+
+def load_blend() -> ctypes.CDLL:
+    """The key-blend library (heat maps of weighted key sets); like ``load`` it has no fallback."""
+    global _blend
+    if _blend is not None:
+        return _blend
+    lib = _open(BLEND_LIB_PATH, 'weighted key heat maps', BLEND_EXPORTS, 'daam_blend_abi_version', BLEND_ABI_VERSION)
+    lib.daam_key_blend.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_size_t,
+                                   c_void_p]
+    lib.daam_key_blend.restype = c_int
+    lib.daam_key_blend_scratch_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.daam_key_blend_scratch_bytes.restype = c_size_t
+    lib.daam_blend_last_error.restype = c_char_p
+    _blend = lib
+    return lib
+
+
+def check_blend(rc: int) -> None:
+    if rc != 0:
+        msg = load_blend().daam_blend_last_error()
+        raise DaamError(rc, msg.decode() if msg else '')
+
+
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -18,6 +18,13 @@ ANALYSIS_SOURCES = ['daam_key_scores.hip', 'daam_token_gram.hip']
 ANALYSIS_HEADERS = ['daam_key_planes.h', 'daam_key_scores.h', 'daam_token_gram.h', 'daam_finalize.h', 'daam_epilogue.h', 'daam_elem.h',
                     'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_analysis.h')]
 ANALYSIS_OUT = os.path.join(HERE, 'libdaam_analysis.so')
+# libdaam_blend.so (include/daam_blend.h): the second side library, daam_key_blend alone.  The kernels and the file lists of the two
+# libraries above are pinned to what their profiles were measured on, so a new per-key kernel starts out beside them, as the token
+# Gram did; a later refactor folds it into libdaam_analysis.so.  Its source reads the other libraries' headers.
+BLEND_SOURCES = ['daam_key_blend.hip']
+BLEND_HEADERS = ['daam_key_blend.h', 'daam_key_planes.h', 'daam_finalize.h', 'daam_epilogue.h', 'daam_elem.h', 'daam_types.h',
+                 os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_analysis.h'),
+                 os.path.join('..', '..', 'include', 'daam_blend.h')]
 
 
 def csrc_sha() -> str:
@@ -115,6 +122,29 @@ def build_analysis(force: bool = False, verbose: bool = True) -> str:
     return ANALYSIS_OUT
 
 
+def blend_out() -> str:
+    return os.path.join(HERE, 'libdaam_blend.so')
+
+
+def blend_stale() -> bool:
+    if not os.path.exists(blend_out()):
+        return True
+    t = os.path.getmtime(blend_out())
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in BLEND_SOURCES + BLEND_HEADERS)
+
+
+def build_blend(force: bool = False, verbose: bool = True) -> str:
+    """``libdaam_blend.so``: one hipcc command, when it is missing or older than what it is made of."""
+    if not force and not blend_stale():
+        return blend_out()
+    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
+           *[os.path.join(HERE, 'csrc', f) for f in BLEND_SOURCES], '-o', blend_out()]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return blend_out()
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -168,6 +198,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     from concurrent.futures import ThreadPoolExecutor
     build_fastpath(force, verbose)
     build_analysis(force, verbose)
+    build_blend(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

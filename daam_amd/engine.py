@@ -296,6 +296,7 @@ class HeatMapEngine:
         self._mask_cache: Dict[tuple, tuple] = {}        # finalize key tables per selection (_select)
         self._ks_cache: Dict[tuple, tuple] = {}          # key_scores: (keys, DaamKeyPlanes tensor) per selection and buffer addresses
         self._gram_scratch: Optional[torch.Tensor] = None    # token_gram: the partial matrices of keys of more than one chunk
+        self._blend_scratch: Optional[torch.Tensor] = None   # key_blend: the partial maps of the chunks of keys
         # deferred mode: the per-call bookkeeping runs in the C++ recorder (csrc/daam_fastpath.cpp) when
         # that extension is built; the Python implementation below is the same logic and stays the
         # slow path (first call of a layer, shape changes) and the fallback.  Both only record host-side
@@ -1154,6 +1155,39 @@ class HeatMapEngine:
                                                    self._gram_scratch.data_ptr(), self._gram_scratch.numel(), self.stream))
         return keys, gram
 
+    def key_blend(self, weights: torch.Tensor, n_rows: Optional[int] = None, factors: Optional[Sequence[int]] = None,
+                  head_idx: Optional[int] = None, layer_idx: Optional[int] = None, n_prompts: int = 1, prompt: int = 0,
+                  bins: Optional[Tuple[int, int]] = None):
+        """Heat maps of weighted key sets (``daam_key_blend`` of ``libdaam_blend.so``): the finalize's arithmetic -- bicubic to the
+        map's size, clamp at 0 -- with ``weights[g][k]`` in front of the sum over keys, ``maps[g] = sum_k weights[g][k] * K_k``.
+        ``weights`` is fp32 ``[G, len(keys)]`` in the key order of ``key_scores`` for the same selection (a host tensor is moved to
+        the device); a zero weight is no contribution and a key every set weighs 0 is not read.  Returns ``(keys, maps)`` with
+        ``maps`` fp32 ``[G, rows, out_h, out_w]`` on the device; one call per 8 sets reads the running sums once.  The selection,
+        key order, ``n_rows`` crop, ``bins`` and ``LookupError`` are ``key_scores``'.  The scratch is the engine's, grown on demand."""
+        rows, planes = self._key_selection(n_rows, factors, head_idx, layer_idx, n_prompts, prompt, bins)
+        keys, desc = self._key_planes(*planes)
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.dim() != 2 \
+                or weights.shape[1] != len(keys) or weights.shape[0] < 1:
+            got = f'{tuple(weights.shape)} {weights.dtype}' if isinstance(weights, torch.Tensor) else type(weights).__name__
+            raise ValueError(f'weights must be fp32 [G, {len(keys)}] (one column per selected key), got {got}')
+        weights = weights.to(self.device).contiguous()
+        lib = nat.load_blend()
+        n_sets, cells = weights.shape[0], self.out_h * self.out_w
+        need = lib.daam_key_blend_scratch_bytes(len(keys), min(n_sets, MAX_BLEND_SETS), rows, self.out_h, self.out_w)
+        if need == 0:
+            raise ValueError(f'daam_key_blend takes up to 2^20 keys and maps of up to 128 x 128, got {len(keys)} keys, {rows} rows of '
+                             f'{self.out_h} x {self.out_w}')
+        with torch.cuda.device(self.device):
+            if self._blend_scratch is None or self._blend_scratch.numel() < need:
+                self._blend_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            maps = torch.empty(n_sets, rows, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
+            for at in range(0, n_sets, MAX_BLEND_SETS):
+                n = min(MAX_BLEND_SETS, n_sets - at)
+                nat.check_blend(lib.daam_key_blend(desc.data_ptr(), len(keys), _DTYPE_CODE[self.acc_dtype], rows, self.out_h, self.out_w,
+                                                   weights[at:at + n].data_ptr(), n, maps[at:at + n].data_ptr(), rows * cells,
+                                                   self._blend_scratch.data_ptr(), self._blend_scratch.numel(), self.stream))
+        return keys, maps
+
     def _key_selection(self, n_rows, factors, head_idx, layer_idx, n_prompts, prompt, bins):
         """What ``key_scores`` and ``token_gram`` decide before they build descriptors: ``(rows, planes)`` -- the ``n_rows`` crop and
         the arguments of ``_key_planes`` for prompt ``prompt``'s selection over the window range ``bins`` (the caller makes that call,
@@ -1321,6 +1355,7 @@ def _check_maps(maps: torch.Tensor) -> None:
         raise RuntimeError('daam_amd: heat maps must be a contiguous fp32 [rows, h, w] tensor')
 
 
+MAX_BLEND_SETS = 8                                # limit of one daam_key_blend call (include/daam_blend.h)
 MAX_REGION_MASKS = 32                             # limit of one daam_region_scores call (include/daam_hip.h)
 
 

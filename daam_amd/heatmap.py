@@ -189,6 +189,25 @@ class KeyAnalysis:
     tokenizer: Any = None
     prompt: Optional[str] = None
 
+    def index_of(self, key) -> int:
+        """The position of ``key`` in ``keys``: ``(factor, layer, head)`` with the layer as an index or as a name of
+        ``layer_names``, or a ``(key, score)`` pair as ``top_keys`` returns them.  ValueError for a key the selection lacks."""
+        if len(key) == 2 and isinstance(key[0], (tuple, list)):
+            key = key[0]
+        factor, layer, head = key
+        if isinstance(layer, str):
+            if self.layer_names is None or layer not in self.layer_names:
+                raise ValueError(f'key {tuple(key)!r}: no layer of that name')
+            # the reference's names restart per block, so the factor and the head help to tell the layers apart
+            found = [i for i, name in enumerate(self.layer_names) if name == layer and (int(factor), i, int(head)) in self.keys]
+            if len(found) > 1:
+                raise ValueError(f'key {tuple(key)!r}: layers {found} share that name and factor; pass the layer\'s index')
+            layer = found[0] if found else -1
+        try:
+            return self.keys.index((int(factor), int(layer), int(head)))
+        except ValueError:
+            raise ValueError(f'key {tuple(key)!r} is not among the {len(self.keys)} keys of the selection') from None
+
     def _grouped(self, pos: int, values: torch.Tensor):
         """``(labels, means)``: ``values`` [K, ...] averaged over the keys that share element ``pos`` of their key, labels ascending."""
         labels = sorted({key[pos] for key in self.keys})

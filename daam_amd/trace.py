@@ -450,6 +450,83 @@ class DiffusionHeatMapHooker(AggregateHooker):
         keys, gram = self._key_call(self.engine.token_gram, **kw)
         return KeyCoattention(keys, gram, list(self.layer_names), self.pipe.tokenizer, prompt)
 
+    def compute_key_heat_map(self, keys, weights=None, prompt=None, normalize=False, prompt_idx: Optional[int] = None,
+                             time_bin=None) -> GlobalHeatMap:
+        """The heat map of a chosen set of ``(factor, layer, head)`` keys: ``sum_k weights[k] * max(bicubic(sum_k), 0)`` over the
+        listed keys, from ONE device pass (``HeatMapEngine.key_blend``) that reads only them.  ``keys``: a sequence of
+        ``(factor, layer, head)`` -- the layer an index or a name of ``layer_names``, the head counted inside the prompt's block --
+        or the ``[(key, score)]`` pairs ``KeyScores.top_keys`` / ``KeyCoattention.top_keys`` return.  ``weights=None`` is the mean
+        over the listed keys (with every key listed: ``compute_global_heat_map()``); given weights are used as they are (negative
+        ones subtract: heads A minus heads B), and a key listed twice adds its weights.  Rows are cropped, and ``normalize``,
+        ``prompt``, ``prompt_idx`` and ``time_bin`` mean what they mean in ``compute_global_heat_map``; non-square traces work.
+        ValueError for a key that was not tapped; probes are out of scope."""
+        return self.compute_key_heat_maps([keys if weights is None else (keys, weights)], prompt=prompt, normalize=normalize,
+                                          prompt_idx=prompt_idx, time_bin=time_bin)[0]
+
+    def compute_key_heat_maps(self, selections, prompt=None, normalize=False, prompt_idx: Optional[int] = None,
+                              time_bin=None) -> List[GlobalHeatMap]:
+        """One ``GlobalHeatMap`` per entry of ``selections`` -- each ``keys`` or ``(keys, weights)`` as in ``compute_key_heat_map``
+        -- from one pass over the union of their keys (8 selections per device call): a key no selection lists is not read, and
+        every map is bit for bit the one ``compute_key_heat_map`` gives for its entry alone."""
+        text, kw = self._key_selection(prompt, None, None, None, prompt_idx, time_bin)
+        selections = [self._key_weights(entry) for entry in selections]
+        if not selections or any(not keys for keys, _ in selections):
+            raise _no_maps(True)
+        eng = self.engine
+        # the selection's key order without a device call: the descriptors are cached, the weights are not built yet
+        try:
+            rows, planes = eng._key_selection(**dict(kw, bins=kw.get('bins')))
+            have, _ = eng._key_planes(*planes)
+        except LookupError:
+            raise _no_maps(False) from None
+        column = {key: i for i, key in enumerate(have)}
+        table = torch.zeros(len(selections), len(have), dtype=torch.float32)
+        for g, (keys, weights) in enumerate(selections):
+            for key, weight in zip(keys, weights):
+                if isinstance(key[1], str):
+                    # the reference's names restart per block (hook.py), so the factor and the head help to tell the layers apart
+                    found = [i for i, name in enumerate(self.layer_names) if name == key[1] and (key[0], i, key[2]) in column]
+                    if len(found) > 1:
+                        raise ValueError(f'key {key!r}: layers {found} share that name and factor; pass the layer\'s index')
+                    key = (key[0], found[0] if found else -1, key[2])
+                if key not in column:
+                    raise ValueError(f'key {key!r} was not tapped in the last generation')
+                table[g, column[key]] += weight
+        _, maps = self._key_call(eng.key_blend, table, **kw)
+        return [self._wrap(maps[g], rows, text, normalize) for g in range(len(selections))]
+
+    def _key_weights(self, entry):
+        """An entry of ``compute_key_heat_maps`` -> ``([(factor, layer index or name, head)], [weight])``."""
+        def is_key(x):
+            return isinstance(x, (tuple, list)) and len(x) == 3 and isinstance(x[0], numbers.Number)
+
+        def is_pair(x):                                                   # a (key, score) pair of top_keys
+            return isinstance(x, (tuple, list)) and len(x) == 2 and is_key(x[0]) and isinstance(x[1], numbers.Number)
+
+        keys, weights = entry, None
+        if isinstance(entry, tuple) and len(entry) == 2 and not is_key(entry[0]) and not is_pair(entry[0]):
+            keys, weights = entry
+        out = []
+        for key in keys:
+            if is_pair(key):
+                key = key[0]
+            if not is_key(key):
+                raise ValueError(f'key {key!r}: expected (factor, layer, head)')
+            factor, layer, head = key
+            if isinstance(layer, str):
+                if layer not in self.layer_names:
+                    raise ValueError(f'key {tuple(key)!r}: the pipeline has no layer named {layer!r}')
+                out.append((int(factor), layer, int(head)))      # resolved against the tapped keys by the caller
+            else:
+                out.append((int(factor), int(layer), int(head)))
+        if weights is None:
+            weights = [1.0 / len(out)] * len(out) if out else []
+        else:
+            weights = [float(w) for w in (weights.tolist() if isinstance(weights, torch.Tensor) else weights)]
+            if len(weights) != len(out):
+                raise ValueError(f'{len(weights)} weights for {len(out)} keys')
+        return out, weights
+
     def _key_selection(self, prompt, factors, head_idx, layer_idx, prompt_idx, time_bin):
         """What the per-key analyses decide before their engine call: ``(prompt, kw)`` -- the text that labels and crops the result,
         and the engine method's keywords: the crop, the filters, the prompt's block and the window range (``_key_call`` makes the
