@@ -145,9 +145,9 @@ def check(rc: int) -> None:
 # ---- libdaam_analysis.so (C ABI: include/daam_analysis.h) -------------------------------------------------------------------------
 ANALYSIS_LIB_NAME = 'libdaam_analysis.so'
 ANALYSIS_LIB_PATH = os.environ.get('DAAM_ANALYSIS_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), ANALYSIS_LIB_NAME)
-ANALYSIS_ABI_VERSION = 2
-ANALYSIS_EXPORTS = ('daam_key_scores', 'daam_token_gram', 'daam_token_gram_scratch_bytes', 'daam_analysis_abi_version',
-                    'daam_analysis_last_error')
+ANALYSIS_ABI_VERSION = 3
+ANALYSIS_EXPORTS = ('daam_key_scores', 'daam_token_gram', 'daam_token_gram_scratch_bytes', 'daam_key_blend', 'daam_key_blend_scratch_bytes',
+                    'daam_analysis_abi_version', 'daam_analysis_last_error')
 
 
 class KeyPlanes(Structure):
@@ -159,7 +159,8 @@ _analysis = None
 
 
 def load_analysis() -> ctypes.CDLL:
-    """The per-key analysis library (key scores, token Gram matrices); like ``load`` it has no fallback."""
+    """The per-key analysis library (key scores, token Gram matrices, heat maps of weighted key sets); like ``load`` it has no
+    fallback."""
     global _analysis
     if _analysis is not None:
         return _analysis
@@ -170,6 +171,11 @@ def load_analysis() -> ctypes.CDLL:
     lib.daam_token_gram.restype = c_int
     lib.daam_token_gram_scratch_bytes.argtypes = [c_int, c_int, c_int]
     lib.daam_token_gram_scratch_bytes.restype = c_size_t
+    lib.daam_key_blend.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_size_t,
+                                   c_void_p]
+    lib.daam_key_blend.restype = c_int
+    lib.daam_key_blend_scratch_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.daam_key_blend_scratch_bytes.restype = c_size_t
     lib.daam_analysis_last_error.restype = c_char_p
     _analysis = lib
     return lib
@@ -178,37 +184,6 @@ def load_analysis() -> ctypes.CDLL:
 def check_analysis(rc: int) -> None:
     if rc != 0:
         msg = load_analysis().daam_analysis_last_error()
-        raise DaamError(rc, msg.decode() if msg else '')
-
-
-# ---- libdaam_blend.so (C ABI: include/daam_blend.h) -------------------------------------------------------------------------------
-BLEND_LIB_NAME = 'libdaam_blend.so'
-BLEND_LIB_PATH = os.environ.get('DAAM_BLEND_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), BLEND_LIB_NAME)
-BLEND_ABI_VERSION = 1
-BLEND_EXPORTS = ('daam_key_blend', 'daam_key_blend_scratch_bytes', 'daam_blend_abi_version', 'daam_blend_last_error')
-
-_blend = None
-
-
-def load_blend() -> ctypes.CDLL:
-    """The key-blend library (heat maps of weighted key sets); like ``load`` it has no fallback."""
-    global _blend
-    if _blend is not None:
-        return _blend
-    lib = _open(BLEND_LIB_PATH, 'weighted key heat maps', BLEND_EXPORTS, 'daam_blend_abi_version', BLEND_ABI_VERSION)
-    lib.daam_key_blend.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_size_t,
-                                   c_void_p]
-    lib.daam_key_blend.restype = c_int
-    lib.daam_key_blend_scratch_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    lib.daam_key_blend_scratch_bytes.restype = c_size_t
-    lib.daam_blend_last_error.restype = c_char_p
-    _blend = lib
-    return lib
-
-
-def check_blend(rc: int) -> None:
-    if rc != 0:
-        msg = load_blend().daam_blend_last_error()
         raise DaamError(rc, msg.decode() if msg else '')
 
 

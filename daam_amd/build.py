@@ -11,20 +11,14 @@ SOURCES = ['daam_api.hip', 'daam_tap_api.hip', 'daam_finalize_api.hip', 'daam_ke
 HEADERS = ['daam_types.h', 'daam_elem.h', 'daam_finalize.h', 'daam_fin_bins.h', 'daam_fin_rect.h', 'daam_ctx.h', 'daam_tap_common.h', 'daam_tap16.h', 'daam_tap16_softmax.h', 'daam_tap_tile64.h', 'daam_tap_walk.h', 'daam_tap_rows.h', 'daam_epilogue.h', 'daam_tap_d64_body.inc', 'daam_finalize_pipe_asm_r16.inc', 'daam_finalize_pipe_asm_bf16.inc', 'daam_finalize_pipe_asm_f32.inc',
            'daam_finalize_pipe_prefill_r16.inc', 'daam_finalize_pipe_prefill_f32.inc', 'daam_fin_kernel_body.inc', 'daam_fin_up_kernel_body.inc', 'daam_fin_down2_kernel_body.inc', 'daam_fin_pipe_kernel_body.inc', 'daam_word_expand_body.inc', os.path.join('..', '..', 'include', 'daam_hip.h')]
 OUT = os.path.join(HERE, 'libdaam_hip.so')
-# libdaam_analysis.so (include/daam_analysis.h): the one side library, every per-key analysis, with no context.  It is kept out of
-# SOURCES / HEADERS so that csrc_sha() and the kernels of libdaam_hip.so stay what the committed profiles were measured on.  Its
-# sources read the first library's headers.
-ANALYSIS_SOURCES = ['daam_key_scores.hip', 'daam_token_gram.hip']
-ANALYSIS_HEADERS = ['daam_key_planes.h', 'daam_key_scores.h', 'daam_token_gram.h', 'daam_finalize.h', 'daam_epilogue.h', 'daam_elem.h',
-                    'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_analysis.h')]
+# libdaam_analysis.so (include/daam_analysis.h): the one side library, the three per-key analyses (key scores, token Gram, weighted
+# key maps), with no context.  It is kept out of SOURCES / HEADERS so that csrc_sha() and the kernels of libdaam_hip.so stay what the
+# committed profiles were measured on.  Its sources read the first library's headers.
+ANALYSIS_SOURCES = ['daam_key_scores.hip', 'daam_token_gram.hip', 'daam_key_blend.hip']
+ANALYSIS_HEADERS = ['daam_key_planes.h', 'daam_key_scores.h', 'daam_token_gram.h', 'daam_key_blend.h', 'daam_finalize.h', 'daam_epilogue.h',
+                    'daam_elem.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'),
+                    os.path.join('..', '..', 'include', 'daam_analysis.h')]
 ANALYSIS_OUT = os.path.join(HERE, 'libdaam_analysis.so')
-# libdaam_blend.so (include/daam_blend.h): the second side library, daam_key_blend alone.  The kernels and the file lists of the two
-# libraries above are pinned to what their profiles were measured on, so a new per-key kernel starts out beside them, as the token
-# Gram did; a later refactor folds it into libdaam_analysis.so.  Its source reads the other libraries' headers.
-BLEND_SOURCES = ['daam_key_blend.hip']
-BLEND_HEADERS = ['daam_key_blend.h', 'daam_key_planes.h', 'daam_finalize.h', 'daam_epilogue.h', 'daam_elem.h', 'daam_types.h',
-                 os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_analysis.h'),
-                 os.path.join('..', '..', 'include', 'daam_blend.h')]
 
 
 def csrc_sha() -> str:
@@ -122,29 +116,6 @@ def build_analysis(force: bool = False, verbose: bool = True) -> str:
     return ANALYSIS_OUT
 
 
-def blend_out() -> str:
-    return os.path.join(HERE, 'libdaam_blend.so')
-
-
-def blend_stale() -> bool:
-    if not os.path.exists(blend_out()):
-        return True
-    t = os.path.getmtime(blend_out())
-    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in BLEND_SOURCES + BLEND_HEADERS)
-
-
-def build_blend(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_blend.so``: one hipcc command, when it is missing or older than what it is made of."""
-    if not force and not blend_stale():
-        return blend_out()
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
-           *[os.path.join(HERE, 'csrc', f) for f in BLEND_SOURCES], '-o', blend_out()]
-    if verbose:
-        print(' '.join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return blend_out()
-
-
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -198,7 +169,6 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     from concurrent.futures import ThreadPoolExecutor
     build_fastpath(force, verbose)
     build_analysis(force, verbose)
-    build_blend(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

@@ -1,10 +1,9 @@
-// daam_key_blend (include/daam_blend.h) between its kernels and its host entry point (all in daam_key_blend.hip): the
+// daam_key_blend (include/daam_analysis.h) between its kernels and its host entry point (all in daam_key_blend.hip): the
 // launch descriptor, the decomposition and the LDS / scratch plan.  The plan is a function of the output's size and n_keys alone --
 // the keys' own sizes live on the device --, so the host sizes the launch without reading them back: a key that does not fit the
 // staging takes the kernel's gather path instead (same arithmetic, same bits).
 #pragma once
 #include "daam_key_planes.h"
-#include "../../include/daam_blend.h"
 
 namespace daam {
 

@@ -1,4 +1,4 @@
-// daam_key_blend (include/daam_blend.h): heat maps of up to 8 weighted key sets from one read of the running sums -- the finalize's
+// daam_key_blend (include/daam_analysis.h): heat maps of up to 8 weighted key sets from one read of the running sums -- the finalize's
 // arithmetic per key with a weight in front of the sum over keys.  key_blend_kernel, grid (n_rows x bands, chunks), 256 threads;
 // workgroup (token row, band of output rows, chunk of 32 keys).  A lane owns one output column and 4 rows of it, lane_rows apart:
 // 8 sets x 4 accumulators in registers, its column's taps and its rows' taps in registers too (computed again only when the next
@@ -16,8 +16,6 @@
 #include "daam_epilogue.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
 namespace daam {
 
@@ -231,17 +229,6 @@ __global__ __launch_bounds__(kBlendThreads) void key_blend_join_kernel(const Ble
 
 namespace {
 
-thread_local char blend_error[256] = "";
-
-__attribute__((format(printf, 2, 3))) int blend_fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(blend_error, sizeof(blend_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 // the limits both entry points know: 0 when one is out of range
 bool blend_sizes_ok(int n_keys, int n_sets, int n_rows, int out_h, int out_w)
 {
@@ -257,10 +244,6 @@ bool blend_sizes_ok(int n_keys, int n_sets, int n_rows, int out_h, int out_w)
 
 using namespace daam;
 
-int daam_blend_abi_version(void) { return DAAM_BLEND_ABI_VERSION; }
-
-const char* daam_blend_last_error(void) { return blend_error; }
-
 size_t daam_key_blend_scratch_bytes(int n_keys, int n_sets, int n_rows, int out_h, int out_w)
 {
     if (!blend_sizes_ok(n_keys, n_sets, n_rows, out_h, out_w)) return 0;
@@ -270,25 +253,22 @@ size_t daam_key_blend_scratch_bytes(int n_keys, int n_sets, int n_rows, int out_
 int daam_key_blend(const DaamKeyPlanes* keys, int n_keys, int dtype, int n_rows, int out_h, int out_w, const float* weights, int n_sets,
                    float* out, int64_t set_stride, void* scratch, size_t scratch_bytes, void* stream)
 {
-    if (n_keys < 1 || n_keys > kKeyMaxKeys) return blend_fail(DAAM_E_INVALID, "%d keys: 1..%d", n_keys, kKeyMaxKeys);
-    if (n_sets < 1 || n_sets > kBlendMaxSets) return blend_fail(DAAM_E_INVALID, "%d weight sets: 1..%d", n_sets, kBlendMaxSets);
+    if (key_args_check(n_keys, dtype, n_rows, 0, !keys || !weights || !out || !scratch)) return DAAM_E_INVALID;
+    if (n_sets < 1 || n_sets > kBlendMaxSets) return analysis_fail(DAAM_E_INVALID, "%d weight sets: 1..%d", n_sets, kBlendMaxSets);
     if (out_h < 1 || out_h > kKeyMaxSide || out_w < 1 || out_w > kKeyMaxSide)
-        return blend_fail(DAAM_E_INVALID, "output of %d x %d: 1 <= out_h, out_w <= %d", out_h, out_w, kKeyMaxSide);
-    if (n_rows < 1) return blend_fail(DAAM_E_INVALID, "%d token rows: at least 1", n_rows);
+        return analysis_fail(DAAM_E_INVALID, "output of %d x %d: 1 <= out_h, out_w <= %d", out_h, out_w, kKeyMaxSide);
     if (!blend_sizes_ok(n_keys, n_sets, n_rows, out_h, out_w))
-        return blend_fail(DAAM_E_INVALID, "%d token rows of %d x %d: more workgroups than a launch grid holds", n_rows, out_h, out_w);
-    if (dtype != DAAM_F16 && dtype != DAAM_F32 && dtype != DAAM_BF16) return blend_fail(DAAM_E_INVALID, "dtype %d: f16, f32 or bf16", dtype);
-    if (!keys || !weights || !out || !scratch) return blend_fail(DAAM_E_INVALID, "NULL argument");
+        return analysis_fail(DAAM_E_INVALID, "%d token rows of %d x %d: more workgroups than a launch grid holds", n_rows, out_h, out_w);
     const int64_t map = (int64_t)n_rows * out_h * out_w;
     if (set_stride < map)
-        return blend_fail(DAAM_E_INVALID, "set_stride %lld: a set is %lld elements", (long long)set_stride, (long long)map);
+        return analysis_fail(DAAM_E_INVALID, "set_stride %lld: a set is %lld elements", (long long)set_stride, (long long)map);
     const size_t need = daam_key_blend_scratch_bytes(n_keys, n_sets, n_rows, out_h, out_w);
     if (scratch_bytes < need)
-        return blend_fail(DAAM_E_INVALID, "scratch of %zu bytes: %d keys, %d sets, %d rows of %d x %d need %zu", scratch_bytes, n_keys, n_sets,
-                          n_rows, out_h, out_w, need);
+        return analysis_fail(DAAM_E_INVALID, "scratch of %zu bytes: %d keys, %d sets, %d rows of %d x %d need %zu", scratch_bytes, n_keys, n_sets,
+                             n_rows, out_h, out_w, need);
     const size_t lds = blend_lds_bytes(out_h, out_w);
     if (lds > kBlendMaxLds)
-        return blend_fail(DAAM_E_UNSUPPORTED, "an output of %d x %d needs %zu bytes of LDS, more than %zu", out_h, out_w, lds, kBlendMaxLds);
+        return analysis_fail(DAAM_E_UNSUPPORTED, "an output of %d x %d needs %zu bytes of LDS, more than %zu", out_h, out_w, lds, kBlendMaxLds);
 
     BlendLaunch L;
     L.keys = keys; L.weights = weights; L.out = out; L.set_stride = set_stride;
@@ -310,6 +290,6 @@ int daam_key_blend(const DaamKeyPlanes* keys, int n_keys, int dtype, int n_rows,
         const dim3 jgrid((unsigned)((map + kBlendThreads - 1) / kBlendThreads), (unsigned)n_sets);
         e = fin_launch(key_blend_join_kernel, jgrid, kBlendThreads, 0, s, L);
     }
-    if (e != hipSuccess) return blend_fail((int)e, "key blend: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return analysis_fail((int)e, "key blend: %s", hipGetErrorString(e));
     return 0;
 }

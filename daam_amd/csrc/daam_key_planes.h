@@ -1,5 +1,5 @@
-// What the per-key analyses of libdaam_analysis.so (include/daam_analysis.h) share: daam_key_scores.h and daam_token_gram.h include
-// this header, and each keeps only what is its own.  A key is a DaamKeyPlanes; here are its limits and "is it a plane", its element
+// What the per-key analyses of libdaam_analysis.so (include/daam_analysis.h) share: daam_key_scores.h, daam_token_gram.h and
+// daam_key_blend.h include this header, and each keeps only what is its own.  A key is a DaamKeyPlanes; here are its limits and "is it a plane", its element
 // types, and the host's one error buffer and one wording of the argument checks every entry point makes (both defined in
 // daam_key_scores.hip, which also holds daam_analysis_last_error).
 #pragma once

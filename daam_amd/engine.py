@@ -1158,7 +1158,7 @@ class HeatMapEngine:
     def key_blend(self, weights: torch.Tensor, n_rows: Optional[int] = None, factors: Optional[Sequence[int]] = None,
                   head_idx: Optional[int] = None, layer_idx: Optional[int] = None, n_prompts: int = 1, prompt: int = 0,
                   bins: Optional[Tuple[int, int]] = None):
-        """Heat maps of weighted key sets (``daam_key_blend`` of ``libdaam_blend.so``): the finalize's arithmetic -- bicubic to the
+        """Heat maps of weighted key sets (``daam_key_blend`` of ``libdaam_analysis.so``): the finalize's arithmetic -- bicubic to the
         map's size, clamp at 0 -- with ``weights[g][k]`` in front of the sum over keys, ``maps[g] = sum_k weights[g][k] * K_k``.
         ``weights`` is fp32 ``[G, len(keys)]`` in the key order of ``key_scores`` for the same selection (a host tensor is moved to
         the device); a zero weight is no contribution and a key every set weighs 0 is not read.  Returns ``(keys, maps)`` with
@@ -1171,7 +1171,7 @@ class HeatMapEngine:
             got = f'{tuple(weights.shape)} {weights.dtype}' if isinstance(weights, torch.Tensor) else type(weights).__name__
             raise ValueError(f'weights must be fp32 [G, {len(keys)}] (one column per selected key), got {got}')
         weights = weights.to(self.device).contiguous()
-        lib = nat.load_blend()
+        lib = nat.load_analysis()
         n_sets, cells = weights.shape[0], self.out_h * self.out_w
         need = lib.daam_key_blend_scratch_bytes(len(keys), min(n_sets, MAX_BLEND_SETS), rows, self.out_h, self.out_w)
         if need == 0:
@@ -1183,9 +1183,9 @@ class HeatMapEngine:
             maps = torch.empty(n_sets, rows, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
             for at in range(0, n_sets, MAX_BLEND_SETS):
                 n = min(MAX_BLEND_SETS, n_sets - at)
-                nat.check_blend(lib.daam_key_blend(desc.data_ptr(), len(keys), _DTYPE_CODE[self.acc_dtype], rows, self.out_h, self.out_w,
-                                                   weights[at:at + n].data_ptr(), n, maps[at:at + n].data_ptr(), rows * cells,
-                                                   self._blend_scratch.data_ptr(), self._blend_scratch.numel(), self.stream))
+                nat.check_analysis(lib.daam_key_blend(desc.data_ptr(), len(keys), _DTYPE_CODE[self.acc_dtype], rows, self.out_h, self.out_w,
+                                                      weights[at:at + n].data_ptr(), n, maps[at:at + n].data_ptr(), rows * cells,
+                                                      self._blend_scratch.data_ptr(), self._blend_scratch.numel(), self.stream))
         return keys, maps
 
     def _key_selection(self, n_rows, factors, head_idx, layer_idx, n_prompts, prompt, bins):
@@ -1355,7 +1355,7 @@ def _check_maps(maps: torch.Tensor) -> None:
         raise RuntimeError('daam_amd: heat maps must be a contiguous fp32 [rows, h, w] tensor')
 
 
-MAX_BLEND_SETS = 8                                # limit of one daam_key_blend call (include/daam_blend.h)
+MAX_BLEND_SETS = 8                                # limit of one daam_key_blend call (include/daam_analysis.h)
 MAX_REGION_MASKS = 32                             # limit of one daam_region_scores call (include/daam_hip.h)
 
 

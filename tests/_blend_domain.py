@@ -1,4 +1,4 @@
-"""Float64 reference and error bound of ``daam_key_blend`` (include/daam_blend.h), shared by ``test_key_blend_cpu.py`` and
+"""Float64 reference and error bound of ``daam_key_blend`` (include/daam_analysis.h), shared by ``test_key_blend_cpu.py`` and
 ``test_gpu_key_blend.py``.
 
 Reference: per key the clamped, resized map ``K_k`` of ``tests/_key_scores_domain.py`` (``clamped64``: the windows summed in

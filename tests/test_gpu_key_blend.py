@@ -1,4 +1,4 @@
-"""``daam_key_blend`` (libdaam_blend.so) on the device: the raw C ABI on signed random planes against the float64 reference and the
+"""``daam_key_blend`` (libdaam_analysis.so) on the device: the raw C ABI on signed random planes against the float64 reference and the
 counted bound of ``tests/_blend_domain.py``, the zero-weight and bad-descriptor rules, its determinism promises, and
 ``compute_key_heat_map`` / ``compute_key_heat_maps`` on traced generations against float64 of the raw running sums."""
 import functools
@@ -22,7 +22,7 @@ PAD = 4                                       # elements between two sets of the
 
 def _lib():
     from daam_amd import _native as nat
-    return nat, nat.load_blend()
+    return nat, nat.load_analysis()
 
 
 def _as_np(t):
@@ -74,7 +74,7 @@ def _call(desc, dt, n_rows, out_h, out_w, weights, extra_scratch=0):
     scratch = torch.full((need + extra_scratch,), 0xA5, dtype=torch.uint8, device=DEV)
     stride = n_rows * cells + PAD
     out = torch.full((n_sets, stride), SENTINEL, dtype=torch.float32, device=DEV)
-    nat.check_blend(lib.daam_key_blend(dev.data_ptr(), len(desc), CODE[dt], n_rows, out_h, out_w, w.data_ptr(), n_sets, out.data_ptr(),
+    nat.check_analysis(lib.daam_key_blend(dev.data_ptr(), len(desc), CODE[dt], n_rows, out_h, out_w, w.data_ptr(), n_sets, out.data_ptr(),
                                        stride, scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     assert (out[:, n_rows * cells:] == SENTINEL).all()
@@ -191,6 +191,37 @@ def test_bit_identical_again_alone_cropped_and_with_more_scratch():
         like = bd.blend_like_kernel(k64.astype(np.float32), w[g]).astype(np.float64)
         assert (np.abs(like - exact[g]) <= bound[g]).all(), g
         assert (np.abs(every[g].cpu().numpy().astype(np.float64) - like) <= 2 * bound[g]).all(), g
+
+
+def test_a_refused_call_then_the_three_calls_on_one_handle():
+    """One library, one error buffer: a ``daam_key_blend`` refused on the host (``set_stride`` one short) leaves the handle good for
+    a blend of two chunks (the join runs) within the bound, and for ``daam_key_scores`` and ``daam_token_gram`` on the same keys."""
+    nat, lib = _lib()
+    n_keys, n_rows, out_h, out_w = C + 1, 2, 8, 8
+    keys = _keys(((4, 4, 1),) * n_keys, 'f16', out_h, out_w)
+    w = _weights(2, n_keys, seed=3)
+    w[:, 3] = 0.0
+    bufs, desc = _upload(keys, n_rows, False)
+    dev = torch.frombuffer(bytearray(bytes((nat.KeyPlanes * n_keys)(*desc))), dtype=torch.uint8).to(DEV)
+    wd = torch.as_tensor(w).to(DEV)
+    need = lib.daam_key_blend_scratch_bytes(n_keys, 2, n_rows, out_h, out_w)
+    scratch = torch.empty(max(need, lib.daam_token_gram_scratch_bytes(n_keys, n_rows, 16)), dtype=torch.uint8, device=DEV)
+    out = torch.full((2, n_rows * out_h * out_w), SENTINEL, dtype=torch.float32, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    rc = lib.daam_key_blend(dev.data_ptr(), n_keys, CODE['f16'], n_rows, out_h, out_w, wd.data_ptr(), 2, out.data_ptr(),
+                            n_rows * out_h * out_w - 1, scratch.data_ptr(), scratch.numel(), stream)
+    assert rc == nat.E_INVALID and 'set_stride' in lib.daam_analysis_last_error().decode()
+    torch.cuda.synchronize()
+    assert (out == SENTINEL).all()                               # refused before any launch
+    got = _call(desc, 'f16', n_rows, out_h, out_w, w).cpu().numpy()
+    exact, bound = bd.blend64(np.stack([k[:n_rows] for _, k, _ in keys]), np.stack([e[:n_rows] for _, _, e in keys]), w)
+    assert np.isfinite(got).all() and bd.worst_ratio(got, exact, bound, 'blend after a refused call') <= 1.0
+    scores = torch.empty(n_keys, 1, n_rows, dtype=torch.float32, device=DEV)
+    gram = torch.empty(n_keys, n_rows, n_rows, dtype=torch.float32, device=DEV)
+    assert lib.daam_key_scores(dev.data_ptr(), n_keys, CODE['f16'], n_rows, out_h, out_w, None, 0, scores.data_ptr(), stream) == 0
+    assert lib.daam_token_gram(dev.data_ptr(), n_keys, CODE['f16'], n_rows, gram.data_ptr(), scratch.data_ptr(), scratch.numel(), stream) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(scores).all() and torch.isfinite(gram).all()
 
 
 # ---- through daam_amd.trace ------------------------------------------------------------------------------------------------------

@@ -1,12 +1,8 @@
-"""Heat maps of weighted key sets without a GPU: ``libdaam_blend.so`` builds beside the other libraries and exports what its header
-declares, its argument checks answer before any device call, no kernel instance has scratch, the float64 reference of
-``tests/_blend_domain.py`` agrees with the oracle and its counted chain is pinned, and the engine and the trace hand ``daam_key_blend``
-the weight table their arguments imply (a recording stand-in below)."""
+"""Heat maps of weighted key sets without a GPU (the library itself: ``test_analysis_library_cpu.py``): the argument checks of
+``daam_key_blend`` answer before any device call, the float64 reference of ``tests/_blend_domain.py`` agrees with the oracle and its
+counted chain is pinned, and the engine and the trace hand ``daam_key_blend`` the weight table their arguments imply (a recording
+stand-in below)."""
 import ctypes
-import os
-import re
-import struct
-import subprocess
 import types
 
 import numpy as np
@@ -16,69 +12,13 @@ import torch
 import _blend_domain as bd
 from _fake_native import fake_engine  # noqa: F401 -- the fixture
 from oracle import heatmap_oracle as ho
-from test_tap_walk_cpu import _kernel_descriptors
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope='module')
 def built():
     from daam_amd import build
     build.build(verbose=False)
-    return build.blend_out()
-
-
-def test_blend_library_builds_and_exports_its_header(built):
-    from daam_amd import _native as nat, build
-    assert os.path.exists(built) and not build.blend_stale() and built == os.path.join(build.HERE, 'libdaam_blend.so')
-    assert build.BLEND_SOURCES == ['daam_key_blend.hip']
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.BLEND_SOURCES + build.BLEND_HEADERS)
-    mine = {'daam_key_blend.hip', 'daam_key_blend.h'}
-    pinned = set(build.SOURCES) | set(build.HEADERS) | set(build.ANALYSIS_SOURCES) | set(build.ANALYSIS_HEADERS)
-    assert mine <= set(build.BLEND_SOURCES + build.BLEND_HEADERS) and not mine & pinned
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_blend.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.BLEND_EXPORTS) and len(exported) == 4
-    assert nat.load_blend().daam_blend_abi_version() == 1 == nat.BLEND_ABI_VERSION
-    # the source defines none of the names it takes from the other libraries' headers
-    src = open(os.path.join(build.HERE, 'csrc', 'daam_key_blend.hip')).read() + open(os.path.join(build.HERE, 'csrc', 'daam_key_blend.h')).read()
-    for name in ('key_planes_ok', 'cubic_taps', 'cubic_row', 'cubic_coeffs', 'fin_dispatch', 'fin_launch'):
-        assert not re.search(r'\b(?:float|int|bool|void|hipError_t)\s+%s\(' % name, src), name
-    assert 'struct KeyElem' not in src and 'typedef' not in src and 'analysis_fail' not in src and 'key_args_check' not in src
-    assert 'atomic' not in src.lower().replace('no floating-point atomic', '')
-
-
-def test_blend_header_is_c99(tmp_path):
-    src = tmp_path / 'use.c'
-    src.write_text('#include "daam_blend.h"\nint main(void) { return sizeof(DaamKeyPlanes) == 32 && DAAM_BLEND_ABI_VERSION == 1 ? 0 : 1; }\n')
-    subprocess.run(['cc', '-std=c99', '-pedantic', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(tmp_path / 'use')],
-                   check=True)
-    assert subprocess.run([str(tmp_path / 'use')]).returncode == 0
-
-
-def test_deleted_blend_library_is_rebuilt_alone(built):
-    from daam_amd import build
-    others = (build.OUT, build.ANALYSIS_OUT, build.fastpath_out())
-    stamps = [os.path.getmtime(p) for p in others]
-    os.remove(built)
-    assert not build.stale() and not build.analysis_stale() and build.blend_stale()
-    build.build(verbose=False)
-    assert os.path.exists(built) and not build.blend_stale()
-    assert [os.path.getmtime(p) for p in others] == stamps
-
-
-def test_no_instance_has_scratch(built):
-    """A resource check only: private segment size 0 and the private-segment enable bit clear in every kernel descriptor."""
-    from daam_amd import build
-    kds = _kernel_descriptors(built)
-    names = list(build.kernel_shas(built))
-    assert len(names) == 4 and sum('key_blend_kernel' in k for k in names) == 3 and sum('key_blend_join_kernel' in k for k in names) == 1
-    for k in names:
-        private, = struct.unpack_from('<I', kds[k], 4)
-        _, rsrc2 = struct.unpack_from('<II', kds[k], 48)
-        assert private == 0 and not (rsrc2 & 1), (k, private)
+    return build.ANALYSIS_OUT
 
 
 def _raw(lib, a):
@@ -88,7 +28,7 @@ def _raw(lib, a):
 
 def test_out_of_limits_arguments_are_refused_on_the_host(built):
     from daam_amd import _native as nat
-    lib = nat.load_blend()
+    lib = nat.load_analysis()
     keys = (nat.KeyPlanes * 1)()
     buf = (ctypes.c_float * 64)()
     k, b = ctypes.addressof(keys), ctypes.addressof(buf)
@@ -105,14 +45,14 @@ def test_out_of_limits_arguments_are_refused_on_the_host(built):
     for change, word in bad:
         rc = _raw(lib, dict(good, **change))
         assert rc == nat.E_INVALID, change
-        assert word in lib.daam_blend_last_error().decode(), (change, lib.daam_blend_last_error().decode())
+        assert word in lib.daam_analysis_last_error().decode(), (change, lib.daam_analysis_last_error().decode())
         with pytest.raises(nat.DaamError):
-            nat.check_blend(rc)
+            nat.check_analysis(rc)
 
 
 def test_scratch_bytes_is_monotone(built):
     from daam_amd import _native as nat
-    size = nat.load_blend().daam_key_blend_scratch_bytes
+    size = nat.load_analysis().daam_key_blend_scratch_bytes
     assert size(1100, 1, 77, 64, 64) == 256 + bd.n_chunks(1100) * 77 * 64 * 64 * 4
     for bad in [(0, 1, 1, 4, 4), ((1 << 20) + 1, 1, 1, 4, 4), (1, 0, 1, 4, 4), (1, 9, 1, 4, 4), (1, 1, 0, 4, 4), (1, 1, 1, 0, 4), (1, 1, 1, 4, 129)]:
         assert size(*bad) == 0, bad
@@ -188,7 +128,6 @@ def _tapped(E, time_bins=None, layers=(1, 0), batch=2):
 def test_engine_call(fake_engine, monkeypatch):
     E, lib = fake_engine
     fake = FakeBlend()
-    monkeypatch.setattr(E.nat, 'load_blend', lambda: fake)
     monkeypatch.setattr(E.nat, 'load_analysis', lambda: fake)
     eng = _tapped(E)
     w = torch.arange(12, dtype=torch.float32).reshape(3, 4)
@@ -253,9 +192,9 @@ def _bare(eng, prompts=('a dog',)):
 def test_trace_builds_the_weight_table(fake_engine, monkeypatch):
     E, lib = fake_engine
     fake = FakeBlend()
-    monkeypatch.setattr(E.nat, 'load_blend', lambda: fake)
+    monkeypatch.setattr(E.nat, 'load_analysis', lambda: fake)
     eng = _tapped(E)
-    tc = _bare(eng)                                              # key order: (8, 0, 0), (8, 0, 1), (8, 1, 0), (8, 1, 1)
+    tc = _bare(eng)                                             # key order: (8, 0, 0), (8, 0, 1), (8, 1, 0), (8, 1, 1)
     hm = tc.compute_key_heat_map([(8, 1, 0), (8, 0, 1)])
     assert hm.heat_maps.shape == (4, 64, 64) and hm.prompt == 'a dog'           # 'a dog' + 2 rows
     call = fake.calls[-1]

@@ -1,11 +1,8 @@
-"""Head analysis without a GPU: ``libdaam_analysis.so`` builds beside ``libdaam_hip.so`` and exports what its header declares, its
-argument checks answer before any device call, the float64 reference of ``tests/_key_scores_domain.py`` agrees with the oracle,
-the engine hands ``daam_key_scores`` the descriptors the views imply (a recording stand-in below), and the ``KeyScores`` algebra."""
+"""Head analysis without a GPU (the library itself: ``test_analysis_library_cpu.py``): the argument checks of ``daam_key_scores``
+answer before any device call, one error buffer serves the library's three calls, the float64 reference of
+``tests/_key_scores_domain.py`` agrees with the oracle, the engine hands ``daam_key_scores`` the descriptors the views imply (a
+recording stand-in below), and the ``KeyScores`` algebra."""
 import ctypes
-import json
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,67 +12,12 @@ import _key_scores_domain as kd
 from _fake_native import fake_engine  # noqa: F401 -- the fixture
 from oracle import heatmap_oracle as ho
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 @pytest.fixture(scope='module')
 def built():
     from daam_amd import build
     build.build(verbose=False)
     return build.ANALYSIS_OUT
-
-
-def _committed_analysis_shas():
-    """The fingerprints the two per-key analyses were profiled on: 3 + 16 kernels."""
-    rec = {}
-    for name in ('key_scores.json', 'token_gram.json'):
-        rec.update(json.load(open(os.path.join(ROOT, 'profiles', name)))['kernel_shas'])
-    return rec
-
-
-def test_second_library_builds_and_exports_its_header(built):
-    from daam_amd import _native as nat, build
-    assert os.path.exists(built) and os.path.exists(build.OUT) and not build.analysis_stale()
-    assert build.ANALYSIS_SOURCES == ['daam_key_scores.hip', 'daam_token_gram.hip']
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.ANALYSIS_SOURCES + build.ANALYSIS_HEADERS)
-    mine = set(build.ANALYSIS_SOURCES) | {'daam_key_scores.h', 'daam_token_gram.h', 'daam_key_planes.h'}
-    assert mine <= set(build.ANALYSIS_SOURCES + build.ANALYSIS_HEADERS) and not mine & (set(build.SOURCES) | set(build.HEADERS))
-    assert not any('analysis' in os.path.basename(f) for f in build.HEADERS)
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_analysis.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.ANALYSIS_EXPORTS) and len(exported) == 5
-    assert nat.load_analysis().daam_analysis_abi_version() == 2 == nat.ANALYSIS_ABI_VERSION
-    assert ctypes.sizeof(nat.KeyPlanes) == 32
-
-
-def test_analysis_header_is_c99(tmp_path):
-    """The public header compiles as C99 under -pedantic, as daam_hip.h is held to (test_host_logic.py)."""
-    src = tmp_path / 'use.c'
-    src.write_text('#include "daam_analysis.h"\nint main(void) { return sizeof(DaamKeyPlanes) == 32 && DAAM_ANALYSIS_ABI_VERSION == 2 ? 0 : 1; }\n')
-    subprocess.run(['cc', '-std=c99', '-pedantic', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(tmp_path / 'use')],
-                   check=True)
-    assert subprocess.run([str(tmp_path / 'use')]).returncode == 0
-
-
-def test_fresh_first_library_does_not_skip_the_second(built):
-    from daam_amd import build
-    os.remove(built)
-    assert not build.stale() and build.analysis_stale()
-    build.build(verbose=False)
-    assert os.path.exists(built) and not build.analysis_stale()  # (rebuilt alone: test_token_gram_cpu.py)
-
-def test_the_first_library_is_what_it_was(built):
-    from daam_amd import _native as nat, build
-    rec = json.load(open(os.path.join(ROOT, 'profiles', 'finalize_launch_refactor.json')))
-    have = build.kernel_shas(build.OUT)
-    assert len(have) == 191 and {k: have.get(k) for k in rec['kernel_shas']} == rec['kernel_shas']
-    # the side library: key_scores_kernel on f16, bf16, f32 and the 16 token-Gram kernels, each the machine code that was profiled
-    want = _committed_analysis_shas()
-    assert len(want) == 19 and sum('key_scores_kernel' in k for k in want) == 3
-    assert build.kernel_shas(built) == want
-    assert nat.load().daam_abi_version() == 6
 
 
 def test_out_of_limits_arguments_are_refused_on_the_host(built):
@@ -100,7 +42,8 @@ def test_out_of_limits_arguments_are_refused_on_the_host(built):
 
 
 def test_one_error_buffer_serves_both_calls(built):
-    """A rejected ``daam_token_gram`` and then a rejected ``daam_key_scores`` on one thread: the message is the second call's."""
+    """A rejected ``daam_token_gram`` or ``daam_key_blend`` and then a rejected ``daam_key_scores`` on one thread: the message is the
+    second call's."""
     from daam_amd import _native as nat
     lib = nat.load_analysis()
     keys = (nat.KeyPlanes * 1)()
@@ -112,11 +55,19 @@ def test_one_error_buffer_serves_both_calls(built):
     assert lib.daam_key_scores(k, 1, 0, 1, 4, 4, None, 33, o, None) == nat.E_INVALID
     second = lib.daam_analysis_last_error().decode()
     assert '33 masks' in second and '97' not in second
-    # the checks the two calls share are reported in the same words
+    assert lib.daam_key_blend(k, 1, 0, 1, 4, 4, o, 9, o, 16, o, 1 << 20, None) == nat.E_INVALID
+    first = lib.daam_analysis_last_error().decode()
+    assert '9 weight sets' in first and 'masks' not in first
+    assert lib.daam_key_scores(k, 1, 0, 1, 4, 4, None, 33, o, None) == nat.E_INVALID
+    second = lib.daam_analysis_last_error().decode()
+    assert '33 masks' in second and 'weight sets' not in second
+    # the checks the three calls share are reported in the same words
     assert lib.daam_token_gram(k, 0, 0, 2, o, o, 64, None) == nat.E_INVALID
     words = lib.daam_analysis_last_error().decode()
     assert lib.daam_key_scores(k, 0, 0, 1, 4, 4, None, 0, o, None) == nat.E_INVALID
     assert words and lib.daam_analysis_last_error().decode() == words
+    assert lib.daam_key_blend(k, 0, 0, 1, 4, 4, o, 1, o, 16, o, 1 << 20, None) == nat.E_INVALID
+    assert lib.daam_analysis_last_error().decode() == words
 
 
 def test_reference_agrees_with_the_oracle_on_squares():

@@ -1,13 +1,7 @@
-"""Token co-attention without a GPU: ``daam_token_gram`` lives in ``libdaam_analysis.so``, the one side library (the libraries' kernels
-stay what they were), which exports what its header declares; its argument checks answer before any device call, no kernel instance
-has scratch, the engine hands ``daam_token_gram`` the descriptors of ``key_scores`` (a recording stand-in below), the ``KeyCoattention``
-arithmetic, and the float64 reference and bound of ``tests/_gram_domain.py`` themselves."""
+"""Token co-attention without a GPU (the library itself: ``test_analysis_library_cpu.py``): the argument checks of ``daam_token_gram``
+answer before any device call, the engine hands it the descriptors of ``key_scores`` (a recording stand-in below), the
+``KeyCoattention`` arithmetic, and the float64 reference and bound of ``tests/_gram_domain.py`` themselves."""
 import ctypes
-import json
-import os
-import re
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,9 +9,6 @@ import torch
 
 import _gram_domain as gd
 from _fake_native import fake_engine  # noqa: F401 -- the fixture
-from test_tap_walk_cpu import _kernel_descriptors
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope='module')
@@ -25,66 +16,6 @@ def built():
     from daam_amd import build
     build.build(verbose=False)
     return build.ANALYSIS_OUT
-
-
-def test_token_gram_is_in_the_one_side_library(built):
-    from daam_amd import _native as nat, build
-    assert os.path.exists(built) and os.path.exists(build.OUT) and not build.analysis_stale()
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.ANALYSIS_SOURCES + build.ANALYSIS_HEADERS)
-    others = set(build.SOURCES) | set(build.HEADERS)
-    mine = {'daam_token_gram.hip', 'daam_token_gram.h', 'daam_key_planes.h'}
-    assert 'daam_token_gram.hip' in build.ANALYSIS_SOURCES and mine <= set(build.ANALYSIS_SOURCES + build.ANALYSIS_HEADERS)
-    assert not set(build.ANALYSIS_SOURCES) & others and not mine & others
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_analysis.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.ANALYSIS_EXPORTS) and len(exported) == 5
-    assert {'daam_token_gram', 'daam_token_gram_scratch_bytes'} <= set(exported)
-    assert nat.load_analysis().daam_analysis_abi_version() == 2 == nat.ANALYSIS_ABI_VERSION
-    # no third library: the build knows two outputs (what it writes: test_deleted_side_library_is_rebuilt_alone)
-    assert sorted(n for n in vars(build) if n.endswith('OUT')) == ['ANALYSIS_OUT', 'OUT']
-
-
-def test_the_other_libraries_are_what_they_were(built):
-    from daam_amd import _native as nat, build
-    rec = json.load(open(os.path.join(ROOT, 'profiles', 'finalize_launch_refactor.json')))
-    have = build.kernel_shas(build.OUT)
-    assert len(have) == 191 and {k: have.get(k) for k in rec['kernel_shas']} == rec['kernel_shas']
-    assert nat.load().daam_abi_version() == 6 and nat.load_analysis().daam_analysis_abi_version() == 2
-    # every kernel of the side library is the machine code its profile was measured on
-    want = dict(json.load(open(os.path.join(ROOT, 'profiles', 'key_scores.json')))['kernel_shas'])
-    gram = json.load(open(os.path.join(ROOT, 'profiles', 'token_gram.json')))['kernel_shas']
-    want.update(gram)
-    mine = build.kernel_shas(built)
-    assert len(mine) == 19 and mine == want
-    # 16-bit path: 2 dtypes x 3 row-block counts; f32 path: 3 dtypes x 3; the join
-    assert len(gram) == 16 and sum('token_gram_kernel' in k for k in mine) == 15 and sum('token_gram_join_kernel' in k for k in mine) == 1
-
-
-def test_deleted_side_library_is_rebuilt_alone(built):
-    from daam_amd import build
-    others = (build.OUT, build.fastpath_out())
-    stamps = [os.path.getmtime(p) for p in others]
-    files = sorted(os.listdir(build.HERE))
-    os.remove(built)
-    assert not build.stale() and build.analysis_stale()
-    build.build(verbose=False)
-    assert os.path.exists(built) and not build.analysis_stale()
-    assert [os.path.getmtime(p) for p in others] == stamps
-    assert sorted(os.listdir(build.HERE)) == files               # the build writes no other file: no further library
-
-
-def test_no_instance_has_scratch(built):
-    """A resource check only: private segment size 0 and the private-segment enable bit clear in every kernel descriptor."""
-    from daam_amd import build
-    kds = _kernel_descriptors(built)
-    names = list(build.kernel_shas(built))
-    assert len(names) == 19 and all(k in kds for k in names)
-    for k in names:
-        private, = struct.unpack_from('<I', kds[k], 4)
-        _, rsrc2 = struct.unpack_from('<II', kds[k], 48)
-        assert private == 0 and not (rsrc2 & 1), (k, private)
 
 
 def test_out_of_limits_arguments_are_refused_on_the_host(built):

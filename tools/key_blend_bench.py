@@ -112,7 +112,8 @@ def main():
         eng.close()
     res = dict(workload=f'synthetic signed fp16 sums, 77 rows, maps of 64 x 64; one sample = one call of a leg between two HIP events, host '
                         f'enqueue included; {args.reps} samples after warm-up, the legs alternating in one process on the same buffers',
-               device=torch.cuda.get_device_name(0), margin=MARGIN, kernel_shas=build.kernel_shas(build.blend_out()), results=rows)
+               device=torch.cuda.get_device_name(0), margin=MARGIN,
+               kernel_shas={k: v for k, v in build.kernel_shas(build.ANALYSIS_OUT).items() if 'key_blend' in k}, results=rows)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(res, f, indent=1)
