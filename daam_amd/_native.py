@@ -187,5 +187,36 @@ def check_analysis(rc: int) -> None:
         raise DaamError(rc, msg.decode() if msg else '')
 
 
+# ---- libdaam_eval.so (C ABI: include/daam_eval.h) ---------------------------------------------------------------------------------
+EVAL_LIB_NAME = 'libdaam_eval.so'
+EVAL_LIB_PATH = os.environ.get('DAAM_EVAL_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), EVAL_LIB_NAME)
+EVAL_ABI_VERSION = 1
+EVAL_EXPORTS = ('daam_threshold_sweep', 'daam_threshold_sweep_workspace', 'daam_eval_abi_version', 'daam_eval_last_error')
+
+_eval = None
+
+
+def load_eval() -> ctypes.CDLL:
+    """The segmentation-evaluation library (threshold sweeps); like ``load`` it has no fallback."""
+    global _eval
+    if _eval is not None:
+        return _eval
+    lib = _open(EVAL_LIB_PATH, 'the threshold sweep', EVAL_EXPORTS, 'daam_eval_abi_version', EVAL_ABI_VERSION)
+    lib.daam_threshold_sweep.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_void_p, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.daam_threshold_sweep.restype = c_int
+    lib.daam_threshold_sweep_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.daam_threshold_sweep_workspace.restype = c_size_t
+    lib.daam_eval_last_error.restype = c_char_p
+    _eval = lib
+    return lib
+
+
+def check_eval(rc: int) -> None:
+    if rc != 0:
+        msg = load_eval().daam_eval_last_error()
+        raise DaamError(rc, msg.decode() if msg else '')
+
+
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -19,6 +19,11 @@ ANALYSIS_HEADERS = ['daam_key_planes.h', 'daam_key_scores.h', 'daam_token_gram.h
                     'daam_elem.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'),
                     os.path.join('..', '..', 'include', 'daam_analysis.h')]
 ANALYSIS_OUT = os.path.join(HERE, 'libdaam_analysis.so')
+# libdaam_eval.so (include/daam_eval.h): segmentation evaluation -- the threshold sweep.  It restates what it shares with
+# daam_word_masks.hip and reads daam_epilogue.h; like the analysis library it stays out of SOURCES / HEADERS.
+EVAL_SOURCES = ['daam_threshold_sweep.hip']
+EVAL_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_eval.h')]
+EVAL_LIB = os.path.join(HERE, 'libdaam_eval.so')
 
 
 def csrc_sha() -> str:
@@ -116,6 +121,25 @@ def build_analysis(force: bool = False, verbose: bool = True) -> str:
     return ANALYSIS_OUT
 
 
+def eval_stale() -> bool:
+    if not os.path.exists(EVAL_LIB):
+        return True
+    t = os.path.getmtime(EVAL_LIB)
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in EVAL_SOURCES + EVAL_HEADERS)
+
+
+def build_eval(force: bool = False, verbose: bool = True) -> str:
+    """``libdaam_eval.so``: one hipcc command, when it is missing or older than what it is made of."""
+    if not force and not eval_stale():
+        return EVAL_LIB
+    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
+           *[os.path.join(HERE, 'csrc', f) for f in EVAL_SOURCES], '-o', EVAL_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return EVAL_LIB
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -169,6 +193,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     from concurrent.futures import ThreadPoolExecutor
     build_fastpath(force, verbose)
     build_analysis(force, verbose)
+    build_eval(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

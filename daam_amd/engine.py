@@ -1348,6 +1348,110 @@ def word_masks(maps: torch.Tensor, idx_lists: Sequence[Sequence[int]], out_h: in
     return word_maps, masks, label_map
 
 
+def word_maps(maps: torch.Tensor, idx_lists: Sequence[Sequence[int]]) -> torch.Tensor:
+    """The mean planes alone, fp32 [len(idx_lists), h, w]: ``daam_word_masks`` without masks or labels (one launch per 32 words or
+    255 indices), so the planes are the ones ``word_masks`` returns, bit for bit."""
+    _check_maps(maps)
+    idx_lists = [[int(i) for i in idxs] for idxs in idx_lists]
+    rows, h, w = maps.shape
+    out = torch.empty(len(idx_lists), h, w, dtype=torch.float32, device=maps.device)
+    ws = torch.empty(2 * MAX_MASK_WORDS, dtype=torch.float32, device=maps.device)
+    first = 0
+    while first < len(idx_lists):
+        flat, begin = [], [0]
+        for idxs in idx_lists[first:first + MAX_MASK_WORDS]:
+            if not idxs:
+                raise ValueError('word_maps: a word with no token indices')
+            for i in idxs:
+                if not 0 <= i < rows:
+                    raise IndexError(f'index {i} is out of bounds for dimension 0 with size {rows}')
+            if len(idxs) > MAX_MASK_INDICES:
+                raise ValueError(f'word_maps: a word of {len(idxs)} token indices, at most {MAX_MASK_INDICES}')
+            if len(flat) + len(idxs) > MAX_MASK_INDICES:
+                break
+            flat += idxs
+            begin.append(len(flat))
+        n = len(begin) - 1
+        nat.check(nat.load().daam_word_masks(
+            maps.data_ptr(), rows, h, w, (ctypes.c_int32 * len(flat))(*flat), (ctypes.c_int32 * len(begin))(*begin), n,
+            out[first:].data_ptr(), 1, 1, 1, 0.0, None, None, ws.data_ptr(), torch.cuda.current_stream(maps.device).cuda_stream))
+        first += n
+    return out
+
+
+MAX_SWEEP_WORDS, MAX_SWEEP_TRUTH, MAX_SWEEP_THRESHOLDS = 32, 32, 64        # limits of one daam_threshold_sweep call (include/daam_eval.h)
+
+
+def _launch_threshold_sweep(planes: torch.Tensor, out_h: int, out_w: int, absolute: bool, thresholds: Sequence[float],
+                            truth: Optional[torch.Tensor]):
+    """One ``daam_threshold_sweep`` call: ``planes`` [W <= 32, h, w] fp32, ``thresholds`` <= 64 ascending floats, ``truth``
+    [G <= 32, out_h, out_w] uint8 or None -> int32 ``(pred_area [W, T], inter [W, G, T] or None, truth_area [G] or None)``.  The
+    counts are below 2^31."""
+    lib = nat.load_eval()
+    n, h, w = planes.shape
+    g, t = 0 if truth is None else truth.shape[0], len(thresholds)
+    dev = planes.device
+    pred = torch.empty(n, t, dtype=torch.int32, device=dev)
+    inter = torch.empty(n, g, t, dtype=torch.int32, device=dev) if g else None
+    area = torch.empty(g, dtype=torch.int32, device=dev) if g else None
+    need = lib.daam_threshold_sweep_workspace(n, g, t, out_h, out_w)
+    if not need:
+        raise ValueError(f'threshold sweep of {n} words, {g} truth masks, {t} thresholds at {out_h} x {out_w}: out of range')
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        nat.check_eval(lib.daam_threshold_sweep(
+            planes.data_ptr(), n, h, w, out_h, out_w, 1 if absolute else 0, (ctypes.c_float * t)(*thresholds), t,
+            truth.data_ptr() if g else None, g, pred.data_ptr(), inter.data_ptr() if g else None, area.data_ptr() if g else None,
+            ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream))
+    return pred, inter, area
+
+
+def threshold_sweep(word_maps: torch.Tensor, out_h: int, out_w: int, thresholds, truth: Optional[torch.Tensor] = None,
+                    absolute: bool = False):
+    """``daam_threshold_sweep``: what ``word_masks(threshold=t)`` followed by ``mask_overlap_matrix`` counts, for every ``t`` of
+    ``thresholds`` at once.  ``word_maps`` [W, h, w] fp32 are the un-expanded mean planes (``word_maps()``, or the first result of
+    ``word_masks``), ``truth`` [G, out_h, out_w] (or [out_h, out_w]) uint8 / bool masks (a byte != 0 is set; other dtypes through
+    ``!= 0``; CPU masks are moved to the device) or None.  Returns int32 device tensors ``(area_pred [W, T], intersection
+    [W, G, T] or None, area_truth [G] or None)``, the thresholds in the caller's order: they go to the device sorted and without
+    duplicates (as f32), and more than 32 words, 32 truth masks or 64 distinct thresholds run in blocks that are stitched on the
+    device.  Two passes at image resolution per block whatever the number of thresholds; no plane of out_h x out_w is written."""
+    from .evaluate import _as_masks
+    _check_maps(word_maps)
+    out_h, out_w = int(out_h), int(out_w)
+    thr = np.asarray(thresholds.detach().cpu().numpy() if isinstance(thresholds, torch.Tensor) else thresholds, dtype=np.float32).reshape(-1)
+    if thr.size == 0 or not np.isfinite(thr).all():
+        raise ValueError('threshold_sweep needs at least one threshold, all of them finite')
+    if word_maps.shape[0] < 1:
+        raise ValueError('threshold_sweep needs at least one word map')
+    uniq, inverse = np.unique(thr, return_inverse=True)
+    if truth is not None:
+        truth = _as_masks(truth, 'truth', word_maps.device)
+        if truth.device != word_maps.device:
+            raise RuntimeError('daam_amd: word maps and truth masks are on different devices')
+        if tuple(truth.shape[1:]) != (out_h, out_w):
+            raise ValueError(f'truth masks of {tuple(truth.shape[1:])} for an output of {(out_h, out_w)}: threshold_sweep does not resize them')
+    truth_blocks = [None] if truth is None else [truth[g:g + MAX_SWEEP_TRUTH] for g in range(0, truth.shape[0], MAX_SWEEP_TRUTH)]
+    thr_blocks = [[float(t) for t in uniq[k:k + MAX_SWEEP_THRESHOLDS]] for k in range(0, uniq.size, MAX_SWEEP_THRESHOLDS)]
+    pred_rows, inter_rows, areas = [], [], []
+    for i in range(0, word_maps.shape[0], MAX_SWEEP_WORDS):
+        pred_cols, inter_cols = [], []
+        for ts in thr_blocks:
+            parts = [_launch_threshold_sweep(word_maps[i:i + MAX_SWEEP_WORDS], out_h, out_w, absolute, ts, tb) for tb in truth_blocks]
+            pred_cols.append(parts[0][0])
+            if truth is not None:
+                inter_cols.append(torch.cat([p[1] for p in parts], dim=1))
+                if not areas:
+                    areas = [p[2] for p in parts]
+        pred_rows.append(torch.cat(pred_cols, dim=1))
+        if truth is not None:
+            inter_rows.append(torch.cat(inter_cols, dim=2))
+    order = torch.as_tensor(np.ascontiguousarray(inverse.reshape(-1)), dtype=torch.long).to(word_maps.device)
+    pred = torch.cat(pred_rows).index_select(1, order)
+    if truth is None:
+        return pred, None, None
+    return pred, torch.cat(inter_rows).index_select(2, order), torch.cat(areas)
+
+
 def _check_maps(maps: torch.Tensor) -> None:
     if maps.device.type != 'cuda':
         raise RuntimeError('daam_amd: heat maps must live on the HIP device (no CPU fallback)')

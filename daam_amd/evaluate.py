@@ -24,7 +24,7 @@ import torch
 from . import _native as nat
 
 __all__ = ['compute_iou', 'compute_ioa', 'mask_overlap', 'compute_iou_batch', 'compute_ioa_batch', 'load_mask',
-           'MeanEvaluator', 'UnsupervisedEvaluator', 'mask_overlap_matrix', 'MaskOverlaps']
+           'MeanEvaluator', 'UnsupervisedEvaluator', 'mask_overlap_matrix', 'MaskOverlaps', 'SweepEvaluator']
 
 MAX_MATRIX_MASKS = 32                              # masks per stack of one daam_mask_overlap_matrix call (include/daam_hip.h)
 
@@ -287,3 +287,49 @@ class MeanEvaluator:
     def __str__(self):
         return (f'{self.name}<{self.mean_iou:.4f} (±{self.ci95_miou:.3f} mIoU) {self.mean_intensity:.4f} (mInt) '
                 f'{len(self)} samples>')
+
+
+class SweepEvaluator:
+    """``MeanEvaluator``'s mean IoU as a curve over the threshold: ``log`` takes the ``heatmap.ThresholdSweep`` of one image and
+    appends, per threshold, what ``MeanEvaluator.log_iou`` would log there -- the best IoU among the candidate pairings of a word --
+    so one pass over a data set gives the mIoU at every threshold and the threshold to report."""
+
+    def __init__(self, name: str = 'SweepEvaluator'):
+        self.name = name
+        self.thresholds: Optional[np.ndarray] = None       # f32 [T], set by the first log
+        self.ious: List[np.ndarray] = []                   # one f32 [T] per logged word
+
+    def log(self, sweep, pairs: Optional[Sequence[Tuple[int, int]]] = None) -> 'SweepEvaluator':
+        """``pairs=None``: one entry per word of ``sweep``, its IoU with the truth mask it matches best (per threshold).
+        ``pairs``: one entry per ``(word index, truth index)``.  One copy to the host per call."""
+        thr = sweep.thresholds.cpu().numpy().astype(np.float32)
+        if self.thresholds is None:
+            self.thresholds = thr
+        elif thr.shape != self.thresholds.shape or not (thr == self.thresholds).all():
+            raise ValueError('SweepEvaluator: this sweep has other thresholds than the ones logged so far')
+        iou = sweep.iou()
+        if iou.shape[1] == 0:
+            raise ValueError('SweepEvaluator: the sweep has no truth masks')
+        rows = iou.max(dim=1).values if pairs is None else torch.stack([iou[int(w), int(g)] for w, g in pairs])
+        self.ious.extend(rows.cpu().numpy().astype(np.float32))
+        return self
+
+    @property
+    def mean_iou(self) -> np.ndarray:
+        """f32 [T]: per threshold, ``MeanEvaluator.mean_iou`` of the values logged there."""
+        cols = np.ascontiguousarray(np.stack(self.ious).astype(np.float64).T)
+        return np.array([np.mean(c) for c in cols], dtype=np.float32)
+
+    @property
+    def best(self) -> Tuple[float, float]:
+        """``(threshold, mIoU)`` of the largest mean IoU; the lowest such threshold on a tie."""
+        curve = self.mean_iou
+        t = min(np.flatnonzero(curve == curve.max()), key=lambda i: self.thresholds[i])
+        return float(self.thresholds[t]), float(curve[t])
+
+    def __len__(self) -> int:
+        return len(self.ious)
+
+    def __str__(self):
+        thr, miou = self.best
+        return f'{self.name}<{miou:.4f} (mIoU) at threshold {thr:g}, {len(self.thresholds)} thresholds, {len(self)} samples>'

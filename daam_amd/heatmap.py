@@ -13,7 +13,7 @@ from . import engine as _engine
 from .utils import cached_nlp, compute_token_merge_indices
 
 __all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair', 'Segmentation',
-           'RegionAttribution', 'KeyScores']
+           'RegionAttribution', 'KeyScores', 'ThresholdSweep']
 
 RawHeatMapKey = Tuple[int, int, int]  # factor, layer, head
 
@@ -145,6 +145,75 @@ class Segmentation:
     def cpu(self) -> 'Segmentation':
         maps = [WordHeatMap(m.heatmap.cpu(), m.word, m.word_idx) for m in self.word_heat_maps]
         return Segmentation(list(self.words), maps, self.masks.cpu(), None if self.labels is None else self.labels.cpu())
+
+
+@dataclass
+class ThresholdSweep:
+    """The pixel counts behind IoU / IoA of every word's mask against every truth mask at every threshold
+    (``GlobalHeatMap.threshold_sweep``): what ``segment(threshold=t)`` followed by ``Segmentation.overlaps(truth)`` counts, for all
+    ``t`` from two passes at image resolution.  Everything lives on the device until ``cpu()`` is asked for."""
+    words: List[str]
+    thresholds: torch.Tensor                    # f32 [T], in the caller's order
+    intersection: torch.Tensor                  # int32 [W, G, T]: pixels where word w's value > thresholds[t] and truth g is set
+    area_pred: torch.Tensor                     # int32 [W, T]: pixels where word w's value > thresholds[t]
+    area_truth: torch.Tensor                    # int32 [G]
+
+    def iou(self) -> torch.Tensor:
+        """f32 [W, G, T], in ``evaluate._ratios``' operand order: inter / ((pred + truth - inter) + 1e-8) -- ``[..., t]`` is
+        bit-equal to ``Segmentation.iou`` at ``thresholds[t]``."""
+        inter = self.intersection.to(torch.float32)
+        union = self.area_pred.to(torch.float32)[:, None, :] + self.area_truth.to(torch.float32)[None, :, None] - inter
+        return inter / (union + 1e-8)
+
+    def ioa(self) -> torch.Tensor:
+        """f32 [W, G, T]: inter / (pred + 1e-8), ``Segmentation.ioa`` at every threshold."""
+        return self.intersection.to(torch.float32) / (self.area_pred.to(torch.float32)[:, None, :] + 1e-8)
+
+    def precision(self) -> torch.Tensor:
+        return self.ioa()
+
+    def recall(self) -> torch.Tensor:
+        """f32 [W, G, T]: inter / (truth + 1e-8)."""
+        return self.intersection.to(torch.float32) / (self.area_truth.to(torch.float32)[None, :, None] + 1e-8)
+
+    def _word(self, word: Union[str, int]) -> int:
+        if isinstance(word, str):
+            if word not in self.words:
+                raise KeyError(word)
+            return self.words.index(word)
+        return int(word)
+
+    def best(self, word: Union[str, int], truth_idx: int = 0) -> Tuple[float, float]:
+        """``(threshold, iou)`` of the largest IoU of ``word`` (a word of ``words`` or its index) against truth mask
+        ``truth_idx``; the lowest such threshold on a tie."""
+        curve = self.iou()[self._word(word), truth_idx].cpu()
+        best = curve.max()
+        thr = self.thresholds.cpu()
+        t = min(range(len(curve)), key=lambda i: (not bool(curve[i] == best), float(thr[i])))
+        return float(thr[t]), float(curve[t])
+
+    def mean_best_iou(self) -> torch.Tensor:
+        """f32 [T]: the mean over the words of each word's best IoU over the truth masks -- per threshold, what
+        ``MeanEvaluator.log_iou`` logs (the best candidate pairing), averaged."""
+        return self.iou().max(dim=1).values.mean(dim=0)
+
+    def best_threshold(self) -> float:
+        """The threshold with the largest ``mean_best_iou()``; the lowest such on a tie."""
+        curve, thr = self.mean_best_iou().cpu(), self.thresholds.cpu()
+        best = curve.max()
+        return float(min((float(thr[i]) for i in range(len(curve)) if bool(curve[i] == best))))
+
+    def at(self, threshold: float):
+        """``evaluate.MaskOverlaps`` of one threshold of the sweep (KeyError when it was not swept)."""
+        from .evaluate import MaskOverlaps
+        hits = (self.thresholds.cpu() == torch.tensor(threshold, dtype=torch.float32)).nonzero()
+        if not len(hits):
+            raise KeyError(threshold)
+        t = int(hits[0])
+        return MaskOverlaps(self.intersection[:, :, t], self.area_pred[:, t], self.area_truth)
+
+    def cpu(self) -> 'ThresholdSweep':
+        return ThresholdSweep(list(self.words), self.thresholds.cpu(), self.intersection.cpu(), self.area_pred.cpu(), self.area_truth.cpu())
 
 
 @dataclass
@@ -301,6 +370,29 @@ class GlobalHeatMap:
         planes = [plane for wm in word_maps for plane in wm]
         heat = [WordHeatMap(plane, w, r[1]) for plane, (w, _), r in zip(planes, pairs, resolved)]
         return Segmentation([w for w, _ in pairs], heat, masks[0] if len(masks) == 1 else torch.cat(masks), label_map)
+
+    def threshold_sweep(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]], image,
+                        truth: Union[None, torch.Tensor, Segmentation] = None, thresholds=None, absolute: bool = False) -> ThresholdSweep:
+        """``segment(words, image, threshold=t).overlaps(truth)`` for every ``t`` of ``thresholds`` (default 0, 0.05 .. 1) at the cost
+        of about one ``segment`` call (``engine.threshold_sweep``: the expansion is the same at every threshold, only a comparison
+        changes).  Words are resolved as in ``segment`` and the output is sized as in ``expand_as``; ``truth`` is a mask [H, W], a
+        stack [G, H, W] of that size (uint8 / bool as they are, other dtypes through ``!= 0``) or a ``Segmentation``; ``None``
+        leaves the predicted areas alone (G = 0)."""
+        pairs = [(w, None) if isinstance(w, str) else (w[0], w[1]) for w in words]
+        if not pairs:
+            raise ValueError('threshold_sweep needs at least one word')
+        resolved = [compute_token_merge_indices(self.tokenizer, self.prompt, w, i) for w, i in pairs]
+        maps = self.heat_maps
+        size = (image.size[0], image.size[1]) if maps.shape[-2] == maps.shape[-1] else (image.size[1], image.size[0])
+        thresholds = [i / 20 for i in range(21)] if thresholds is None else thresholds
+        masks = truth.masks if isinstance(truth, Segmentation) else truth
+        planes = _engine.word_maps(maps, [idxs for idxs, _ in resolved])
+        pred, inter, area = _engine.threshold_sweep(planes, int(size[0]), int(size[1]), thresholds, masks, absolute=absolute)
+        thr = torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1).to(pred.device)
+        if inter is None:
+            inter = torch.zeros(pred.shape[0], 0, pred.shape[1], dtype=torch.int32, device=pred.device)
+            area = torch.zeros(0, dtype=torch.int32, device=pred.device)
+        return ThresholdSweep([w for w, _ in pairs], thr, inter, pred, area)
 
     def attribute(self, regions: Union[torch.Tensor, Segmentation]) -> RegionAttribution:
         """The opposite question to ``segment``: for each region -- ``regions`` is a mask [H, W], a stack [M, H, W] (uint8 / bool as
