@@ -218,5 +218,36 @@ def check_eval(rc: int) -> None:
         raise DaamError(rc, msg.decode() if msg else '')
 
 
+# ---- libdaam_locate.so (C ABI: include/daam_locate.h) -----------------------------------------------------------------------------
+LOCATE_LIB_NAME = 'libdaam_locate.so'
+LOCATE_LIB_PATH = os.environ.get('DAAM_LOCATE_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), LOCATE_LIB_NAME)
+LOCATE_ABI_VERSION = 1
+LOCATE_EXPORTS = ('daam_localize', 'daam_localize_workspace', 'daam_locate_abi_version', 'daam_locate_last_error')
+
+_locate = None
+
+
+def load_locate() -> ctypes.CDLL:
+    """The localisation library (boxes, peaks, pointing hits); like ``load`` it has no fallback."""
+    global _locate
+    if _locate is not None:
+        return _locate
+    lib = _open(LOCATE_LIB_PATH, 'localize', LOCATE_EXPORTS, 'daam_locate_abi_version', LOCATE_ABI_VERSION)
+    lib.daam_localize.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.daam_localize.restype = c_int
+    lib.daam_localize_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.daam_localize_workspace.restype = c_size_t
+    lib.daam_locate_last_error.restype = c_char_p
+    _locate = lib
+    return lib
+
+
+def check_locate(rc: int) -> None:
+    if rc != 0:
+        msg = load_locate().daam_locate_last_error()
+        raise DaamError(rc, msg.decode() if msg else '')
+
+
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -24,6 +24,11 @@ ANALYSIS_OUT = os.path.join(HERE, 'libdaam_analysis.so')
 EVAL_SOURCES = ['daam_threshold_sweep.hip']
 EVAL_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_eval.h')]
 EVAL_LIB = os.path.join(HERE, 'libdaam_eval.so')
+# libdaam_locate.so (include/daam_locate.h): localisation -- boxes, peaks and pointing hits.  Like the evaluation library it restates
+# what it shares with daam_word_masks.hip through daam_epilogue.h and stays out of every list above.
+LOCATE_SOURCES = ['daam_locate.hip']
+LOCATE_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_locate.h')]
+LOCATE_LIB = os.path.join(HERE, 'libdaam_locate.so')
 
 
 def csrc_sha() -> str:
@@ -140,6 +145,25 @@ def build_eval(force: bool = False, verbose: bool = True) -> str:
     return EVAL_LIB
 
 
+def locate_stale() -> bool:
+    if not os.path.exists(LOCATE_LIB):
+        return True
+    t = os.path.getmtime(LOCATE_LIB)
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in LOCATE_SOURCES + LOCATE_HEADERS)
+
+
+def build_locate(force: bool = False, verbose: bool = True) -> str:
+    """``libdaam_locate.so``: one hipcc command, when it is missing or older than what it is made of."""
+    if not force and not locate_stale():
+        return LOCATE_LIB
+    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
+           *[os.path.join(HERE, 'csrc', f) for f in LOCATE_SOURCES], '-o', LOCATE_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return LOCATE_LIB
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -194,6 +218,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     build_fastpath(force, verbose)
     build_analysis(force, verbose)
     build_eval(force, verbose)
+    build_locate(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

@@ -1452,6 +1452,82 @@ def threshold_sweep(word_maps: torch.Tensor, out_h: int, out_w: int, thresholds,
     return pred, torch.cat(inter_rows).index_select(2, order), torch.cat(areas)
 
 
+MAX_LOCATE_WORDS, MAX_LOCATE_TRUTH, MAX_LOCATE_THRESHOLDS = 32, 32, 64     # limits of one daam_localize call (include/daam_locate.h)
+
+
+def _launch_localize(planes: Optional[torch.Tensor], out_h: int, out_w: int, absolute: bool, thresholds: Sequence[float],
+                     truth: Optional[torch.Tensor]):
+    """One ``daam_localize`` call: ``planes`` [W <= 32, h, w] fp32 or None, ``thresholds`` <= 64 floats in any order, ``truth``
+    [G <= 32, out_h, out_w] uint8 or None -> ``(boxes int32 [W, T, 4], peaks int32 [W, 2], peak_values f32 [W, 3], truth_boxes int32
+    [G, 4] or None, hits uint8 [W, G] or None)``; the first three are None without planes."""
+    lib = nat.load_locate()
+    n, h, w = (0, 1, 1) if planes is None else planes.shape
+    g, t = 0 if truth is None else truth.shape[0], len(thresholds)
+    dev = truth.device if planes is None else planes.device
+    boxes = torch.empty(n, t, 4, dtype=torch.int32, device=dev) if n else None
+    peaks = torch.empty(n, 2, dtype=torch.int32, device=dev) if n else None
+    values = torch.empty(n, 3, dtype=torch.float32, device=dev) if n else None
+    truth_boxes = torch.empty(g, 4, dtype=torch.int32, device=dev) if g else None
+    hits = torch.empty(n, g, dtype=torch.uint8, device=dev) if n and g else None
+    need = lib.daam_localize_workspace(n, g, t, out_h, out_w)
+    if not need:
+        raise ValueError(f'localize of {n} words, {g} truth masks, {t} thresholds at {out_h} x {out_w}: out of range')
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        nat.check_locate(lib.daam_localize(
+            planes.data_ptr() if n else None, n, h, w, out_h, out_w, 1 if absolute else 0, (ctypes.c_float * max(t, 1))(*thresholds), t,
+            truth.data_ptr() if g else None, g, boxes.data_ptr() if n and t else None, peaks.data_ptr() if n else None,
+            values.data_ptr() if n else None, truth_boxes.data_ptr() if g else None, hits.data_ptr() if n and g else None,
+            ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream))
+    return boxes, peaks, values, truth_boxes, hits
+
+
+def localize(word_maps: torch.Tensor, out_h: int, out_w: int, thresholds=(), truth: Optional[torch.Tensor] = None,
+             absolute: bool = False):
+    """``daam_localize``: per word and threshold the bounding box of the mask ``word_masks(threshold=t)`` gives, every word's peak
+    (the arg-max of its expanded map) and whether it lies inside each truth mask, from one pass at image resolution whatever the
+    number of thresholds.  ``word_maps`` [W, h, w] fp32 are the un-expanded mean planes (``word_maps()``), ``truth`` [G, out_h,
+    out_w] (or [out_h, out_w]) uint8 / bool masks (a byte != 0 is set; other dtypes through ``!= 0``; CPU masks are moved to the
+    device) or None.  Returns device tensors ``(boxes int32 [W, T, 4] -- x0 y0 x1 y1 inclusive, (out_w, out_h, -1, -1) when empty --,
+    peaks int32 [W, 2] -- x, y --, peak_values f32 [W, 3] -- the raw expanded value at the peak, the minimum, the maximum --,
+    truth_boxes int32 [G, 4] or None, hits bool [W, G] or None)``.  The thresholds are taken as they come (any order, duplicates
+    allowed); more than 32 words, 32 truth masks or 64 thresholds run in blocks that are stitched on the device."""
+    from .evaluate import _as_masks
+    _check_maps(word_maps)
+    out_h, out_w = int(out_h), int(out_w)
+    thr = np.asarray(thresholds.detach().cpu().numpy() if isinstance(thresholds, torch.Tensor) else thresholds, dtype=np.float32).reshape(-1)
+    if not np.isfinite(thr).all():
+        raise ValueError('localize needs finite thresholds')
+    if word_maps.shape[0] < 1:
+        raise ValueError('localize needs at least one word map')
+    if truth is not None:
+        truth = _as_masks(truth, 'truth', word_maps.device)
+        if truth.device != word_maps.device:
+            raise RuntimeError('daam_amd: word maps and truth masks are on different devices')
+        if tuple(truth.shape[1:]) != (out_h, out_w):
+            raise ValueError(f'truth masks of {tuple(truth.shape[1:])} for an output of {(out_h, out_w)}: localize does not resize them')
+    truth_blocks = [None] if truth is None else [truth[g:g + MAX_LOCATE_TRUTH] for g in range(0, truth.shape[0], MAX_LOCATE_TRUTH)]
+    thr_blocks = [[float(t) for t in thr[k:k + MAX_LOCATE_THRESHOLDS]] for k in range(0, thr.size, MAX_LOCATE_THRESHOLDS)] or [[]]
+    box_rows, peak_rows, value_rows, hit_rows, truth_boxes = [], [], [], [], []
+    for i in range(0, word_maps.shape[0], MAX_LOCATE_WORDS):
+        planes = word_maps[i:i + MAX_LOCATE_WORDS]
+        # the first block of thresholds goes with the first block of truth masks; the other blocks of either go alone
+        first = _launch_localize(planes, out_h, out_w, absolute, thr_blocks[0], truth_blocks[0])
+        cols = [first[0]] + [_launch_localize(planes, out_h, out_w, absolute, ts, None)[0] for ts in thr_blocks[1:]]
+        rest = [_launch_localize(planes, out_h, out_w, absolute, [], tb) for tb in truth_blocks[1:]]
+        box_rows.append(torch.zeros(planes.shape[0], 0, 4, dtype=torch.int32, device=planes.device) if cols[0] is None else torch.cat(cols, dim=1))
+        peak_rows.append(first[1])
+        value_rows.append(first[2])
+        if truth is not None:
+            hit_rows.append(torch.cat([first[4]] + [r[4] for r in rest], dim=1))
+            if not truth_boxes:
+                truth_boxes = [first[3]] + [r[3] for r in rest]
+    out = (torch.cat(box_rows), torch.cat(peak_rows), torch.cat(value_rows))
+    if truth is None:
+        return out + (None, None)
+    return out + (torch.cat(truth_boxes), torch.cat(hit_rows) != 0)
+
+
 def _check_maps(maps: torch.Tensor) -> None:
     if maps.device.type != 'cuda':
         raise RuntimeError('daam_amd: heat maps must live on the HIP device (no CPU fallback)')

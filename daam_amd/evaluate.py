@@ -24,7 +24,8 @@ import torch
 from . import _native as nat
 
 __all__ = ['compute_iou', 'compute_ioa', 'mask_overlap', 'compute_iou_batch', 'compute_ioa_batch', 'load_mask',
-           'MeanEvaluator', 'UnsupervisedEvaluator', 'mask_overlap_matrix', 'MaskOverlaps', 'SweepEvaluator']
+           'MeanEvaluator', 'UnsupervisedEvaluator', 'mask_overlap_matrix', 'MaskOverlaps', 'SweepEvaluator', 'mask_boxes',
+           'LocalizationEvaluator']
 
 MAX_MATRIX_MASKS = 32                              # masks per stack of one daam_mask_overlap_matrix call (include/daam_hip.h)
 
@@ -173,6 +174,17 @@ def mask_overlap_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None) -> Ma
             blocks[i, j], area_a[i], area_b[j] = _launch_overlap_matrix(a[i:i + step], None if b is None and i == j else cols[j:j + step])
     inter = torch.cat([torch.cat([blocks[i, j] for j in range(0, cols.shape[0], step)], dim=1) for i in range(0, a.shape[0], step)])
     return MaskOverlaps(inter, torch.cat([area_a[i] for i in sorted(area_a)]), torch.cat([area_b[j] for j in sorted(area_b)]))
+
+
+def mask_boxes(masks: torch.Tensor) -> torch.Tensor:
+    """int32 [M, 4] on the device: the bounding box ``x0 y0 x1 y1`` (inclusive) of the set pixels of every mask of ``masks`` [M, h, w]
+    (or [h, w]; uint8 / bool as they are, other dtypes through ``!= 0``; CPU masks are moved to the device), ``(w, h, -1, -1)`` for a
+    mask with none: ``daam_localize`` without words, every byte read once, 32 masks per launch."""
+    from . import engine
+    masks = _as_masks(masks, 'masks')
+    step = engine.MAX_LOCATE_TRUTH
+    parts = [engine._launch_localize(None, masks.shape[1], masks.shape[2], True, [], masks[i:i + step])[3] for i in range(0, masks.shape[0], step)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
 def load_mask(path: str) -> torch.Tensor:
@@ -333,3 +345,59 @@ class SweepEvaluator:
     def __str__(self):
         thr, miou = self.best
         return f'{self.name}<{miou:.4f} (mIoU) at threshold {thr:g}, {len(self.thresholds)} thresholds, {len(self)} samples>'
+
+
+class LocalizationEvaluator:
+    """The two localisation measures over a data set, modelled on ``SweepEvaluator``: ``log`` takes the ``heatmap.Localization`` of
+    one image and appends, per word, whether its peak hits a truth mask (the pointing game) and, per threshold, its box IoU with a
+    truth box; ``pointing_accuracy`` is the share of hits and ``corloc`` the share of entries whose box IoU is at least 0.5."""
+    IOU_BAR = 0.5
+
+    def __init__(self, name: str = 'LocalizationEvaluator'):
+        self.name = name
+        self.thresholds: Optional[np.ndarray] = None       # f32 [T], set by the first log
+        self.hits: List[bool] = []                         # one per logged entry
+        self.ious: List[np.ndarray] = []                   # one f32 [T] per logged entry
+
+    def log(self, loc, pairs: Optional[Sequence[Tuple[int, int]]] = None) -> 'LocalizationEvaluator':
+        """``pairs=None``: one entry per word of ``loc``, judged against the truth mask that serves it best (a hit in any mask; per
+        threshold the largest box IoU).  ``pairs``: one entry per ``(word index, truth index)``.  One copy to the host per call."""
+        thr = loc.thresholds.cpu().numpy().astype(np.float32)
+        if self.thresholds is None:
+            self.thresholds = thr
+        elif thr.shape != self.thresholds.shape or not (thr == self.thresholds).all():
+            raise ValueError('LocalizationEvaluator: this localization has other thresholds than the ones logged so far')
+        if loc.hits is None or loc.hits.shape[1] == 0:
+            raise ValueError('LocalizationEvaluator: the localization has no truth masks')
+        iou, hits = loc.box_iou().cpu().numpy().astype(np.float32), loc.hits.cpu().numpy().astype(bool)
+        if pairs is None:
+            self.hits.extend(bool(h) for h in hits.any(1))
+            self.ious.extend(iou.max(1))
+        else:
+            self.hits.extend(bool(hits[int(w), int(g)]) for w, g in pairs)
+            self.ious.extend(iou[int(w), int(g)] for w, g in pairs)
+        return self
+
+    @property
+    def pointing_accuracy(self) -> float:
+        return float(np.mean(self.hits))
+
+    @property
+    def corloc(self) -> np.ndarray:
+        """f32 [T]: per threshold, the share of the logged entries whose box IoU is >= 0.5."""
+        return (np.stack(self.ious) >= np.float32(self.IOU_BAR)).mean(0).astype(np.float32)
+
+    @property
+    def best(self) -> Tuple[float, float]:
+        """``(threshold, CorLoc)`` of the largest CorLoc; the lowest such threshold on a tie."""
+        curve = self.corloc
+        t = min(np.flatnonzero(curve == curve.max()), key=lambda i: self.thresholds[i])
+        return float(self.thresholds[t]), float(curve[t])
+
+    def __len__(self) -> int:
+        return len(self.hits)
+
+    def __str__(self):
+        thr, best = self.best
+        return (f'{self.name}<{self.pointing_accuracy:.4f} (pointing) {best:.4f} (CorLoc) at threshold {thr:g}, '
+                f'{len(self.thresholds)} thresholds, {len(self)} samples>')

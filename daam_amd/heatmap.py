@@ -13,7 +13,7 @@ from . import engine as _engine
 from .utils import cached_nlp, compute_token_merge_indices
 
 __all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair', 'Segmentation',
-           'RegionAttribution', 'KeyScores', 'ThresholdSweep']
+           'RegionAttribution', 'KeyScores', 'ThresholdSweep', 'Localization']
 
 RawHeatMapKey = Tuple[int, int, int]  # factor, layer, head
 
@@ -216,6 +216,71 @@ class ThresholdSweep:
         return ThresholdSweep(list(self.words), self.thresholds.cpu(), self.intersection.cpu(), self.area_pred.cpu(), self.area_truth.cpu())
 
 
+def _box_iou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """IoU of inclusive pixel boxes ``a`` [..., 4] and ``b`` [..., 4] (broadcast), f32; an empty box (x1 < x0) scores 0.  The areas
+    are exact in int64 and the ratio is formed in float64 and rounded once."""
+    a, b = a.to(torch.int64), b.to(torch.int64)
+    area_a = (a[..., 2] - a[..., 0] + 1).clamp(min=0) * (a[..., 3] - a[..., 1] + 1).clamp(min=0)
+    area_b = (b[..., 2] - b[..., 0] + 1).clamp(min=0) * (b[..., 3] - b[..., 1] + 1).clamp(min=0)
+    iw = (torch.minimum(a[..., 2], b[..., 2]) - torch.maximum(a[..., 0], b[..., 0]) + 1).clamp(min=0)
+    ih = (torch.minimum(a[..., 3], b[..., 3]) - torch.maximum(a[..., 1], b[..., 1]) + 1).clamp(min=0)
+    inter = torch.where((area_a > 0) & (area_b > 0), iw * ih, torch.zeros_like(iw))
+    union = area_a + area_b - inter
+    return (inter.to(torch.float64) / union.clamp(min=1).to(torch.float64)).to(torch.float32)
+
+
+@dataclass
+class Localization:
+    """Where the words of one prompt lie in an image (``GlobalHeatMap.localize``): the bounding box of every word's mask at every
+    threshold, the peak of every word's expanded map, the boxes of the truth masks and whether each peak lies inside each truth
+    mask (the pointing game) -- from one pass at image resolution.  Everything lives on the device until ``cpu()`` is asked for."""
+    words: List[str]
+    thresholds: torch.Tensor                    # f32 [T], in the caller's order
+    size: Tuple[int, int]                       # (height, width) of the output
+    boxes: torch.Tensor                         # int32 [W, T, 4]: x0 y0 x1 y1, inclusive; (width, height, -1, -1) when empty
+    peaks: torch.Tensor                         # int32 [W, 2]: x, y
+    peak_values: torch.Tensor                   # f32 [W, 3]: the raw expanded value at the peak, the minimum, the maximum
+    truth_boxes: Optional[torch.Tensor]         # int32 [G, 4], or None without truth masks
+    hits: Optional[torch.Tensor]                # bool [W, G]: the peak of word w lies in truth mask g; None without truth masks
+
+    def _word(self, word: Union[str, int]) -> int:
+        if isinstance(word, str):
+            if word not in self.words:
+                raise KeyError(word)
+            return self.words.index(word)
+        return int(word)
+
+    def box(self, word: Union[str, int], threshold: Optional[float] = None) -> Optional[Tuple[int, int, int, int]]:
+        """``(x0, y0, x1, y1)`` of ``word`` at ``threshold`` (``None``: the first one), ``None`` when its mask is empty there;
+        KeyError for a threshold that was not asked for."""
+        t = 0
+        if threshold is not None:
+            found = (self.thresholds.cpu() == torch.tensor(threshold, dtype=torch.float32)).nonzero()
+            if not len(found):
+                raise KeyError(threshold)
+            t = int(found[0])
+        x0, y0, x1, y1 = (int(v) for v in self.boxes[self._word(word), t].cpu())
+        return None if x1 < x0 else (x0, y0, x1, y1)
+
+    def box_iou(self, truth_boxes: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """f32 [W, G, T]: the IoU of every word's box at every threshold with every box of ``truth_boxes`` [G, 4] (inclusive pixel
+        boxes; default: the boxes of the truth masks); an empty box scores 0."""
+        truth_boxes = self.truth_boxes if truth_boxes is None else torch.as_tensor(truth_boxes).reshape(-1, 4).to(self.boxes.device)
+        if truth_boxes is None:
+            raise ValueError('box_iou needs truth boxes: the localization has no truth masks')
+        return _box_iou(self.boxes[:, None, :, :], truth_boxes[None, :, None, :])
+
+    def pointing(self) -> torch.Tensor:
+        """bool [W, G]: the pointing game -- the peak of word w lies inside truth mask g."""
+        if self.hits is None:
+            raise ValueError('pointing needs truth masks')
+        return self.hits
+
+    def cpu(self) -> 'Localization':
+        return Localization(list(self.words), self.thresholds.cpu(), self.size, self.boxes.cpu(), self.peaks.cpu(), self.peak_values.cpu(),
+                            None if self.truth_boxes is None else self.truth_boxes.cpu(), None if self.hits is None else self.hits.cpu())
+
+
 @dataclass
 class RegionAttribution:
     """Which prompt tokens put their attention inside each of M image regions (``GlobalHeatMap.attribute``): the sums of every
@@ -393,6 +458,24 @@ class GlobalHeatMap:
             inter = torch.zeros(pred.shape[0], 0, pred.shape[1], dtype=torch.int32, device=pred.device)
             area = torch.zeros(0, dtype=torch.int32, device=pred.device)
         return ThresholdSweep([w for w, _ in pairs], thr, inter, pred, area)
+
+    def localize(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]], image, thresholds=(0.4,),
+                 truth: Union[None, torch.Tensor, Segmentation] = None, absolute: bool = False) -> Localization:
+        """The bounding box of ``segment(words, image, threshold=t).masks`` for every ``t`` of ``thresholds``, the peak of every
+        word's expanded map and, with ``truth`` (a mask [H, W], a stack [G, H, W] or a ``Segmentation``), the truth masks' boxes and
+        the pointing hits -- one pass at image resolution (``engine.localize``), no mask is written.  Words are resolved as in
+        ``segment`` and the output is sized as in ``expand_as``."""
+        pairs = [(w, None) if isinstance(w, str) else (w[0], w[1]) for w in words]
+        if not pairs:
+            raise ValueError('localize needs at least one word')
+        resolved = [compute_token_merge_indices(self.tokenizer, self.prompt, w, i) for w, i in pairs]
+        maps = self.heat_maps
+        size = (image.size[0], image.size[1]) if maps.shape[-2] == maps.shape[-1] else (image.size[1], image.size[0])
+        masks = truth.masks if isinstance(truth, Segmentation) else truth
+        planes = _engine.word_maps(maps, [idxs for idxs, _ in resolved])
+        boxes, peaks, values, truth_boxes, hits = _engine.localize(planes, int(size[0]), int(size[1]), thresholds, masks, absolute=absolute)
+        thr = torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1).to(boxes.device)
+        return Localization([w for w, _ in pairs], thr, (int(size[0]), int(size[1])), boxes, peaks, values, truth_boxes, hits)
 
     def attribute(self, regions: Union[torch.Tensor, Segmentation]) -> RegionAttribution:
         """The opposite question to ``segment``: for each region -- ``regions`` is a mask [H, W], a stack [M, H, W] (uint8 / bool as
