@@ -1,12 +1,14 @@
 """Non-square generations on the device: ``finalize_rect_kernel`` (planes [h, w] -> maps [out_h, out_w]) through the raw C ABI, the tap
 routes on layers whose ``hw`` is not a square, the orientation of every view, and a traced generation with ``height=`` / ``width=``.
 
-Finalize reference: float64 numpy, ``oracle.heatmap_oracle.bicubic_taps`` (torch's f32 coefficients) applied along the rows and then
-down the columns, clamp at 0, mean over the keys.  With equal sides it is held against the oracle's ``global_heat_map``
+Finalize reference (``tests/_rect_domain.py``, which ``tests/test_gpu_rect_domain.py`` uses on multi-key walks): float64 numpy,
+``oracle.heatmap_oracle.bicubic_taps`` (torch's f32 coefficients) applied along the rows and then down the columns, clamp at 0, mean over
+the keys.  With equal sides it is held against the oracle's ``global_heat_map``
 (``test_reference_agrees_with_the_oracle_on_squares``).  Bound: the accuracy class include/daam_hip.h documents for f32 arithmetic on
 any finite planes, per token row t: max |out - exact| <= 2^-19 * max |exact|.
 Tap reference: the oracle's ``attention_probs``, kept half, reshaped [h, w] row-major; tolerances of
-``test_gpu_parity.py::test_tap_qk_vs_oracle`` for the same dtype mode."""
+``test_gpu_parity.py::test_tap_qk_vs_oracle`` for the same dtype mode; and, per probability, the float64 softmax at the bound of
+``tests/_tap_domain.py`` (``test_taps_on_rectangular_layers_per_probability``)."""
 import ctypes
 import types
 
@@ -14,8 +16,12 @@ import numpy as np
 import pytest
 import torch
 
+import _attend_domain as ad
+import _rect_domain as rd
+import _tap_domain as td
 from oracle import fake_diffusers as fd
 from oracle import heatmap_oracle as ho
+from test_gpu_layouts import _configure
 from test_gpu_parity import _dev, _qk, _to_bh
 
 pytestmark = pytest.mark.gpu
@@ -42,23 +48,8 @@ def _kernels(nat, lib, ctx, which):
     return buf.value.decode()
 
 
-# ---- the float64 reference -------------------------------------------------------------------------------------------------------
-def _resize64(planes, out_h, out_w):
-    """[..., h, w] -> [..., out_h, out_w] float64: rows first, then columns (torch's order); an axis of the output's size is a copy."""
-    x = planes.astype(np.float64)
-    h, w = x.shape[-2:]
-    if w != out_w:
-        ix, wx = ho.bicubic_taps(w, out_w, np.float32)
-        x = sum(x[..., :, ix[:, a]] * wx[:, a].astype(np.float64) for a in range(4))
-    if h != out_h:
-        iy, wy = ho.bicubic_taps(h, out_h, np.float32)
-        x = sum(x[..., iy[:, a], :] * wy[:, a].astype(np.float64)[:, None] for a in range(4))
-    return x
-
-
-def _global64(key_planes, out_h, out_w):
-    """mean over keys of clamp(resize(plane), 0); ``key_planes``: list of [77, h, w]."""
-    return sum(np.maximum(_resize64(p, out_h, out_w), 0) for p in key_planes) / len(key_planes)
+# ---- the float64 reference: tests/_rect_domain.py ----------------------------------------------------------------------------------
+_resize64, _global64 = rd.resize64, rd.global64
 
 
 def _assert_rows(got, want, what):
@@ -300,6 +291,85 @@ def test_taps_on_rectangular_layers(hw_shape, d, mode):
                 assert err <= tol, f'{route}: {err} > {tol}'
         if not takes:                                              # the fallback IS the stand-alone tap: the same bits
             assert torch.equal(bufs[3], bufs[0])
+    finally:
+        lib.daam_ctx_destroy(ctx)
+
+
+_tap_inputs, _tap_refs = {}, {}
+
+
+def _tap_reference(hw, heads, d, np_dt, n_steps, acc_np):
+    """``_attend_domain.build`` rows and ``_tap_domain.reference`` of them, computed once per shape, pipeline and sum dtype."""
+    key = (hw, heads, d, str(np_dt), n_steps)
+    if key not in _tap_inputs:
+        _tap_inputs[key] = ad.build(hw, heads, d, np_dt, n_steps)
+    steps, names = _tap_inputs[key]
+    if key + (str(acc_np),) not in _tap_refs:
+        _tap_refs[key + (str(acc_np),)] = td.reference(steps, heads, d ** -0.5, np_dt, acc_np)
+    return steps, names, _tap_refs[key + (str(acc_np),)]
+
+
+@pytest.mark.parametrize('mode,sums', [('f16', 'f16'), ('f16', 'f32'), ('bf16', 'bf16'), ('bf16', 'f32'), ('f32', 'f32')])
+@pytest.mark.parametrize('d', [64, 40])
+@pytest.mark.parametrize('hw_shape', [(6, 10), (26, 38), (8, 24)])
+def test_taps_on_rectangular_layers_per_probability(hw_shape, d, mode, sums, monkeypatch):
+    """The routes of ``test_taps_on_rectangular_layers`` on the rows of ``tests/_attend_domain.py``, every sum element against the float64
+    softmax at ``tests/_tap_domain.py``'s own bound (as ``tests/test_gpu_tap_domain.py::_run_route`` judges the square layers): 60 pixels are
+    less than one 64-pixel wave tile, 988 end in a ragged one, 192 take the MFMA kernels.  ``sums``: the dtype of the running sums; f32
+    sums under a 16-bit pipeline also carry the rounding-bias rule wherever the layer has the 4096 elements it asks for."""
+    _configure(monkeypatch, {})                                    # no kernel switch left over from another test
+    nat, lib = _nat()
+    h, w = hw_shape
+    hw = h * w
+    heads = 2 if d == 64 else 8
+    batch, steps_n = 2, 3
+    c = heads * d
+    np_dt, acc_np = NP_DT[mode], NP_DT[sums]
+    steps, names, ref = _tap_reference(hw, heads, d, np_dt, steps_n, acc_np)
+    tq = [_dev(q, np_dt) for q, _ in steps]
+    tk = [_dev(k, np_dt) for _, k in steps]
+    tv = [_dev(v, np_dt) for v in ad.values('plain', heads, d, np_dt, steps_n)]
+    tp = [_dev(ho.attention_probs(_to_bh(q, heads), _to_bh(k, heads), d ** -0.5, np_dt), np_dt) for q, k in steps]
+    inputs = tq + tk + tv + tp
+    before = [t.clone() for t in inputs]
+    generic = hw % 8 != 0 or mode == 'f32'
+    want_name = ('tap_generic_kernel',) * 2 if generic else ('tap_d64_kernel', 'tap_slab_kernel' if (mode, d) == ('f16', 40) else 'tap_d64_kernel')
+    ctx = nat.c_void_p()
+    nat.check(lib.daam_ctx_create_rect(4, TOKENS, 2 * h, 2 * w, CODE[sums], nat.byref(ctx)))
+    bufs = [torch.zeros(heads, TOKENS, h, w, dtype=TORCH_DT[sums], device=DEV) for _ in range(4)]
+    try:
+        for layer in range(4):
+            nat.check(lib.daam_layer_configure_rect(ctx, layer, heads, h, w, 2, bufs[layer].data_ptr()))
+        desc = nat.QKDesc(in_dtype=CODE[mode], batch=batch, heads=heads, hw=hw, tokens=TOKENS, head_dim=d, round_logits=1, scale=d ** -0.5,
+                          q_stride_b=hw * c, q_stride_h=d, q_stride_p=c, k_stride_b=TOKENS * c, k_stride_h=d, k_stride_t=c)
+        s = _stream()
+        for q, k in zip(tq, tk):
+            nat.check(lib.daam_tap_qk(ctx, 0, q.data_ptr(), k.data_ptr(), nat.byref(desc), s))
+        assert _kernels(nat, lib, ctx, 0) == want_name[0], _kernels(nat, lib, ctx, 0)
+        for q, k in zip(tq, tk):
+            nat.check(lib.daam_tap_qk_enqueue(ctx, 1, q.data_ptr(), k.data_ptr(), nat.byref(desc)))
+        nat.check(lib.daam_tap_flush(ctx, s))
+        assert _kernels(nat, lib, ctx, 0) == want_name[1], _kernels(nat, lib, ctx, 0)
+        for p in tp:
+            nat.check(lib.daam_tap_probs(ctx, 2, p.data_ptr(), CODE[mode], batch * heads, hw, TOKENS, s))
+        out = torch.empty_like(tq[0])
+        adesc = nat.AttendDesc(qk=desc, v_stride_b=TOKENS * c, v_stride_h=d, v_stride_t=c, o_stride_b=hw * c, o_stride_h=d, o_stride_p=c)
+        takes = bool(lib.daam_attend_supported(nat.byref(adesc), tq[0].data_ptr(), tk[0].data_ptr(), tv[0].data_ptr(), out.data_ptr()))
+        assert takes == (not generic), (hw, mode, takes)
+        for q, k, v in zip(tq, tk, tv):
+            if takes:
+                nat.check(lib.daam_attend(ctx, 3, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), nat.byref(adesc), 1, s))
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(inputs, before)), 'an input was written to'
+        for layer, route in enumerate(('tap_qk', 'enqueue + flush', 'tap_probs', 'attend')[:4 if takes else 3]):
+            what = f'{hw_shape} d={d} {mode} pipeline, {sums} sums, {route}'
+            got = bufs[layer].float().cpu().numpy().astype(np.float64).reshape(heads, TOKENS, hw)
+            td.assert_inside_bound(got, ref, names, what)
+            if mode != 'f32' and sums == 'f32':
+                if td.bias(got, ref, names, np_dt)[1] >= td.BIAS_MIN_COUNT:      # a count of the inputs: 60 pixels x 2 heads have too few
+                    td.assert_unbiased(got, ref, names, np_dt, what)
+                else:
+                    assert (hw, heads) == (60, 2), (hw, heads)
     finally:
         lib.daam_ctx_destroy(ctx)
 
