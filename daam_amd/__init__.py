@@ -10,6 +10,7 @@ from .experiment import *    # noqa: F401,F403
 from .evaluate import compute_iou, compute_ioa, load_mask, MeanEvaluator, UnsupervisedEvaluator  # noqa: F401
 from .evaluate import mask_overlap_matrix, MaskOverlaps, SweepEvaluator  # noqa: F401
 from .evaluate import mask_boxes, LocalizationEvaluator  # noqa: F401
+from .evaluate import mask_components, MaskComponents  # noqa: F401
 from .engine import region_scores, region_dots  # noqa: F401
 
 __version__ = '0.1.0'

@@ -249,5 +249,36 @@ def check_locate(rc: int) -> None:
         raise DaamError(rc, msg.decode() if msg else '')
 
 
+# ---- libdaam_components.so (C ABI: include/daam_components.h) ---------------------------------------------------------------------
+COMPONENTS_LIB_NAME = 'libdaam_components.so'
+COMPONENTS_LIB_PATH = os.environ.get('DAAM_COMPONENTS_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), COMPONENTS_LIB_NAME)
+COMPONENTS_ABI_VERSION = 1
+COMPONENTS_EXPORTS = ('daam_mask_components', 'daam_mask_components_workspace', 'daam_components_abi_version', 'daam_components_last_error')
+
+_components = None
+
+
+def load_components() -> ctypes.CDLL:
+    """The connected-components library (labels, areas, largest-blob boxes); like ``load`` it has no fallback."""
+    global _components
+    if _components is not None:
+        return _components
+    lib = _open(COMPONENTS_LIB_PATH, 'mask_components', COMPONENTS_EXPORTS, 'daam_components_abi_version', COMPONENTS_ABI_VERSION)
+    lib.daam_mask_components.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.daam_mask_components.restype = c_int
+    lib.daam_mask_components_workspace.argtypes = [c_int, c_int, c_int, c_int]
+    lib.daam_mask_components_workspace.restype = c_size_t
+    lib.daam_components_last_error.restype = c_char_p
+    _components = lib
+    return lib
+
+
+def check_components(rc: int) -> None:
+    if rc != 0:
+        msg = load_components().daam_components_last_error()
+        raise DaamError(rc, msg.decode() if msg else '')
+
+
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -29,6 +29,12 @@ EVAL_LIB = os.path.join(HERE, 'libdaam_eval.so')
 LOCATE_SOURCES = ['daam_locate.hip']
 LOCATE_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_locate.h')]
 LOCATE_LIB = os.path.join(HERE, 'libdaam_locate.so')
+# libdaam_components.so (include/daam_components.h): connected components of byte masks.  It reads daam_epilogue.h for the bit-set
+# helpers alone and stays out of every list above.
+COMPONENTS_SOURCES = ['daam_components.hip']
+COMPONENTS_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'),
+                      os.path.join('..', '..', 'include', 'daam_components.h')]
+COMPONENTS_LIB = os.path.join(HERE, 'libdaam_components.so')
 
 
 def csrc_sha() -> str:
@@ -164,6 +170,25 @@ def build_locate(force: bool = False, verbose: bool = True) -> str:
     return LOCATE_LIB
 
 
+def components_stale() -> bool:
+    if not os.path.exists(COMPONENTS_LIB):
+        return True
+    t = os.path.getmtime(COMPONENTS_LIB)
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in COMPONENTS_SOURCES + COMPONENTS_HEADERS)
+
+
+def build_components(force: bool = False, verbose: bool = True) -> str:
+    """``libdaam_components.so``: one hipcc command, when it is missing or older than what it is made of."""
+    if not force and not components_stale():
+        return COMPONENTS_LIB
+    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
+           *[os.path.join(HERE, 'csrc', f) for f in COMPONENTS_SOURCES], '-o', COMPONENTS_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return COMPONENTS_LIB
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -219,6 +244,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     build_analysis(force, verbose)
     build_eval(force, verbose)
     build_locate(force, verbose)
+    build_components(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

@@ -1528,6 +1528,61 @@ def localize(word_maps: torch.Tensor, out_h: int, out_w: int, thresholds=(), tru
     return out + (torch.cat(truth_boxes), torch.cat(hit_rows) != 0)
 
 
+MAX_COMPONENT_MASKS, MAX_COMPONENT_ROWS = 32, 65536      # limits of one daam_mask_components call (include/daam_components.h)
+_KEEP_CODES = {None: 0, 0: 0, 'area': 1, 1: 1, 'largest': 2, 2: 2}
+
+
+def _launch_components(masks: torch.Tensor, connectivity: int, min_area: int, keep: int, max_comp: int, labels: bool):
+    """One ``daam_mask_components`` call: ``masks`` [M <= 32, H, W] uint8, contiguous -> ``(labels int32 [M, H, W] or None, counts
+    int32 [M, 2], comps int32 [M, max_comp, 6], largest int32 [M, 6], kept uint8 [M, H, W] or None)``."""
+    lib = nat.load_components()
+    n, h, w = masks.shape
+    dev = masks.device
+    label_map = torch.empty(n, h, w, dtype=torch.int32, device=dev) if labels else None
+    counts = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    comps = torch.empty(n, max_comp, 6, dtype=torch.int32, device=dev)
+    largest = torch.empty(n, 6, dtype=torch.int32, device=dev)
+    kept = torch.empty(n, h, w, dtype=torch.uint8, device=dev) if keep else None
+    need = lib.daam_mask_components_workspace(n, h, w, max_comp)
+    if not need:
+        raise ValueError(f'mask_components of {n} masks at {h} x {w} with {max_comp} rows: out of range')
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        nat.check_components(lib.daam_mask_components(
+            masks.data_ptr(), n, h, w, connectivity, min_area, keep, max_comp, label_map.data_ptr() if labels else None, counts.data_ptr(),
+            comps.data_ptr() if max_comp else None, largest.data_ptr(), kept.data_ptr() if keep else None, ws.data_ptr(), need,
+            torch.cuda.current_stream(dev).cuda_stream))
+    return label_map, counts, comps, largest, kept
+
+
+def mask_components(masks: torch.Tensor, connectivity: int = 8, min_area: int = 0, keep=None, max_components: int = 256,
+                    labels: bool = True):
+    """``daam_mask_components``: the connected components (``connectivity`` 4 or 8) of every mask of ``masks`` [M, H, W] (or [H, W];
+    uint8 / bool as they are -- a byte != 0 is set --, other dtypes through ``!= 0``; CPU masks are moved to the device).  Returns
+    device tensors ``(labels int32 [M, H, W] or None -- the rank of the pixel's component when a mask's components are sorted by their
+    lowest row-major index, ``scipy.ndimage.label`` minus one; -1 on background --, counts int32 [M, 2] -- components; components of at
+    least ``min_area`` pixels --, components int32 [M, max_components, 6] -- per rank the root, the area and x0 y0 x1 y1 inclusive;
+    (-1, 0, W, H, -1, -1) past the last --, largest int32 [M, 6] -- the same columns for the component of the greatest area, the
+    lowest root on a tie --, kept uint8 [M, H, W] or None)``.  ``keep``: ``None`` nothing, ``'area'`` the components of at least
+    ``min_area`` pixels, ``'largest'`` the largest alone.  A mask with more components than ``max_components`` has its list cut
+    and everything else exact.  More than 32 masks run in blocks that are concatenated on the device."""
+    from .evaluate import _as_masks
+    masks = _as_masks(masks, 'masks')
+    if connectivity not in (4, 8):
+        raise ValueError(f'connectivity {connectivity!r}: 4 or 8')
+    if keep not in _KEEP_CODES:
+        raise ValueError(f"keep {keep!r}: None, 'area' or 'largest'")
+    min_area, max_components = int(min_area), int(max_components)
+    if min_area < 0 or not 0 <= max_components <= MAX_COMPONENT_ROWS:
+        raise ValueError(f'min_area {min_area} must be >= 0 and max_components {max_components} in 0..{MAX_COMPONENT_ROWS}')
+    step = MAX_COMPONENT_MASKS
+    parts = [_launch_components(masks[i:i + step], int(connectivity), min_area, _KEEP_CODES[keep], max_components, bool(labels))
+             for i in range(0, masks.shape[0], step)]
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
+
+
 def _check_maps(maps: torch.Tensor) -> None:
     if maps.device.type != 'cuda':
         raise RuntimeError('daam_amd: heat maps must live on the HIP device (no CPU fallback)')

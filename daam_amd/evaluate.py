@@ -25,7 +25,7 @@ from . import _native as nat
 
 __all__ = ['compute_iou', 'compute_ioa', 'mask_overlap', 'compute_iou_batch', 'compute_ioa_batch', 'load_mask',
            'MeanEvaluator', 'UnsupervisedEvaluator', 'mask_overlap_matrix', 'MaskOverlaps', 'SweepEvaluator', 'mask_boxes',
-           'LocalizationEvaluator']
+           'LocalizationEvaluator', 'mask_components', 'MaskComponents']
 
 MAX_MATRIX_MASKS = 32                              # masks per stack of one daam_mask_overlap_matrix call (include/daam_hip.h)
 
@@ -185,6 +185,50 @@ def mask_boxes(masks: torch.Tensor) -> torch.Tensor:
     step = engine.MAX_LOCATE_TRUTH
     parts = [engine._launch_localize(None, masks.shape[1], masks.shape[2], True, [], masks[i:i + step])[3] for i in range(0, masks.shape[0], step)]
     return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+@dataclass
+class MaskComponents:
+    """The connected components of a stack of masks (``mask_components``): device tensors until ``cpu()`` is asked for.  A component's
+    rank is its position when the components of one mask are sorted by their lowest row-major index (``scipy.ndimage.label`` minus
+    one)."""
+    labels: Optional[torch.Tensor]              # int32 [M, H, W]: the rank of the pixel's component, -1 on background; None if not asked for
+    counts: torch.Tensor                        # int32 [M, 2]: components; components of at least min_area pixels
+    components: torch.Tensor                    # int32 [M, K, 6]: per rank root, area, x0 y0 x1 y1 (inclusive); (-1, 0, W, H, -1, -1) past the last
+    largest: torch.Tensor                       # int32 [M, 6]: the same columns for the largest component (the lowest root on a tie)
+    kept: Optional[torch.Tensor]                # uint8 [M, H, W]: the pixels of the components that were kept; None if none were asked for
+
+    def n(self, m: int = 0) -> int:
+        """The number of components of mask ``m`` (exact, also beyond the rows of ``components``)."""
+        return int(self.counts[m, 0])
+
+    def _listed(self, m: int) -> torch.Tensor:
+        return self.components[m, :min(self.n(m), self.components.shape[1])]
+
+    def areas(self, m: int = 0) -> torch.Tensor:
+        """int32 [k]: the areas of the listed components of mask ``m``, by rank."""
+        return self._listed(m)[:, 1]
+
+    def boxes(self, m: int = 0) -> torch.Tensor:
+        """int32 [k, 4]: ``x0 y0 x1 y1`` (inclusive) of the listed components of mask ``m``, by rank."""
+        return self._listed(m)[:, 2:6]
+
+    def largest_boxes(self) -> torch.Tensor:
+        """int32 [M, 4]: the box of every mask's largest component; ``(W, H, -1, -1)`` for an empty mask, as ``mask_boxes`` gives."""
+        return self.largest[:, 2:6]
+
+    def cpu(self) -> 'MaskComponents':
+        return MaskComponents(None if self.labels is None else self.labels.cpu(), self.counts.cpu(), self.components.cpu(),
+                              self.largest.cpu(), None if self.kept is None else self.kept.cpu())
+
+
+def mask_components(masks: torch.Tensor, connectivity: int = 8, min_area: int = 0, keep=None, max_components: int = 256,
+                    labels: bool = True) -> MaskComponents:
+    """``engine.mask_components`` as a ``MaskComponents``: which pixels of every mask of ``masks`` [M, H, W] (or [H, W]) belong
+    together -- labels, counts, the list of components, the largest one and, with ``keep`` (``'area'``: at least ``min_area`` pixels,
+    ``'largest'``), the cleaned masks -- from one ``daam_mask_components`` call per 32 masks, everything left on the device."""
+    from . import engine
+    return MaskComponents(*engine.mask_components(masks, connectivity, min_area, keep, max_components, labels))
 
 
 def load_mask(path: str) -> torch.Tensor:

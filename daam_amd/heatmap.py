@@ -142,6 +142,23 @@ class Segmentation:
         from .evaluate import mask_overlap_matrix
         return float(mask_overlap_matrix(self.mask(word_a), self.mask(word_b)).ioa()[0, 0])
 
+    def components(self, connectivity: int = 8, min_area: int = 0):
+        """``evaluate.MaskComponents`` of the word masks: per word the labelled blobs, their number, areas and boxes and the largest
+        one (``evaluate.mask_components``)."""
+        from .evaluate import mask_components
+        return mask_components(self.masks, connectivity=connectivity, min_area=min_area)
+
+    def clean(self, min_area: int = 0, largest: bool = False, connectivity: int = 8) -> 'Segmentation':
+        """A ``Segmentation`` of the same words and word heat maps whose masks keep only the blobs of at least ``min_area`` pixels
+        or, with ``largest``, every word's largest blob alone (and nothing when that has fewer than ``min_area`` pixels); it has no
+        label map.  ``iou`` / ``ioa`` / ``attribute`` run on the cleaned masks as on any others."""
+        from . import engine
+        _, _, _, big, kept = engine.mask_components(self.masks, connectivity, 0 if largest else min_area, 'largest' if largest else 'area',
+                                                    max_components=0, labels=False)
+        if largest and min_area > 0:
+            kept = kept * (big[:, 1] >= int(min_area)).to(torch.uint8)[:, None, None]
+        return Segmentation(list(self.words), list(self.word_heat_maps), kept, None)
+
     def cpu(self) -> 'Segmentation':
         maps = [WordHeatMap(m.heatmap.cpu(), m.word, m.word_idx) for m in self.word_heat_maps]
         return Segmentation(list(self.words), maps, self.masks.cpu(), None if self.labels is None else self.labels.cpu())
@@ -460,19 +477,35 @@ class GlobalHeatMap:
         return ThresholdSweep([w for w, _ in pairs], thr, inter, pred, area)
 
     def localize(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]], image, thresholds=(0.4,),
-                 truth: Union[None, torch.Tensor, Segmentation] = None, absolute: bool = False) -> Localization:
+                 truth: Union[None, torch.Tensor, Segmentation] = None, absolute: bool = False, component: Optional[str] = None,
+                 connectivity: int = 8) -> Localization:
         """The bounding box of ``segment(words, image, threshold=t).masks`` for every ``t`` of ``thresholds``, the peak of every
         word's expanded map and, with ``truth`` (a mask [H, W], a stack [G, H, W] or a ``Segmentation``), the truth masks' boxes and
         the pointing hits -- one pass at image resolution (``engine.localize``), no mask is written.  Words are resolved as in
-        ``segment`` and the output is sized as in ``expand_as``."""
+        ``segment`` and the output is sized as in ``expand_as``.
+
+        ``component='largest'``: ``boxes[j][t]`` is the box of the LARGEST connected component (``connectivity`` 4 or 8) of that
+        mask, as CAM-style CorLoc is defined, so a stray speckle no longer stretches the box.  The row and column maxima of the
+        one-pass route cannot give that box (they say which rows and columns hold a mask pixel, not which pixels touch), so per
+        threshold the masks are written (``engine.word_masks``) and labelled (``engine.mask_components``); peaks, peak values,
+        truth boxes and hits still come from one ``engine.localize`` call."""
         pairs = [(w, None) if isinstance(w, str) else (w[0], w[1]) for w in words]
         if not pairs:
             raise ValueError('localize needs at least one word')
+        if component not in (None, 'largest'):
+            raise ValueError(f"component {component!r}: None or 'largest'")
         resolved = [compute_token_merge_indices(self.tokenizer, self.prompt, w, i) for w, i in pairs]
         maps = self.heat_maps
         size = (image.size[0], image.size[1]) if maps.shape[-2] == maps.shape[-1] else (image.size[1], image.size[0])
         masks = truth.masks if isinstance(truth, Segmentation) else truth
         planes = _engine.word_maps(maps, [idxs for idxs, _ in resolved])
+        if component == 'largest':
+            thr = torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1)
+            _, peaks, values, truth_boxes, hits = _engine.localize(planes, int(size[0]), int(size[1]), (), masks, absolute=absolute)
+            cols = [_engine.mask_components(self.segment(pairs, image, threshold=float(t), absolute=absolute, labels=False).masks,
+                                            connectivity, max_components=0, labels=False)[3][:, 2:6] for t in thr]
+            boxes = torch.stack(cols, 1) if cols else torch.zeros(len(pairs), 0, 4, dtype=torch.int32, device=peaks.device)
+            return Localization([w for w, _ in pairs], thr.to(peaks.device), (int(size[0]), int(size[1])), boxes, peaks, values, truth_boxes, hits)
         boxes, peaks, values, truth_boxes, hits = _engine.localize(planes, int(size[0]), int(size[1]), thresholds, masks, absolute=absolute)
         thr = torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1).to(boxes.device)
         return Localization([w for w, _ in pairs], thr, (int(size[0]), int(size[1])), boxes, peaks, values, truth_boxes, hits)
