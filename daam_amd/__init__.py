@@ -11,6 +11,7 @@ from .evaluate import compute_iou, compute_ioa, load_mask, MeanEvaluator, Unsupe
 from .evaluate import mask_overlap_matrix, MaskOverlaps, SweepEvaluator  # noqa: F401
 from .evaluate import mask_boxes, LocalizationEvaluator  # noqa: F401
 from .evaluate import mask_components, MaskComponents  # noqa: F401
+from .evaluate import image_affinity, ImageAffinity  # noqa: F401
 from .engine import region_scores, region_dots  # noqa: F401
 
 __version__ = '0.1.0'

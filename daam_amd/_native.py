@@ -280,5 +280,41 @@ def check_components(rc: int) -> None:
         raise DaamError(rc, msg.decode() if msg else '')
 
 
+# ---- libdaam_refine.so (C ABI: include/daam_refine.h) ------------------------------------------------------------------------------
+REFINE_LIB_NAME = 'libdaam_refine.so'
+REFINE_LIB_PATH = os.environ.get('DAAM_REFINE_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), REFINE_LIB_NAME)
+REFINE_ABI_VERSION = 1
+REFINE_EXPORTS = ('daam_refine_affinity', 'daam_refine_apply', 'daam_refine_weights_bytes', 'daam_refine_workspace',
+                  'daam_refine_abi_version', 'daam_refine_last_error')
+
+_refine = None
+
+
+def load_refine() -> ctypes.CDLL:
+    """The refinement library (local-affinity propagation of soft word maps along the image); like ``load`` it has no fallback."""
+    global _refine
+    if _refine is not None:
+        return _refine
+    lib = _open(REFINE_LIB_PATH, 'refine', REFINE_EXPORTS, 'daam_refine_abi_version', REFINE_ABI_VERSION)
+    lib.daam_refine_affinity.argtypes = [c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int, c_float, c_void_p, c_void_p]
+    lib.daam_refine_affinity.restype = c_int
+    lib.daam_refine_apply.argtypes = [c_void_p, POINTER(c_int32), c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.daam_refine_apply.restype = c_int
+    lib.daam_refine_weights_bytes.argtypes = [c_int, c_int, c_int]
+    lib.daam_refine_weights_bytes.restype = c_size_t
+    lib.daam_refine_workspace.argtypes = [c_int, c_int, c_int]
+    lib.daam_refine_workspace.restype = c_size_t
+    lib.daam_refine_last_error.restype = c_char_p
+    _refine = lib
+    return lib
+
+
+def check_refine(rc: int) -> None:
+    if rc != 0:
+        msg = load_refine().daam_refine_last_error()
+        raise DaamError(rc, msg.decode() if msg else '')
+
+
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -35,6 +35,11 @@ COMPONENTS_SOURCES = ['daam_components.hip']
 COMPONENTS_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'),
                       os.path.join('..', '..', 'include', 'daam_components.h')]
 COMPONENTS_LIB = os.path.join(HERE, 'libdaam_components.so')
+# libdaam_refine.so (include/daam_refine.h): image-guided refinement of soft word maps (local-affinity propagation).  It reads no
+# header of csrc/ and stays out of every list above.
+REFINE_SOURCES = ['daam_refine.hip']
+REFINE_HEADERS = [os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_refine.h')]
+REFINE_LIB = os.path.join(HERE, 'libdaam_refine.so')
 
 
 def csrc_sha() -> str:
@@ -189,6 +194,25 @@ def build_components(force: bool = False, verbose: bool = True) -> str:
     return COMPONENTS_LIB
 
 
+def refine_stale() -> bool:
+    if not os.path.exists(REFINE_LIB):
+        return True
+    t = os.path.getmtime(REFINE_LIB)
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in REFINE_SOURCES + REFINE_HEADERS)
+
+
+def build_refine(force: bool = False, verbose: bool = True) -> str:
+    """``libdaam_refine.so``: one hipcc command, when it is missing or older than what it is made of."""
+    if not force and not refine_stale():
+        return REFINE_LIB
+    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
+           *[os.path.join(HERE, 'csrc', f) for f in REFINE_SOURCES], '-o', REFINE_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return REFINE_LIB
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -245,6 +269,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     build_eval(force, verbose)
     build_locate(force, verbose)
     build_components(force, verbose)
+    build_refine(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

@@ -1583,6 +1583,113 @@ def mask_components(masks: torch.Tensor, connectivity: int = 8, min_area: int = 
     return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
 
 
+MAX_REFINE_MAPS, MAX_REFINE_DILATIONS, MAX_REFINE_DILATION, MAX_REFINE_ITERATIONS = 32, 6, 64, 64   # include/daam_refine.h
+REFINE_DILATIONS = (1, 2, 4, 8, 12, 24)
+
+
+def _refine_dilations(dilations) -> Tuple[int, ...]:
+    dil = tuple(int(d) for d in dilations)
+    if not 1 <= len(dil) <= MAX_REFINE_DILATIONS or any(not 1 <= d <= MAX_REFINE_DILATION for d in dil) or \
+            any(b <= a for a, b in zip(dil, dil[1:])):
+        raise ValueError(f'dilations {dil!r}: 1..{MAX_REFINE_DILATIONS} strictly increasing integers within 1..{MAX_REFINE_DILATION}')
+    return dil
+
+
+def _image_bytes(image) -> torch.Tensor:
+    """``image`` as uint8 [H, W, C], C 1 or 3, contiguous, on the device: a PIL image (modes other than L and RGB are converted to
+    RGB) or a uint8 [H, W], [H, W, 1] or [H, W, 3] array or tensor (CPU ones are moved to the device)."""
+    from .evaluate import _to_hip
+    if hasattr(image, 'convert') and hasattr(image, 'mode'):
+        image = torch.from_numpy(np.array(image if image.mode in ('L', 'RGB') else image.convert('RGB')))
+    elif not isinstance(image, torch.Tensor):
+        image = torch.from_numpy(np.ascontiguousarray(image))
+    if image.dtype != torch.uint8:
+        raise RuntimeError(f'daam_amd: refinement reads a uint8 image, got {image.dtype}')
+    if image.dim() == 2:
+        image = image.unsqueeze(-1)
+    if image.dim() != 3 or image.shape[2] not in (1, 3) or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError(f'image must be [H, W], [H, W, 1] or [H, W, 3], got {tuple(image.shape)}')
+    return _to_hip(image, 'image').contiguous()
+
+
+def refine_affinity(image, dilations=REFINE_DILATIONS, scale: float = 0.1) -> torch.Tensor:
+    """``daam_refine_affinity``: the propagation weights of ``image`` (a PIL image, or a uint8 [H, W], [H, W, 1] or [H, W, 3] array or
+    tensor; RGBA and other PIL modes are converted to RGB) as f32 [8 * len(dilations), H, W] on the device: per pixel the softmax over
+    its 8 neighbours at every dilation of minus the mean absolute colour difference over ``scale`` times the local deviation
+    (include/daam_refine.h).  They depend on the image alone: one call serves every word, threshold and ``refine_maps`` call."""
+    lib = nat.load_refine()
+    dil = _refine_dilations(dilations)
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError(f'scale {scale!r}: finite and > 0')
+    pixels = _image_bytes(image)
+    h, w, c = pixels.shape
+    if not lib.daam_refine_weights_bytes(h, w, len(dil)):
+        raise ValueError(f'an image of {h} x {w} with {len(dil)} dilations: out of range (fewer than 2^31 weights)')
+    weights = torch.empty(8 * len(dil), h, w, dtype=torch.float32, device=pixels.device)
+    with torch.cuda.device(pixels.device):
+        nat.check_refine(lib.daam_refine_affinity(pixels.data_ptr(), h, w, c, (ctypes.c_int32 * len(dil))(*dil), len(dil), scale,
+                                                  weights.data_ptr(), torch.cuda.current_stream(pixels.device).cuda_stream))
+    return weights
+
+
+def _launch_refine(weights: torch.Tensor, dil: Tuple[int, ...], maps: torch.Tensor, iterations: int, threshold: float, masks: bool,
+                   labels: bool):
+    """One ``daam_refine_apply`` call: ``maps`` [N <= 32, H, W] fp32, contiguous -> ``(refined f32 [N, H, W], masks uint8 [N, H, W] or
+    None, labels uint8 [H, W] or None)``."""
+    lib = nat.load_refine()
+    n, h, w = maps.shape
+    dev = maps.device
+    refined = torch.empty(n, h, w, dtype=torch.float32, device=dev)
+    mask_stack = torch.empty(n, h, w, dtype=torch.uint8, device=dev) if masks else None
+    label_map = torch.empty(h, w, dtype=torch.uint8, device=dev) if labels else None
+    need = lib.daam_refine_workspace(n, h, w)
+    if not need:
+        raise ValueError(f'refine_maps of {n} maps at {h} x {w}: out of range')
+    ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        nat.check_refine(lib.daam_refine_apply(
+            weights.data_ptr(), (ctypes.c_int32 * len(dil))(*dil), len(dil), maps.data_ptr(), n, h, w, iterations, threshold,
+            refined.data_ptr(), mask_stack.data_ptr() if masks else None, label_map.data_ptr() if labels else None, ws.data_ptr(), need,
+            torch.cuda.current_stream(dev).cuda_stream))
+    return refined, mask_stack, label_map
+
+
+def refine_maps(weights: torch.Tensor, dilations, maps: torch.Tensor, iterations: int = 10, threshold: float = 0.4, masks: bool = True,
+                labels: bool = True):
+    """``daam_refine_apply``: ``iterations`` rounds of ``m(p) <- sum_k weights[k](p) * m(q_k(p))`` on every map of ``maps``
+    [N, H, W] fp32 on the device, with ``weights`` [8 * len(dilations), H, W] from ``refine_affinity`` of the same ``dilations``.
+    Returns device tensors ``(refined f32 [N, H, W], masks uint8 [N, H, W] = refined > threshold or None, labels uint8 [H, W] -- the
+    word with the largest refined value, the lowest index on a tie, 255 where none exceeds the threshold -- or None)``; masks and
+    labels come out of the last iteration's launch.  More than 32 maps run in blocks that are concatenated on the device; a label
+    map orders at most 32."""
+    _check_maps(maps)
+    dil = _refine_dilations(dilations)
+    if weights.device != maps.device:
+        raise RuntimeError('daam_amd: weights and maps are on different devices')
+    if weights.dtype != torch.float32 or not weights.is_contiguous() or weights.dim() != 3:
+        raise RuntimeError('daam_amd: refinement weights must be a contiguous fp32 [8 * dilations, H, W] tensor')
+    if weights.shape[0] != 8 * len(dil):
+        raise ValueError(f'{weights.shape[0]} weight planes for {len(dil)} dilations: {8 * len(dil)} are needed')
+    if tuple(weights.shape[1:]) != tuple(maps.shape[1:]):
+        raise ValueError(f'the weights are of an image of {weights.shape[1]} x {weights.shape[2]}, the maps are {maps.shape[1]} x {maps.shape[2]}')
+    iterations, threshold = int(iterations), float(threshold)
+    if not 0 <= iterations <= MAX_REFINE_ITERATIONS:
+        raise ValueError(f'iterations {iterations}: 0..{MAX_REFINE_ITERATIONS}')
+    if not math.isfinite(threshold):
+        raise ValueError(f'threshold {threshold!r} is not finite')
+    if maps.shape[0] < 1:
+        raise ValueError('refine_maps needs at least one map')
+    if labels and maps.shape[0] > MAX_REFINE_MAPS:
+        raise ValueError(f'a label map orders at most {MAX_REFINE_MAPS} maps, got {maps.shape[0]}; pass labels=False')
+    step = MAX_REFINE_MAPS
+    parts = [_launch_refine(weights, dil, maps[i:i + step], iterations, threshold, bool(masks), bool(labels))
+             for i in range(0, maps.shape[0], step)]
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
+
+
 def _check_maps(maps: torch.Tensor) -> None:
     if maps.device.type != 'cuda':
         raise RuntimeError('daam_amd: heat maps must live on the HIP device (no CPU fallback)')

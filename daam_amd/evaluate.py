@@ -25,7 +25,7 @@ from . import _native as nat
 
 __all__ = ['compute_iou', 'compute_ioa', 'mask_overlap', 'compute_iou_batch', 'compute_ioa_batch', 'load_mask',
            'MeanEvaluator', 'UnsupervisedEvaluator', 'mask_overlap_matrix', 'MaskOverlaps', 'SweepEvaluator', 'mask_boxes',
-           'LocalizationEvaluator', 'mask_components', 'MaskComponents']
+           'LocalizationEvaluator', 'mask_components', 'MaskComponents', 'image_affinity', 'ImageAffinity']
 
 MAX_MATRIX_MASKS = 32                              # masks per stack of one daam_mask_overlap_matrix call (include/daam_hip.h)
 
@@ -229,6 +229,32 @@ def mask_components(masks: torch.Tensor, connectivity: int = 8, min_area: int = 
     ``'largest'``), the cleaned masks -- from one ``daam_mask_components`` call per 32 masks, everything left on the device."""
     from . import engine
     return MaskComponents(*engine.mask_components(masks, connectivity, min_area, keep, max_components, labels))
+
+
+@dataclass
+class ImageAffinity:
+    """The propagation weights of one image (``image_affinity``): what ``GlobalHeatMap.refine`` / ``Segmentation.refine`` spread the
+    soft maps along.  They depend on the image, the dilations and the scale alone, so one instance serves every word, threshold and
+    call on that image (``refine(..., affinity=)``)."""
+    weights: torch.Tensor                       # f32 [8 * len(dilations), H, W] on the device (engine.refine_affinity)
+    dilations: Tuple[int, ...]
+    scale: float
+    size: Tuple[int, int]                       # (H, W) of the image
+
+    def refine(self, maps: torch.Tensor, iterations: int = 10, threshold: float = 0.4, masks: bool = True, labels: bool = True):
+        """``engine.refine_maps`` of ``maps`` f32 [N, H, W] with these weights: ``(refined, masks or None, labels or None)``."""
+        from . import engine
+        if tuple(maps.shape[-2:]) != tuple(self.size):
+            raise ValueError(f'the affinity is of an image of {self.size[0]} x {self.size[1]}, the maps are {maps.shape[-2]} x {maps.shape[-1]}')
+        return engine.refine_maps(self.weights, self.dilations, maps, iterations, threshold, masks, labels)
+
+
+def image_affinity(image, dilations=(1, 2, 4, 8, 12, 24), scale: float = 0.1) -> ImageAffinity:
+    """``engine.refine_affinity`` as an ``ImageAffinity``: ``image`` is a PIL image or a uint8 [H, W], [H, W, 1] or [H, W, 3] array or
+    tensor."""
+    from . import engine
+    weights = engine.refine_affinity(image, dilations, scale)
+    return ImageAffinity(weights, tuple(int(d) for d in dilations), float(scale), (int(weights.shape[1]), int(weights.shape[2])))
 
 
 def load_mask(path: str) -> torch.Tensor:

@@ -115,6 +115,7 @@ class Segmentation:
     word_heat_maps: List[WordHeatMap]
     masks: torch.Tensor                         # uint8 [len(words), height, width]: 1 where the word's expanded map > threshold
     labels: Optional[torch.Tensor]              # uint8 [height, width]: index into ``words`` or BACKGROUND; None if not computed
+    refined: Optional[torch.Tensor] = None      # f32 [len(words), height, width]: the refined soft maps behind ``masks`` (``refine``); else None
 
     def mask(self, word: str) -> torch.Tensor:
         """The uint8 [height, width] mask of ``word`` (its first entry, when the word was asked for twice)."""
@@ -159,9 +160,41 @@ class Segmentation:
             kept = kept * (big[:, 1] >= int(min_area)).to(torch.uint8)[:, None, None]
         return Segmentation(list(self.words), list(self.word_heat_maps), kept, None)
 
+    def refine(self, image, threshold: float = 0.4, iterations: int = 10, dilations=_engine.REFINE_DILATIONS, scale: float = 0.1,
+               absolute: bool = False, labels: bool = True, affinity=None) -> 'Segmentation':
+        """``GlobalHeatMap.refine`` of the same words, starting from ``word_heat_maps``: the expanded soft maps are propagated along
+        ``image``'s local colour affinities and thresholded again."""
+        return _refine_words(list(self.words), list(self.word_heat_maps), image, threshold, iterations, dilations, scale, absolute, labels,
+                             affinity)
+
     def cpu(self) -> 'Segmentation':
         maps = [WordHeatMap(m.heatmap.cpu(), m.word, m.word_idx) for m in self.word_heat_maps]
-        return Segmentation(list(self.words), maps, self.masks.cpu(), None if self.labels is None else self.labels.cpu())
+        return Segmentation(list(self.words), maps, self.masks.cpu(), None if self.labels is None else self.labels.cpu(),
+                            None if self.refined is None else self.refined.cpu())
+
+
+def _refine_words(words: List[str], heat: List[WordHeatMap], image, threshold: float, iterations: int, dilations, scale: float,
+                  absolute: bool, labels: bool, affinity) -> Segmentation:
+    """What ``GlobalHeatMap.refine`` and ``Segmentation.refine`` share: every word map expanded as ``expand_as(image, absolute=)``
+    expands it (on the device), ``iterations`` rounds of ``engine.refine_maps`` along the image's affinities, masks and labels."""
+    from .evaluate import ImageAffinity, image_affinity
+    if not heat:
+        raise ValueError('refine needs at least one word')
+    if labels and len(heat) > _engine.MAX_REFINE_MAPS:
+        raise ValueError(f'a label map orders at most {_engine.MAX_REFINE_MAPS} words, got {len(heat)}; pass labels=False for masks only')
+    plane = heat[0].heatmap
+    pil = (image.shape[1], image.shape[0]) if hasattr(image, 'shape') else image.size       # an array's (width, height), PIL's size
+    size = (pil[0], pil[1]) if plane.shape[-2] == plane.shape[-1] else (pil[1], pil[0])
+    if affinity is None:
+        affinity = image_affinity(image, dilations, scale)
+    elif not isinstance(affinity, ImageAffinity):
+        raise TypeError(f'affinity must be an ImageAffinity (daam_amd.image_affinity), got {type(affinity).__name__}')
+    if tuple(affinity.size) != (int(size[0]), int(size[1])):
+        raise ValueError(f'the affinity is of an image of {affinity.size[0]} x {affinity.size[1]}, the expanded maps are '
+                         f'{int(size[0])} x {int(size[1])}')
+    soft = torch.stack([_engine.expand_word_map(m.heatmap.float(), int(size[0]), int(size[1]), absolute=absolute) for m in heat])
+    refined, masks, label_map = affinity.refine(soft, iterations, threshold, True, labels)
+    return Segmentation(words, heat, masks, label_map, refined)
 
 
 @dataclass
@@ -452,6 +485,24 @@ class GlobalHeatMap:
         planes = [plane for wm in word_maps for plane in wm]
         heat = [WordHeatMap(plane, w, r[1]) for plane, (w, _), r in zip(planes, pairs, resolved)]
         return Segmentation([w for w, _ in pairs], heat, masks[0] if len(masks) == 1 else torch.cat(masks), label_map)
+
+    def refine(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]], image, threshold: float = 0.4, iterations: int = 10,
+               dilations=_engine.REFINE_DILATIONS, scale: float = 0.1, absolute: bool = False, labels: bool = True,
+               affinity=None) -> Segmentation:
+        """``segment`` with the image's outline: the soft map ``compute_word_heat_map(w).expand_as(image, absolute=)`` of every word is
+        propagated for ``iterations`` rounds along the local colour affinities of ``image`` (a PIL image: each pixel takes the
+        affinity-weighted mean of its 8 neighbours at every dilation; ``engine.refine_affinity`` / ``refine_maps``) and
+        then thresholded.  The result is a ``Segmentation`` whose ``refined`` holds the f32 maps, so ``iou`` / ``ioa`` / ``components`` /
+        ``clean`` / ``attribute`` compose as after ``segment``.  ``affinity``: an ``ImageAffinity`` of this image
+        (``daam_amd.image_affinity``) to reuse across calls; ``dilations`` and ``scale`` are then its own.  The maps are not
+        renormalised after the propagation."""
+        pairs = [(w, None) if isinstance(w, str) else (w[0], w[1]) for w in words]
+        if not pairs:
+            raise ValueError('refine needs at least one word')
+        resolved = [compute_token_merge_indices(self.tokenizer, self.prompt, w, i) for w, i in pairs]
+        planes = _engine.word_maps(self.heat_maps, [idxs for idxs, _ in resolved])
+        heat = [WordHeatMap(plane, w, r[1]) for plane, (w, _), r in zip(planes, pairs, resolved)]
+        return _refine_words([w for w, _ in pairs], heat, image, threshold, iterations, dilations, scale, absolute, labels, affinity)
 
     def threshold_sweep(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]], image,
                         truth: Union[None, torch.Tensor, Segmentation] = None, thresholds=None, absolute: bool = False) -> ThresholdSweep:
