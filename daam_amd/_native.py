@@ -316,5 +316,42 @@ def check_refine(rc: int) -> None:
         raise DaamError(rc, msg.decode() if msg else '')
 
 
+# ---- libdaam_selfaff.so (C ABI: include/daam_self_affinity.h) ----------------------------------------------------------------------
+SELFAFF_LIB_NAME = 'libdaam_selfaff.so'
+SELFAFF_LIB_PATH = os.environ.get('DAAM_SELFAFF_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), SELFAFF_LIB_NAME)
+SELFAFF_ABI_VERSION = 1
+SELFAFF_EXPORTS = ('daam_self_affinity_accumulate', 'daam_self_affinity_propagate', 'daam_self_affinity_workspace',
+                   'daam_self_affinity_propagate_workspace', 'daam_self_affinity_abi_version', 'daam_self_affinity_last_error')
+
+_selfaff = None
+
+
+def load_self_affinity() -> ctypes.CDLL:
+    """The self-attention affinity library (head-summed softmax(Q K^T) of attn1, propagation of word maps along it); like ``load`` it
+    has no fallback."""
+    global _selfaff
+    if _selfaff is not None:
+        return _selfaff
+    lib = _open(SELFAFF_LIB_PATH, 'self_affinity', SELFAFF_EXPORTS, 'daam_self_affinity_abi_version', SELFAFF_ABI_VERSION)
+    lib.daam_self_affinity_accumulate.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64,
+                                                  c_int64, c_int64, c_float, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.daam_self_affinity_accumulate.restype = c_int
+    lib.daam_self_affinity_propagate.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.daam_self_affinity_propagate.restype = c_int
+    lib.daam_self_affinity_workspace.argtypes = [c_int, c_int, c_int]
+    lib.daam_self_affinity_workspace.restype = c_size_t
+    lib.daam_self_affinity_propagate_workspace.argtypes = [c_int, c_int]
+    lib.daam_self_affinity_propagate_workspace.restype = c_size_t
+    lib.daam_self_affinity_last_error.restype = c_char_p
+    _selfaff = lib
+    return lib
+
+
+def check_self_affinity(rc: int) -> None:
+    if rc != 0:
+        msg = load_self_affinity().daam_self_affinity_last_error()
+        raise DaamError(rc, msg.decode() if msg else '')
+
+
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -40,6 +40,11 @@ COMPONENTS_LIB = os.path.join(HERE, 'libdaam_components.so')
 REFINE_SOURCES = ['daam_refine.hip']
 REFINE_HEADERS = [os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_refine.h')]
 REFINE_LIB = os.path.join(HERE, 'libdaam_refine.so')
+# libdaam_selfaff.so (include/daam_self_affinity.h): the self-attention affinity (head-summed softmax(Q K^T) of attn1, an MFMA kernel
+# of its own) and the propagation of word maps along it.  It reads no header of csrc/ and stays out of every list above.
+SELFAFF_SOURCES = ['daam_self_affinity.hip']
+SELFAFF_HEADERS = [os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_self_affinity.h')]
+SELFAFF_LIB = os.path.join(HERE, 'libdaam_selfaff.so')
 
 
 def csrc_sha() -> str:
@@ -213,6 +218,25 @@ def build_refine(force: bool = False, verbose: bool = True) -> str:
     return REFINE_LIB
 
 
+def self_affinity_stale() -> bool:
+    if not os.path.exists(SELFAFF_LIB):
+        return True
+    t = os.path.getmtime(SELFAFF_LIB)
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in SELFAFF_SOURCES + SELFAFF_HEADERS)
+
+
+def build_self_affinity(force: bool = False, verbose: bool = True) -> str:
+    """``libdaam_selfaff.so``: one hipcc command, when it is missing or older than what it is made of."""
+    if not force and not self_affinity_stale():
+        return SELFAFF_LIB
+    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
+           *[os.path.join(HERE, 'csrc', f) for f in SELFAFF_SOURCES], '-o', SELFAFF_LIB]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return SELFAFF_LIB
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -270,6 +294,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     build_locate(force, verbose)
     build_components(force, verbose)
     build_refine(force, verbose)
+    build_self_affinity(force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')

@@ -8,6 +8,7 @@ reference keeps in ``RawHeatMapCollection`` (daam/heatmap.py:148-172) plus the b
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -224,7 +225,7 @@ def release_parked_contexts() -> None:
 class HeatMapEngine:
     def __init__(self, n_layers: int, tokens: int = 77, out_side: int = 64, accumulate: str = 'exact',
                  defer_steps: int = 0, defer_bytes: int = 32 << 30, reuse_context: bool = False, time_bins=None,
-                 n_probes: int = 0, out_hw: Optional[Tuple[int, int]] = None):
+                 n_probes: int = 0, out_hw: Optional[Tuple[int, int]] = None, self_affinity: bool = False):
         """``accumulate``: ``'exact'`` keeps the running sums in the pipeline dtype like the
         reference (fp16 sums on an fp16 pipeline, heatmap.py:156); ``'float32'`` is the
         accuracy mode.  ``defer_steps`` > 0 records Q/K pointers and taps ``defer_steps``
@@ -241,7 +242,9 @@ class HeatMapEngine:
         ``out_hw`` = ``(out_h, out_w)``: the map of a non-square generation (``map_geometry``; replaces ``out_side``).  Layers are then
         ``[heads, tokens, h, w]`` by ``layer_geometry``, maps ``[rows, out_h, out_w]``, and the finalize is ``finalize_rect_kernel``.
         Not with ``time_bins`` (ValueError); ``daam_finalize_prepare`` does not apply (the finalize clears its output itself).
-        Equal sides are ``out_side``."""
+        Equal sides are ``out_side``.
+        ``self_affinity``: the engine also holds a ``SelfAffinityState`` on the map's grid, fed by ``self_affinity_tap``; it lives and
+        dies with the engine (it is not parked with the context).  ``False`` holds nothing."""
         if accumulate not in ('exact', 'float32'):
             raise ValueError("accumulate must be 'exact' or 'float32'")
         self.lib = nat.load()
@@ -256,6 +259,7 @@ class HeatMapEngine:
         else:
             self.out_h = self.out_w = self.out_side
         self.rect = self.out_h != self.out_w
+        self.self_affinity: Optional['SelfAffinityState'] = SelfAffinityState(self.out_h, self.out_w) if self_affinity else None
         if self.rect and time_bins is not None:
             raise ValueError('time_bins cannot be combined with a non-square map (height= / width=)')
         self.accumulate = accumulate
@@ -475,6 +479,8 @@ class HeatMapEngine:
     # ---- RawHeatMapCollection.clear (heatmap.py:170-172) -----------------------------------------
     def clear(self) -> None:
         self._drop_recorded()
+        if self.self_affinity is not None:
+            self.self_affinity.reset()
         self.touched.clear()
         self._touched_flag = [False] * self.n_layers
         self._set_window(self.defer_steps)
@@ -496,6 +502,13 @@ class HeatMapEngine:
             self._views_out = False
 
     # ---- tap -------------------------------------------------------------------------------------
+    def self_affinity_tap(self, query: torch.Tensor, key: torch.Tensor, heads: int, scale: float) -> None:
+        """One ``attn1`` call's ``to_q`` / ``to_k`` outputs ``[batch, h w, heads * d]`` (the kept half of the batch) into the affinity of
+        an engine built with ``self_affinity=True``."""
+        if self.self_affinity is None:
+            raise ValueError('the engine was built without self_affinity=True')
+        self.self_affinity.tap(query, key, heads, scale)
+
     def tap_qk(self, layer: int, query: torch.Tensor, key: torch.Tensor, heads: int, scale: float,
                factor: int, round_logits: bool = True) -> None:
         """``query`` [B, hw, heads*d], ``key`` [B, tokens, heads*d] straight out of ``to_q`` /
@@ -1688,6 +1701,122 @@ def refine_maps(weights: torch.Tensor, dilations, maps: torch.Tensor, iterations
     if len(parts) == 1:
         return parts[0]
     return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
+
+
+MAX_AFFINITY_CELLS, MAX_AFFINITY_SLICES, MAX_AFFINITY_MAPS, MAX_AFFINITY_ITERATIONS = 16384, 4096, 32, 16   # include/daam_self_affinity.h
+AFFINITY_HEAD_DIMS = (40, 64, 80, 160)
+
+
+def _check_on_device(query: torch.Tensor, key: torch.Tensor) -> None:
+    if query.device.type != 'cuda' or key.device != query.device:
+        raise RuntimeError('daam_amd: the self-attention affinity reads Q and K on the HIP device (no CPU fallback)')
+
+
+class SelfAffinityState:
+    """The self-attention affinity of one trace (include/daam_self_affinity.h): one f32 ``[P, P]`` tensor, P = h w cells
+    of the heat map's grid, into which every tapped ``attn1`` call adds its head-summed ``softmax(Q K^T scale)``
+    (``daam_self_affinity_accumulate``), the statistics workspace, and the counts of calls and slices.  Nothing is allocated before the
+    first tapped call, whose launch overwrites the tensor (``accumulate = 0``)."""
+
+    def __init__(self, h: int, w: int):
+        self.grid = (int(h), int(w))
+        self.cells = self.grid[0] * self.grid[1]
+        if not 1 <= self.cells <= MAX_AFFINITY_CELLS:
+            raise ValueError(f'a grid of {h} x {w} cells: the affinity takes 1..{MAX_AFFINITY_CELLS} cells')
+        self.sums: Optional[torch.Tensor] = None
+        self._ws: Optional[torch.Tensor] = None
+        self.calls = 0
+        self.slices = 0
+
+    def reset(self) -> None:
+        """A new generation: the next tapped call overwrites the sums."""
+        self.calls = self.slices = 0
+
+    def tap(self, query: torch.Tensor, key: torch.Tensor, heads: int, scale: float, weight: float = 1.0) -> None:
+        """``query`` / ``key``: what ``to_q`` / ``to_k`` gave, fp16 or bf16 ``[batch, P, heads * d]`` on the device, read in place
+        through their strides."""
+        lib = nat.load_self_affinity()
+        _check_on_device(query, key)
+        if query.dtype not in (torch.float16, torch.bfloat16) or key.dtype != query.dtype:
+            raise RuntimeError(f'daam_amd: the self-attention affinity reads fp16 or bf16 Q and K, got {query.dtype} / {key.dtype}')
+        if query.dim() != 3 or key.shape != query.shape or query.shape[1] != self.cells or query.shape[2] % heads:
+            raise ValueError(f'self-affinity tap: Q {tuple(query.shape)} / K {tuple(key.shape)} on a grid of {self.cells} cells, {heads} heads')
+        batch, cells, channels = query.shape
+        d = channels // heads
+        if d not in AFFINITY_HEAD_DIMS:
+            raise ValueError(f'self-affinity tap: head dim {d}: one of {AFFINITY_HEAD_DIMS}')
+        if query.stride(2) != 1:
+            query = query.contiguous()
+        if key.stride(2) != 1:
+            key = key.contiguous()
+        need = lib.daam_self_affinity_workspace(batch, heads, cells)
+        if not need:
+            raise ValueError(f'self-affinity tap: batch {batch} x {heads} heads: at most {MAX_AFFINITY_SLICES} slices')
+        dev = query.device
+        if self.sums is None or self.sums.device != dev:
+            self.sums = torch.empty(cells, cells, dtype=torch.float32, device=dev)
+            self.calls = self.slices = 0
+        if self._ws is None or self._ws.device != dev or self._ws.numel() * 8 < need:
+            self._ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            nat.check_self_affinity(lib.daam_self_affinity_accumulate(
+                query.data_ptr(), key.data_ptr(), _DTYPE_CODE[query.dtype], batch, heads, cells, d, query.stride(0), d, query.stride(1),
+                key.stride(0), d, key.stride(1), float(scale), float(weight), int(self.calls > 0), self.sums.data_ptr(), self._ws.data_ptr(),
+                self._ws.numel() * 8, torch.cuda.current_stream(dev).cuda_stream))
+        self.calls += 1
+        self.slices += batch * heads
+
+
+def _launch_propagate(sums: torch.Tensor, maps: torch.Tensor, iterations: int) -> torch.Tensor:
+    """One ``daam_self_affinity_propagate`` call: ``maps`` [N <= 32, P] fp32, contiguous -> f32 [N, P]."""
+    lib = nat.load_self_affinity()
+    n, cells = maps.shape
+    dev = maps.device
+    need = _PROPAGATE_NEED.get((n, cells))
+    if need is None:
+        need = _PROPAGATE_NEED[(n, cells)] = lib.daam_self_affinity_propagate_workspace(n, cells)
+    if not need:
+        raise ValueError(f'affinity_propagate of {n} maps of {cells} cells: out of range')
+    # one allocation: the result, then the workspace behind it (a few hundred KB that live as long as the result does)
+    buf = torch.empty(n * cells + need // 4, dtype=torch.float32, device=dev)
+    out = buf.data_ptr()
+    with _device_guard(dev):
+        nat.check_self_affinity(lib.daam_self_affinity_propagate(sums.data_ptr(), cells, maps.data_ptr(), n, iterations, out, out + 4 * n * cells,
+                                                                 need, torch.cuda.current_stream(dev).cuda_stream))
+    return buf[:n * cells].view(n, cells)
+
+
+_PROPAGATE_NEED: Dict[Tuple[int, int], int] = {}     # (maps, cells) -> daam_self_affinity_propagate_workspace, a pure function of them
+
+
+def _device_guard(dev: torch.device):
+    """``torch.cuda.device(dev)``, or nothing where ``dev`` is the current device already (the common case: entering the context costs
+    several microseconds of a call that takes tens)."""
+    if dev.index is None or dev.index == torch.cuda.current_device():
+        return contextlib.nullcontext()
+    return torch.cuda.device(dev)
+
+
+def affinity_propagate(sums: torch.Tensor, maps: torch.Tensor, iterations: int = 1) -> torch.Tensor:
+    """``daam_self_affinity_propagate``: ``iterations`` rounds of ``m(i) <- sum_j sums[i][j] m(j) / sum_j sums[i][j]`` on every map of
+    ``maps`` [N, h, w] fp32 on the device, ``sums`` the fp32 [h w, h w] affinity (entries finite and >= 0).  Returns f32 [N, h, w]; more
+    than 32 maps run in blocks that are concatenated on the device."""
+    _check_maps(maps)
+    if sums.device != maps.device:
+        raise RuntimeError('daam_amd: the affinity and the maps are on different devices')
+    if sums.dtype != torch.float32 or not sums.is_contiguous() or sums.dim() != 2 or sums.shape[0] != sums.shape[1]:
+        raise RuntimeError('daam_amd: the affinity must be a contiguous fp32 [P, P] tensor')
+    n, h, w = maps.shape
+    if h * w != sums.shape[0]:
+        raise ValueError(f'the affinity is of {sums.shape[0]} cells, the maps are {h} x {w}')
+    iterations = int(iterations)
+    if not 0 <= iterations <= MAX_AFFINITY_ITERATIONS:
+        raise ValueError(f'iterations {iterations}: 0..{MAX_AFFINITY_ITERATIONS}')
+    if n < 1:
+        raise ValueError('affinity_propagate needs at least one map')
+    flat = maps.reshape(n, h * w)
+    parts = [_launch_propagate(sums, flat[i:i + MAX_AFFINITY_MAPS], iterations) for i in range(0, n, MAX_AFFINITY_MAPS)]
+    return (parts[0] if len(parts) == 1 else torch.cat(parts)).reshape(n, h, w)
 
 
 def _check_maps(maps: torch.Tensor) -> None:

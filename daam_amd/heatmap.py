@@ -13,7 +13,7 @@ from . import engine as _engine
 from .utils import cached_nlp, compute_token_merge_indices
 
 __all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair', 'Segmentation',
-           'RegionAttribution', 'KeyScores', 'ThresholdSweep', 'Localization']
+           'RegionAttribution', 'KeyScores', 'ThresholdSweep', 'Localization', 'SelfAffinity']
 
 RawHeatMapKey = Tuple[int, int, int]  # factor, layer, head
 
@@ -440,6 +440,43 @@ class KeyScores(KeyAnalysis):
                          self.tokenizer, self.prompt)
 
 
+class SelfAffinity:
+    """The self-attention affinity of a traced generation (``trace(pipe, self_affinity=True)`` -> ``compute_self_affinity()``;
+    DESIGN 3.22): ``sums`` f32 [P, P], P = h w cells of ``grid``, is the sum over every tapped ``attn1`` call and head of
+    ``softmax(Q K^T scale)`` -- ``slices`` row-stochastic matrices from ``calls`` calls, so every row sums to ``slices``."""
+
+    def __init__(self, sums: torch.Tensor, grid: Tuple[int, int], slices: int, calls: int):
+        grid = (int(grid[0]), int(grid[1]))
+        if sums.dim() != 2 or sums.shape[0] != sums.shape[1] or sums.shape[0] != grid[0] * grid[1]:
+            raise ValueError(f'sums {tuple(sums.shape)} are not the [P, P] matrix of a grid of {grid[0]} x {grid[1]} cells')
+        self.sums, self.grid, self.slices, self.calls = sums, grid, int(slices), int(calls)
+
+    def matrix(self) -> torch.Tensor:
+        """f32 [P, P]: ``sums`` with every row divided by its sum (a row of zeros stays zero)."""
+        total = self.sums.sum(dim=1, keepdim=True)
+        return self.sums / torch.where(total == 0, torch.ones_like(total), total)
+
+    def of(self, y: int, x: int) -> torch.Tensor:
+        """f32 [h, w]: the affinity of the cell ``(y, x)`` to every cell, its row of ``matrix()``."""
+        h, w = self.grid
+        if not (0 <= y < h and 0 <= x < w):
+            raise ValueError(f'cell ({y}, {x}) is outside the grid of {h} x {w}')
+        row = self.sums[y * w + x]
+        total = row.sum()
+        return (row / torch.where(total == 0, torch.ones_like(total), total)).reshape(h, w)
+
+    def propagate(self, maps: torch.Tensor, iterations: int = 1) -> torch.Tensor:
+        """``iterations`` rounds of ``m <- matrix() @ m`` on f32 ``maps`` [N, h, w] for any N (``engine.affinity_propagate``: blocks of
+        32 maps, one launch per iteration and block)."""
+        if maps.dim() != 3 or tuple(maps.shape[1:]) != self.grid:
+            got = ' x '.join(str(int(s)) for s in maps.shape[-2:])
+            raise ValueError(f'the affinity is of a grid of {self.grid[0]} x {self.grid[1]} cells, the maps are {got}')
+        return _engine.affinity_propagate(self.sums, maps, iterations)
+
+    def cpu(self) -> 'SelfAffinity':
+        return SelfAffinity(self.sums.cpu(), self.grid, self.slices, self.calls)
+
+
 class GlobalHeatMap:
     """reference heatmap.py:114-142."""
 
@@ -503,6 +540,20 @@ class GlobalHeatMap:
         planes = _engine.word_maps(self.heat_maps, [idxs for idxs, _ in resolved])
         heat = [WordHeatMap(plane, w, r[1]) for plane, (w, _), r in zip(planes, pairs, resolved)]
         return _refine_words([w for w, _ in pairs], heat, image, threshold, iterations, dilations, scale, absolute, labels, affinity)
+
+    def propagate(self, affinity: SelfAffinity, iterations: int = 1) -> 'GlobalHeatMap':
+        """A new ``GlobalHeatMap`` (same tokenizer and prompt) whose every token plane is propagated along the generation's
+        self-attention affinity for ``iterations`` rounds (``SelfAffinity.propagate``), computed in f32 and cast back to the planes'
+        dtype.  The propagation is linear, so ``compute_word_heat_map`` on the result is the propagated word map, and ``segment``,
+        ``threshold_sweep``, ``localize``, ``refine`` and ``attribute`` compose on it unchanged."""
+        if not isinstance(affinity, SelfAffinity):
+            raise TypeError(f'affinity must be a SelfAffinity, got {type(affinity).__name__}')
+        maps = self.heat_maps
+        if maps.dim() != 3 or tuple(maps.shape[1:]) != affinity.grid:
+            mine = ' x '.join(str(int(s)) for s in maps.shape[-2:])
+            raise ValueError(f'the affinity is of a grid of {affinity.grid[0]} x {affinity.grid[1]} cells, the heat maps are {mine}')
+        out = affinity.propagate(maps.float().contiguous(), iterations)
+        return GlobalHeatMap(self.tokenizer, self.prompt, out.to(maps.dtype))
 
     def threshold_sweep(self, words: Sequence[Union[str, Tuple[str, Optional[int]]]], image,
                         truth: Union[None, torch.Tensor, Segmentation] = None, thresholds=None, absolute: bool = False) -> ThresholdSweep:

@@ -12,7 +12,7 @@ from __future__ import annotations
 import functools
 from typing import Any, Callable, Dict, Generic, Iterable, Iterator, List, Optional, Tuple, TypeVar
 
-__all__ = ['ObjectHooker', 'ModuleLocator', 'AggregateHooker', 'UNetCrossAttentionLocator']
+__all__ = ['ObjectHooker', 'ModuleLocator', 'AggregateHooker', 'UNetCrossAttentionLocator', 'UNetSelfAttentionLocator']
 
 T = TypeVar('T')
 
@@ -128,15 +128,24 @@ class UNetCrossAttentionLocator(ModuleLocator[Any]):
     def _wanted(self, position: int) -> bool:
         return self.restrict is None or position in self.restrict
 
+    ATTRIBUTE = 'attn2'
+
     def locate(self, model) -> List[Any]:
         self.layer_names.clear()
         located: List[Any] = []
         for tag, block in self._stages(model):
             if 'CrossAttn' not in type(block).__name__:
                 continue
-            cross = [tb.attn2 for transformer in block.attentions for tb in transformer.transformer_blocks]
+            cross = [getattr(tb, self.ATTRIBUTE) for transformer in block.attentions for tb in transformer.transformer_blocks]
             kept = [attn for position, attn in enumerate(cross) if self._wanted(position)]
             located += kept
             # the reference numbers the names over the KEPT list but filters them with `restrict` again
             self.layer_names += [f'{tag}-attn-{i}' for i in range(len(kept)) if self._wanted(i)]
         return located
+
+
+class UNetSelfAttentionLocator(UNetCrossAttentionLocator):
+    """The ``attn1`` (self-attention) of the same transformer blocks whose ``attn2`` ``UNetCrossAttentionLocator`` returns for the same
+    arguments, in the same order."""
+
+    ATTRIBUTE = 'attn1'

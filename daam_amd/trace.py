@@ -27,8 +27,8 @@ import torch.nn.functional as F
 
 from .engine import HeatMapEngine, check_probes, check_time_bins, map_geometry, region_scores
 from .coattention import KeyCoattention
-from .heatmap import GlobalHeatMap, KeyScores, RawHeatMapCollection, RegionAttribution, Segmentation
-from .hook import AggregateHooker, ObjectHooker, UNetCrossAttentionLocator
+from .heatmap import GlobalHeatMap, KeyScores, RawHeatMapCollection, RegionAttribution, Segmentation, SelfAffinity
+from .hook import AggregateHooker, ObjectHooker, UNetCrossAttentionLocator, UNetSelfAttentionLocator
 from .utils import cache_dir
 
 __all__ = ['trace', 'DiffusionHeatMapHooker', 'GlobalHeatMap']
@@ -91,6 +91,17 @@ def _probe_embeddings(pipeline, probes, probe_embeds=None) -> torch.Tensor:
     return torch.cat(rows)
 
 
+def _pipeline_dtype(pipeline) -> Optional[torch.dtype]:
+    """The dtype of the pipeline's UNet (its ``dtype``, else that of its first parameter); ``None`` where it cannot be told."""
+    dtype = getattr(pipeline.unet, 'dtype', None)
+    if isinstance(dtype, torch.dtype):
+        return dtype
+    try:
+        return next(pipeline.unet.parameters()).dtype
+    except (AttributeError, StopIteration, TypeError):
+        return None
+
+
 def _no_maps(filtered: bool) -> RuntimeError:
     """What the engine's ``LookupError('no heat maps')`` means to the caller (the reference's two texts, trace.py:119-124)."""
     if filtered:
@@ -102,7 +113,8 @@ class DiffusionHeatMapHooker(AggregateHooker):
     def __init__(self, pipeline, low_memory: bool = False, load_heads: bool = False, save_heads: bool = False,
                  data_dir: Optional[str] = None, *, accumulate: str = 'exact', tap: str = 'qk',
                  defer_steps: Optional[int] = None, batch_prompts: bool = False, time_bins=None, probes=None,
-                 probe_embeds: Optional[torch.Tensor] = None, height: Optional[int] = None, width: Optional[int] = None):
+                 probe_embeds: Optional[torch.Tensor] = None, height: Optional[int] = None, width: Optional[int] = None,
+                 self_affinity: bool = False):
         """Positional arguments as in the reference (trace.py:23-30).  Keyword-only extras:
         ``accumulate`` = ``'exact'`` (running sums in the pipeline dtype, like the reference) or
         ``'float32'``; ``tap`` = ``'qk'`` (fused, default) or ``'probs'`` (materialised
@@ -133,9 +145,20 @@ class DiffusionHeatMapHooker(AggregateHooker):
         ``2 * cell``, at most 128 cells per side), the running sums are ``[heads, 77, h, w]`` per layer (position ``p`` = pixel
         ``(p // w, p % w)``) and every ``compute_*_heat_map(s)`` returns ``[rows, out_h, out_w]`` maps.  A tapped layer whose size
         does not divide the map by its factor is a ValueError.  ``height == width ==`` the pipeline's default size is the default
-        trace.  Not with ``time_bins`` (ValueError: the window-range reduction is not extended to such maps)."""
+        trace.  Not with ``time_bins`` (ValueError: the window-range reduction is not extended to such maps).
+        ``self_affinity=True`` also taps the self-attention (``attn1``) of the transformer blocks whose ``attn2`` is tapped: every call
+        whose query length is the cell count of the global heat map adds its head-summed ``softmax(Q K^T scale)`` (the kept half of the
+        batch) into one f32 ``[h w, h w]`` matrix over all steps, which ``compute_self_affinity()`` returns as a ``SelfAffinity``
+        (``GlobalHeatMap.propagate`` spreads word maps along it).  The model's own output still comes from the original
+        processor with the original arguments.  Not with ``batch_prompts`` (ValueError: per-prompt affinities are out of scope),
+        nor on a pipeline whose UNet is neither fp16 nor bf16 (ValueError here, not in the middle of a generation).
+        ``False`` locates nothing, installs nothing and allocates nothing."""
         if tap not in ('qk', 'probs'):
             raise ValueError("tap must be 'qk' or 'probs'")
+        if self_affinity and batch_prompts:
+            raise ValueError('self_affinity cannot be combined with batch_prompts (one affinity per prompt is out of scope)')
+        if self_affinity and _pipeline_dtype(pipeline) not in (None, torch.float16, torch.bfloat16):
+            raise ValueError(f'self_affinity reads fp16 or bf16 Q and K: the pipeline\'s UNet is {_pipeline_dtype(pipeline)}')
         self.probes = check_probes(probes, time_bins)
         self.time_bins = check_time_bins(time_bins)
         if self.probes is not None and (save_heads or load_heads):
@@ -164,7 +187,7 @@ class DiffusionHeatMapHooker(AggregateHooker):
                                     out_side=int(math.sqrt(self.latent_hw)), out_hw=out_hw, accumulate=accumulate,
                                     defer_steps=_default_defer() if defer_steps is None else defer_steps,
                                     defer_bytes=_default_defer_bytes(pipeline), reuse_context=True, time_bins=self.time_bins,
-                                    n_probes=len(self.probes) if self.probes is not None else 0)
+                                    n_probes=len(self.probes) if self.probes is not None else 0, self_affinity=bool(self_affinity))
         self.all_heat_maps = RawHeatMapCollection(self.engine)
         self.last_prompt: str = ''
         self.last_prompts: List[str] = []
@@ -185,6 +208,10 @@ class DiffusionHeatMapHooker(AggregateHooker):
                                      save_heads=save_heads, data_dir=data_dir)
             for idx, m in enumerate(modules_found)
         ]
+        if self_affinity:
+            self_locator = UNetSelfAttentionLocator(restrict={0} if low_memory else None, locate_middle_block=locate_middle)
+            hookers += [UNetSelfAttentionHooker(m, me, cells=self.engine.out_h * self.engine.out_w)
+                        for m in self_locator.locate(pipeline.unet)]
         hookers.append(PipelineHooker(pipeline, me))
         if type(pipeline).__name__ == 'StableDiffusionXLPipeline':           # trace.py:55-56
             hookers.append(ImageProcessorHooker(pipeline.image_processor, me))
@@ -417,6 +444,19 @@ class DiffusionHeatMapHooker(AggregateHooker):
         except LookupError:
             raise _no_maps(head_idx is not None or layer_idx is not None) from None
         return self._wrap(maps, n_rows, prompt, normalize)
+
+    # -- self-attention affinity ---------------------------------------------------------------------------
+    def compute_self_affinity(self) -> SelfAffinity:
+        """The self-attention affinity of the last generation (a trace built with ``self_affinity=True``): a ``SelfAffinity`` over the
+        grid of the global heat map, summed over every tapped ``attn1`` call of every step (a copy: the next generation starts over)."""
+        state = self.engine.self_affinity
+        if state is None:
+            raise ValueError('the trace was built without self_affinity=True')
+        if state.sums is None or state.calls == 0:
+            h, w = state.grid
+            raise RuntimeError(f'No self-attention maps found: no attn1 call of the last generation had {h} x {w} = {h * w} query positions. '
+                               'Did you forget to call `with trace(..., self_affinity=True)` during generation?')
+        return SelfAffinity(state.sums.clone(), state.grid, state.slices, state.calls)
 
     # -- head analysis -----------------------------------------------------------------------------------
     def compute_key_scores(self, regions=None, prompt=None, factors=None, head_idx=None, layer_idx=None,
@@ -848,6 +888,36 @@ class UNetCrossAttentionHooker(ObjectHooker):
             attention_mask = attn.prepare_attention_mask(attention_mask, positions, batch)
             mixed = self._materialised(attn, hidden_states, context, attention_mask)
         return attn.to_out[1](attn.to_out[0](mixed))                       # output projection, dropout
+
+
+class UNetSelfAttentionHooker(ObjectHooker):
+    """The processor installed on every located ``attn1`` of a trace with ``self_affinity=True``.  The model's output is what the
+    ORIGINAL processor returns for the original arguments, so the traced generation is bit-identical to the untraced one.  Beside it,
+    under ``no_grad``, a call whose query length is the cell count of the global heat map and that carries no attention mask gives
+    ``to_q`` / ``to_k`` of the kept half of its batch (``x[B // 2:]``, as the cross-attention tap keeps it; a batch of 1 whole) to
+    ``HeatMapEngine.self_affinity_tap``."""
+
+    def __init__(self, module, parent_trace: 'trace', cells: int):
+        super().__init__(module)
+        self.trace = parent_trace
+        self.cells = int(cells)
+
+    def _hook_impl(self):
+        self.original_processor = self.module.processor
+        self.module.set_processor(self)
+
+    def _unhook_impl(self):
+        self.module.set_processor(self.original_processor)
+
+    def __call__(self, attn, hidden_states, *args, **kwargs):
+        out = self.original_processor(attn, hidden_states, *args, **kwargs)
+        context = kwargs.get('encoder_hidden_states', args[0] if args else None)
+        mask = kwargs.get('attention_mask', args[1] if len(args) > 1 else None)
+        if context is None and mask is None and hidden_states.dim() == 3 and hidden_states.shape[1] == self.cells:
+            with torch.no_grad():
+                kept = hidden_states[hidden_states.shape[0] // 2:]
+                self.trace.engine.self_affinity_tap(attn.to_q(kept), attn.to_k(kept), attn.heads, attn.scale)
+        return out
 
 
 trace: Type[DiffusionHeatMapHooker] = DiffusionHeatMapHooker
