@@ -5,46 +5,59 @@ import os
 import shutil
 import subprocess
 import sys
+from functools import partial
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ['daam_api.hip', 'daam_tap_api.hip', 'daam_finalize_api.hip', 'daam_kernels.hip', 'daam_tap_mfma.hip', 'daam_tap_d64.hip', 'daam_tap_wide.hip', 'daam_tap_chunk.hip', 'daam_tap_slab.hip', 'daam_tap_pair.hip', 'daam_tap_walk.hip', 'daam_attend_d64.hip', 'daam_finalize.hip', 'daam_finalize_pipe.hip', 'daam_fin_bins.hip', 'daam_finalize_rect.hip', 'daam_epilogue.hip', 'daam_word_masks.hip', 'daam_mask_matrix.hip', 'daam_region_scores.hip']
 HEADERS = ['daam_types.h', 'daam_elem.h', 'daam_finalize.h', 'daam_fin_bins.h', 'daam_fin_rect.h', 'daam_ctx.h', 'daam_tap_common.h', 'daam_tap16.h', 'daam_tap16_softmax.h', 'daam_tap_tile64.h', 'daam_tap_walk.h', 'daam_tap_rows.h', 'daam_epilogue.h', 'daam_tap_d64_body.inc', 'daam_finalize_pipe_asm_r16.inc', 'daam_finalize_pipe_asm_bf16.inc', 'daam_finalize_pipe_asm_f32.inc',
            'daam_finalize_pipe_prefill_r16.inc', 'daam_finalize_pipe_prefill_f32.inc', 'daam_fin_kernel_body.inc', 'daam_fin_up_kernel_body.inc', 'daam_fin_down2_kernel_body.inc', 'daam_fin_pipe_kernel_body.inc', 'daam_word_expand_body.inc', os.path.join('..', '..', 'include', 'daam_hip.h')]
 OUT = os.path.join(HERE, 'libdaam_hip.so')
-# libdaam_analysis.so (include/daam_analysis.h): the one side library, the three per-key analyses (key scores, token Gram, weighted
-# key maps), with no context.  It is kept out of SOURCES / HEADERS so that csrc_sha() and the kernels of libdaam_hip.so stay what the
-# committed profiles were measured on.  Its sources read the first library's headers.
-ANALYSIS_SOURCES = ['daam_key_scores.hip', 'daam_token_gram.hip', 'daam_key_blend.hip']
-ANALYSIS_HEADERS = ['daam_key_planes.h', 'daam_key_scores.h', 'daam_token_gram.h', 'daam_key_blend.h', 'daam_finalize.h', 'daam_epilogue.h',
-                    'daam_elem.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'),
-                    os.path.join('..', '..', 'include', 'daam_analysis.h')]
-ANALYSIS_OUT = os.path.join(HERE, 'libdaam_analysis.so')
-# libdaam_eval.so (include/daam_eval.h): segmentation evaluation -- the threshold sweep.  It restates what it shares with
-# daam_word_masks.hip and reads daam_epilogue.h; like the analysis library it stays out of SOURCES / HEADERS.
-EVAL_SOURCES = ['daam_threshold_sweep.hip']
-EVAL_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_eval.h')]
-EVAL_LIB = os.path.join(HERE, 'libdaam_eval.so')
-# libdaam_locate.so (include/daam_locate.h): localisation -- boxes, peaks and pointing hits.  Like the evaluation library it restates
-# what it shares with daam_word_masks.hip through daam_epilogue.h and stays out of every list above.
-LOCATE_SOURCES = ['daam_locate.hip']
-LOCATE_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_locate.h')]
-LOCATE_LIB = os.path.join(HERE, 'libdaam_locate.so')
-# libdaam_components.so (include/daam_components.h): connected components of byte masks.  It reads daam_epilogue.h for the bit-set
-# helpers alone and stays out of every list above.
-COMPONENTS_SOURCES = ['daam_components.hip']
-COMPONENTS_HEADERS = ['daam_epilogue.h', 'daam_types.h', os.path.join('..', '..', 'include', 'daam_hip.h'),
-                      os.path.join('..', '..', 'include', 'daam_components.h')]
-COMPONENTS_LIB = os.path.join(HERE, 'libdaam_components.so')
-# libdaam_refine.so (include/daam_refine.h): image-guided refinement of soft word maps (local-affinity propagation).  It reads no
-# header of csrc/ and stays out of every list above.
-REFINE_SOURCES = ['daam_refine.hip']
-REFINE_HEADERS = [os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_refine.h')]
-REFINE_LIB = os.path.join(HERE, 'libdaam_refine.so')
-# libdaam_selfaff.so (include/daam_self_affinity.h): the self-attention affinity (head-summed softmax(Q K^T) of attn1, an MFMA kernel
-# of its own) and the propagation of word maps along it.  It reads no header of csrc/ and stays out of every list above.
-SELFAFF_SOURCES = ['daam_self_affinity.hip']
-SELFAFF_HEADERS = [os.path.join('..', '..', 'include', 'daam_hip.h'), os.path.join('..', '..', 'include', 'daam_self_affinity.h')]
-SELFAFF_LIB = os.path.join(HERE, 'libdaam_selfaff.so')
+HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden']    # one command: compile and link
+
+
+class SideLibrary(NamedTuple):
+    """A stateless library beside ``libdaam_hip.so``: ``sources`` go through one hipcc command into ``out``; ``headers`` are what else
+    it is made of (files under csrc/, or relative to it), for ``side_stale``."""
+    name: str
+    sources: list
+    headers: list
+    out: str
+
+
+def _api(header: str) -> str:
+    return os.path.join('..', '..', 'include', header)
+
+
+# Every side library is kept out of SOURCES / HEADERS so that csrc_sha() and the kernels of libdaam_hip.so stay what the committed
+# profiles were measured on.  The order is the build order.
+SIDE_LIBRARIES = (
+    # libdaam_analysis.so (include/daam_analysis.h): the three per-key analyses (key scores, token Gram, weighted key maps), with no
+    # context.  Its sources read the first library's headers.
+    SideLibrary('analysis', ['daam_key_scores.hip', 'daam_token_gram.hip', 'daam_key_blend.hip'],
+                ['daam_key_planes.h', 'daam_key_scores.h', 'daam_token_gram.h', 'daam_key_blend.h', 'daam_finalize.h', 'daam_epilogue.h',
+                 'daam_elem.h', 'daam_types.h', _api('daam_hip.h'), _api('daam_analysis.h')], os.path.join(HERE, 'libdaam_analysis.so')),
+    # libdaam_eval.so (include/daam_eval.h): segmentation evaluation -- the threshold sweep.  It restates what it shares with
+    # daam_word_masks.hip and reads daam_epilogue.h.
+    SideLibrary('eval', ['daam_threshold_sweep.hip'], ['daam_epilogue.h', 'daam_types.h', _api('daam_hip.h'), _api('daam_eval.h')],
+                os.path.join(HERE, 'libdaam_eval.so')),
+    # libdaam_locate.so (include/daam_locate.h): localisation -- boxes, peaks and pointing hits.  Like the evaluation library it
+    # restates what it shares with daam_word_masks.hip through daam_epilogue.h.
+    SideLibrary('locate', ['daam_locate.hip'], ['daam_epilogue.h', 'daam_types.h', _api('daam_hip.h'), _api('daam_locate.h')],
+                os.path.join(HERE, 'libdaam_locate.so')),
+    # libdaam_components.so (include/daam_components.h): connected components of byte masks.  It reads daam_epilogue.h for the
+    # bit-set helpers alone.
+    SideLibrary('components', ['daam_components.hip'], ['daam_epilogue.h', 'daam_types.h', _api('daam_hip.h'), _api('daam_components.h')],
+                os.path.join(HERE, 'libdaam_components.so')),
+    # libdaam_refine.so (include/daam_refine.h): image-guided refinement of soft word maps (local-affinity propagation).  It reads no
+    # header of csrc/.
+    SideLibrary('refine', ['daam_refine.hip'], [_api('daam_hip.h'), _api('daam_refine.h')], os.path.join(HERE, 'libdaam_refine.so')),
+    # libdaam_selfaff.so (include/daam_self_affinity.h): the self-attention affinity (head-summed softmax(Q K^T) of attn1, an MFMA
+    # kernel of its own) and the propagation of word maps along it.  It reads no header of csrc/.
+    SideLibrary('selfaff', ['daam_self_affinity.hip'], [_api('daam_hip.h'), _api('daam_self_affinity.h')],
+                os.path.join(HERE, 'libdaam_selfaff.so')),
+)
+ANALYSIS, EVAL, LOCATE, COMPONENTS, REFINE, SELFAFF = SIDE_LIBRARIES
 
 
 def csrc_sha() -> str:
@@ -123,118 +136,33 @@ def stale() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def analysis_stale() -> bool:
-    if not os.path.exists(ANALYSIS_OUT):
+def side_stale(lib: SideLibrary) -> bool:
+    if not os.path.exists(lib.out):
         return True
-    t = os.path.getmtime(ANALYSIS_OUT)
-    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in ANALYSIS_SOURCES + ANALYSIS_HEADERS)
+    t = os.path.getmtime(lib.out)
+    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in lib.sources + lib.headers)
 
 
-def build_analysis(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_analysis.so``: one hipcc command, when it is missing or older than what it is made of."""
-    if not force and not analysis_stale():
-        return ANALYSIS_OUT
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
-           *[os.path.join(HERE, 'csrc', f) for f in ANALYSIS_SOURCES], '-o', ANALYSIS_OUT]
+def build_side(lib: SideLibrary, force: bool = False, verbose: bool = True) -> str:
+    """A side library: one hipcc command, when it is missing or older than what it is made of."""
+    if not force and not side_stale(lib):
+        return lib.out
+    cmd = [hipcc(), *HIPCC_FLAGS, *[os.path.join(HERE, 'csrc', f) for f in lib.sources], '-o', lib.out]
     if verbose:
         print(' '.join(cmd), flush=True)
     subprocess.run(cmd, check=True)
-    return ANALYSIS_OUT
+    return lib.out
 
 
-def eval_stale() -> bool:
-    if not os.path.exists(EVAL_LIB):
-        return True
-    t = os.path.getmtime(EVAL_LIB)
-    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in EVAL_SOURCES + EVAL_HEADERS)
-
-
-def build_eval(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_eval.so``: one hipcc command, when it is missing or older than what it is made of."""
-    if not force and not eval_stale():
-        return EVAL_LIB
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
-           *[os.path.join(HERE, 'csrc', f) for f in EVAL_SOURCES], '-o', EVAL_LIB]
-    if verbose:
-        print(' '.join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return EVAL_LIB
-
-
-def locate_stale() -> bool:
-    if not os.path.exists(LOCATE_LIB):
-        return True
-    t = os.path.getmtime(LOCATE_LIB)
-    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in LOCATE_SOURCES + LOCATE_HEADERS)
-
-
-def build_locate(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_locate.so``: one hipcc command, when it is missing or older than what it is made of."""
-    if not force and not locate_stale():
-        return LOCATE_LIB
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
-           *[os.path.join(HERE, 'csrc', f) for f in LOCATE_SOURCES], '-o', LOCATE_LIB]
-    if verbose:
-        print(' '.join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return LOCATE_LIB
-
-
-def components_stale() -> bool:
-    if not os.path.exists(COMPONENTS_LIB):
-        return True
-    t = os.path.getmtime(COMPONENTS_LIB)
-    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in COMPONENTS_SOURCES + COMPONENTS_HEADERS)
-
-
-def build_components(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_components.so``: one hipcc command, when it is missing or older than what it is made of."""
-    if not force and not components_stale():
-        return COMPONENTS_LIB
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
-           *[os.path.join(HERE, 'csrc', f) for f in COMPONENTS_SOURCES], '-o', COMPONENTS_LIB]
-    if verbose:
-        print(' '.join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return COMPONENTS_LIB
-
-
-def refine_stale() -> bool:
-    if not os.path.exists(REFINE_LIB):
-        return True
-    t = os.path.getmtime(REFINE_LIB)
-    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in REFINE_SOURCES + REFINE_HEADERS)
-
-
-def build_refine(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_refine.so``: one hipcc command, when it is missing or older than what it is made of."""
-    if not force and not refine_stale():
-        return REFINE_LIB
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
-           *[os.path.join(HERE, 'csrc', f) for f in REFINE_SOURCES], '-o', REFINE_LIB]
-    if verbose:
-        print(' '.join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return REFINE_LIB
-
-
-def self_affinity_stale() -> bool:
-    if not os.path.exists(SELFAFF_LIB):
-        return True
-    t = os.path.getmtime(SELFAFF_LIB)
-    return any(os.path.getmtime(os.path.join(HERE, 'csrc', f)) > t for f in SELFAFF_SOURCES + SELFAFF_HEADERS)
-
-
-def build_self_affinity(force: bool = False, verbose: bool = True) -> str:
-    """``libdaam_selfaff.so``: one hipcc command, when it is missing or older than what it is made of."""
-    if not force and not self_affinity_stale():
-        return SELFAFF_LIB
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden',
-           *[os.path.join(HERE, 'csrc', f) for f in SELFAFF_SOURCES], '-o', SELFAFF_LIB]
-    if verbose:
-        print(' '.join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return SELFAFF_LIB
+# The names tests, tools and the entry point use, all of them read off the records.
+ANALYSIS_SOURCES, ANALYSIS_HEADERS, ANALYSIS_OUT = ANALYSIS[1:]
+EVAL_SOURCES, EVAL_HEADERS, EVAL_LIB = EVAL[1:]
+LOCATE_SOURCES, LOCATE_HEADERS, LOCATE_LIB = LOCATE[1:]
+COMPONENTS_SOURCES, COMPONENTS_HEADERS, COMPONENTS_LIB = COMPONENTS[1:]
+REFINE_SOURCES, REFINE_HEADERS, REFINE_LIB = REFINE[1:]
+SELFAFF_SOURCES, SELFAFF_HEADERS, SELFAFF_LIB = SELFAFF[1:]
+analysis_stale, eval_stale, locate_stale, components_stale, refine_stale, self_affinity_stale = (partial(side_stale, lib) for lib in SIDE_LIBRARIES)
+build_analysis, build_eval, build_locate, build_components, build_refine, build_self_affinity = (partial(build_side, lib) for lib in SIDE_LIBRARIES)
 
 
 def fastpath_out() -> str:
@@ -270,8 +198,7 @@ def build_fastpath(force: bool = False, verbose: bool = True) -> str:
 def build_variant(out: str, flags, verbose: bool = True) -> str:
     """A/B builds for kernel experiments (tools/): the same sources with extra ``-D`` flags into another file; load it with
     ``DAAM_HIP_LIB=<out>``."""
-    cmd = [hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden', *flags,
-           *[os.path.join(HERE, 'csrc', f) for f in SOURCES], '-o', out]
+    cmd = [hipcc(), *HIPCC_FLAGS, *flags, *[os.path.join(HERE, 'csrc', f) for f in SOURCES], '-o', out]
     if verbose:
         print(' '.join(cmd), flush=True)
     subprocess.run(cmd, check=True)
@@ -289,17 +216,13 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
     ``kernel_shas()`` of the library is what ties profiles to a build."""
     from concurrent.futures import ThreadPoolExecutor
     build_fastpath(force, verbose)
-    build_analysis(force, verbose)
-    build_eval(force, verbose)
-    build_locate(force, verbose)
-    build_components(force, verbose)
-    build_refine(force, verbose)
-    build_self_affinity(force, verbose)
+    for lib in SIDE_LIBRARIES:
+        build_side(lib, force, verbose)
     if not force and not stale():
         return OUT
     objdir = os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)
-    flags = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden']
+    flags = [f for f in HIPCC_FLAGS if f != '-shared']
     todo = []
     for f in SOURCES:
         obj = os.path.join(objdir, f + '.o')
@@ -312,8 +235,8 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
         subprocess.run(cmd, check=True)
     with ThreadPoolExecutor(max_workers=jobs or min(6, os.cpu_count() or 1)) as ex:
         list(ex.map(run, todo))
-    run([hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-fvisibility=hidden',
-         *[os.path.join(objdir, f + '.o') for f in SOURCES], '-o', OUT])
+    # the link: no -O3 / -std=, and -shared ahead of -fPIC as this command has always had them
+    run([hipcc(), *[HIPCC_FLAGS[i] for i in (0, 4, 3, 5)], *[os.path.join(objdir, f + '.o') for f in SOURCES], '-o', OUT])
     return OUT
 
 

@@ -1,17 +1,16 @@
 """``libdaam_analysis.so`` without a GPU, said once for its three analyses (key scores, token Gram, key blend): it is the one side
 library, built by one hipcc command beside ``libdaam_hip.so``; it exports what its header declares; every kernel of both libraries
-is the machine code its committed profile was measured on; no kernel instance has scratch; a deleted library is rebuilt alone.  What
-each call does with its arguments is in ``test_key_scores_cpu.py``, ``test_token_gram_cpu.py`` and ``test_key_blend_cpu.py``."""
+is the machine code its committed profile was measured on; no kernel instance has scratch.  That a deleted library is rebuilt alone
+is said for every side library in ``test_side_libraries_cpu.py``; what each call does with its arguments is in ``test_key_scores_cpu.py``, ``test_token_gram_cpu.py`` and ``test_key_blend_cpu.py``."""
 import ctypes
 import json
 import os
 import re
-import struct
 import subprocess
 
 import pytest
 
-from test_tap_walk_cpu import _kernel_descriptors
+import _libcheck as LC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,20 +30,14 @@ def test_one_side_library_builds_and_exports_its_header(built):
     from daam_amd import _native as nat, build
     assert os.path.exists(built) and os.path.exists(build.OUT) and not build.stale() and not build.analysis_stale()
     assert build.ANALYSIS_SOURCES == ['daam_key_scores.hip', 'daam_token_gram.hip', 'daam_key_blend.hip']
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.ANALYSIS_SOURCES + build.ANALYSIS_HEADERS)
-    mine = set(build.ANALYSIS_SOURCES) | {'daam_key_scores.h', 'daam_token_gram.h', 'daam_key_blend.h', 'daam_key_planes.h'}
-    assert mine <= set(build.ANALYSIS_SOURCES + build.ANALYSIS_HEADERS) and not mine & (set(build.SOURCES) | set(build.HEADERS))
     assert not any('analysis' in os.path.basename(f) for f in build.HEADERS)
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_analysis.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.ANALYSIS_EXPORTS) and len(exported) == 7
+    exported = LC.exported(built)
+    assert exported == LC.declared('daam_analysis.h') == sorted(nat.ANALYSIS_EXPORTS) and len(exported) == 7
     assert {'daam_key_scores', 'daam_token_gram', 'daam_token_gram_scratch_bytes', 'daam_key_blend', 'daam_key_blend_scratch_bytes'} <= set(exported)
     assert nat.load_analysis().daam_analysis_abi_version() == 3 == nat.ANALYSIS_ABI_VERSION
     assert ctypes.sizeof(nat.KeyPlanes) == 32
-    # no further library: the build knows two outputs (what it writes: test_deleted_side_library_is_rebuilt_alone), and neither the
-    # build nor the binding has a name of the library the blend once had to itself
+    # no further library: the build knows two outputs (what it writes: test_side_libraries_cpu.py, test_deleted_library_is_rebuilt_alone),
+    # and neither the build nor the binding has a name of the library the blend once had to itself
     assert sorted(n for n in vars(build) if n.endswith('OUT')) == ['ANALYSIS_OUT', 'OUT']
     assert not [n for mod in (build, nat) for n in vars(mod) if 'blend' in n.lower()]
 
@@ -88,23 +81,6 @@ def test_every_kernel_is_what_it_was(built):
 def test_no_instance_has_scratch(built):
     """A resource check only: private segment size 0 and the private-segment enable bit clear in every kernel descriptor."""
     from daam_amd import build
-    kds = _kernel_descriptors(built)
     names = list(build.kernel_shas(built))
-    assert len(names) == 23 and all(k in kds for k in names)
-    for k in names:
-        private, = struct.unpack_from('<I', kds[k], 4)
-        _, rsrc2 = struct.unpack_from('<II', kds[k], 48)
-        assert private == 0 and not (rsrc2 & 1), (k, private)
-
-
-def test_deleted_side_library_is_rebuilt_alone(built):
-    from daam_amd import build
-    others = (build.OUT, build.fastpath_out())
-    stamps = [os.path.getmtime(p) for p in others]
-    files = sorted(os.listdir(build.HERE))
-    os.remove(built)
-    assert not build.stale() and build.analysis_stale()          # a fresh first library does not skip the second
-    build.build(verbose=False)
-    assert os.path.exists(built) and not build.analysis_stale()
-    assert [os.path.getmtime(p) for p in others] == stamps
-    assert sorted(os.listdir(build.HERE)) == files               # the build writes no other file: no further library
+    assert len(names) == 23
+    LC.assert_no_scratch(built, names)

@@ -6,8 +6,6 @@ components; and the Python layer (``engine.mask_components``, ``MaskComponents``
 ``GlobalHeatMap.localize(component='largest')``, ``LocalizationEvaluator``) on a numpy stand-in of the library.  The kernels run in
 ``test_gpu_components.py``."""
 import os
-import re
-import struct
 import subprocess
 
 import numpy as np
@@ -15,9 +13,9 @@ import pytest
 import torch
 
 import _components_domain as C
+import _libcheck as LC
 import _locate_domain as L
 from oracle import fake_diffusers as fd
-from test_tap_walk_cpu import _kernel_descriptors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ('comp_init_kernel', 'comp_local_kernel', 'comp_seam_kernel', 'comp_flatten_kernel', 'comp_scan_kernel', 'comp_roots_kernel',
@@ -43,17 +41,8 @@ def test_library_builds_and_exports_its_header(built, lib):
     from daam_amd import _native as nat, build
     assert os.path.exists(built) and os.path.basename(built) == 'libdaam_components.so' and not build.components_stale()
     assert build.COMPONENTS_SOURCES == ['daam_components.hip']
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.COMPONENTS_SOURCES + build.COMPONENTS_HEADERS)
-    mine = set(build.COMPONENTS_SOURCES) | {os.path.join('..', '..', 'include', 'daam_components.h')}
-    assert mine <= set(build.COMPONENTS_SOURCES + build.COMPONENTS_HEADERS)
-    others = (set(build.SOURCES) | set(build.HEADERS) | set(build.ANALYSIS_SOURCES) | set(build.ANALYSIS_HEADERS) | set(build.EVAL_SOURCES) |
-              set(build.EVAL_HEADERS) | set(build.LOCATE_SOURCES) | set(build.LOCATE_HEADERS))
-    assert not mine & others
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_components.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.COMPONENTS_EXPORTS) and len(exported) == 4
+    exported = LC.exported(built)
+    assert exported == LC.declared('daam_components.h') == sorted(nat.COMPONENTS_EXPORTS) and len(exported) == 4
     assert lib.daam_components_abi_version() == 1 == nat.COMPONENTS_ABI_VERSION
     assert len(lib.daam_mask_components.argtypes) == 16
     assert nat.COMPONENTS_LIB_PATH == built or os.environ.get('DAAM_COMPONENTS_LIB')
@@ -71,13 +60,9 @@ def test_components_header_is_c99(tmp_path):
 def test_no_kernel_has_scratch(built):
     """Private segment size 0 and the private-segment enable bit clear in every kernel descriptor."""
     from daam_amd import build
-    kds = _kernel_descriptors(built)
     names = list(build.kernel_shas(built))
-    assert len(names) == len(KERNELS) and all(k in kds for k in names)
-    for k in names:
-        private, = struct.unpack_from('<I', kds[k], 4)
-        _, rsrc2 = struct.unpack_from('<II', kds[k], 48)
-        assert private == 0 and not (rsrc2 & 1), (k, private)
+    assert len(names) == len(KERNELS)
+    LC.assert_no_scratch(built, names)
 
 
 # ---- argument checks: all of them before any HIP call, so they run here ---------------------------------------------------------------

@@ -7,8 +7,6 @@ stand-in of the library; and, on the float64 oracle alone, that the cases ``test
 ambiguous.  The kernels run in that file."""
 import ctypes
 import os
-import re
-import struct
 import subprocess
 
 import numpy as np
@@ -16,10 +14,10 @@ import pytest
 import torch
 
 import _epilogue_domain as D
+import _libcheck as LC
 import _locate_domain as L
 import _sweep_domain as S
 from oracle import fake_diffusers as fd
-from test_tap_walk_cpu import _kernel_descriptors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ('locate_init_kernel', 'locate_profile_kernel', 'locate_truth_kernel', 'locate_boxes_kernel')
@@ -44,18 +42,8 @@ def test_library_builds_and_exports_its_header(built, lib):
     from daam_amd import _native as nat, build
     assert os.path.exists(built) and os.path.basename(built) == 'libdaam_locate.so' and not build.locate_stale()
     assert build.LOCATE_SOURCES == ['daam_locate.hip']
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.LOCATE_SOURCES + build.LOCATE_HEADERS)
-    mine = set(build.LOCATE_SOURCES) | {os.path.join('..', '..', 'include', 'daam_locate.h')}
-    assert mine <= set(build.LOCATE_SOURCES + build.LOCATE_HEADERS)
-    others = (set(build.SOURCES) | set(build.HEADERS) | set(build.ANALYSIS_SOURCES) | set(build.ANALYSIS_HEADERS) | set(build.EVAL_SOURCES) |
-              set(build.EVAL_HEADERS))
-    assert not mine & others
-    assert not set(build.LOCATE_SOURCES) & (set(build.SOURCES) | set(build.ANALYSIS_SOURCES) | set(build.EVAL_SOURCES))
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_locate.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.LOCATE_EXPORTS) and len(exported) == 4
+    exported = LC.exported(built)
+    assert exported == LC.declared('daam_locate.h') == sorted(nat.LOCATE_EXPORTS) and len(exported) == 4
     assert lib.daam_locate_abi_version() == 1 == nat.LOCATE_ABI_VERSION
     assert len(lib.daam_localize.argtypes) == 19
     assert nat.LOCATE_LIB_PATH == built or os.environ.get('DAAM_LOCATE_LIB')
@@ -73,13 +61,9 @@ def test_locate_header_is_c99(tmp_path):
 def test_no_kernel_has_scratch(built):
     """Private segment size 0 and the private-segment enable bit clear in every kernel descriptor."""
     from daam_amd import build
-    kds = _kernel_descriptors(built)
     names = list(build.kernel_shas(built))
-    assert len(names) == 4 and all(k in kds for k in names)
-    for k in names:
-        private, = struct.unpack_from('<I', kds[k], 4)
-        _, rsrc2 = struct.unpack_from('<II', kds[k], 48)
-        assert private == 0 and not (rsrc2 & 1), (k, private)
+    assert len(names) == 4
+    LC.assert_no_scratch(built, names)
 
 
 # ---- argument checks: all of them before any HIP call, so they run here ---------------------------------------------------------------

@@ -6,7 +6,6 @@ blob to an ellipse's outline; and the Python layer (``engine.refine_affinity`` /
 import ctypes
 import math
 import os
-import re
 import struct
 import subprocess
 
@@ -15,9 +14,9 @@ import pytest
 import torch
 
 import _components_domain as C
+import _libcheck as LC
 import _refine_domain as R
 from oracle import fake_diffusers as fd
-from test_tap_walk_cpu import _kernel_descriptors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID = -1
@@ -42,34 +41,14 @@ def test_library_builds_and_exports_its_header(built, lib):
     from daam_amd import _native as nat, build
     assert os.path.exists(built) and os.path.basename(built) == 'libdaam_refine.so' and not build.refine_stale()
     assert build.REFINE_SOURCES == ['daam_refine.hip']
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.REFINE_SOURCES + build.REFINE_HEADERS)
-    mine = set(build.REFINE_SOURCES) | {os.path.join('..', '..', 'include', 'daam_refine.h')}
-    assert mine <= set(build.REFINE_SOURCES + build.REFINE_HEADERS)
-    others = (set(build.SOURCES) | set(build.HEADERS) | set(build.ANALYSIS_SOURCES) | set(build.ANALYSIS_HEADERS) | set(build.EVAL_SOURCES) |
-              set(build.EVAL_HEADERS) | set(build.LOCATE_SOURCES) | set(build.LOCATE_HEADERS) | set(build.COMPONENTS_SOURCES) |
-              set(build.COMPONENTS_HEADERS))
-    assert not mine & others
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_refine.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.REFINE_EXPORTS) and len(exported) == 6
+    exported = LC.exported(built)
+    assert exported == LC.declared('daam_refine.h') == sorted(nat.REFINE_EXPORTS) and len(exported) == 6
     assert lib.daam_refine_abi_version() == 1 == nat.REFINE_ABI_VERSION
     assert len(lib.daam_refine_affinity.argtypes) == 9 and len(lib.daam_refine_apply.argtypes) == 15
     assert nat.REFINE_LIB_PATH == built or os.environ.get('DAAM_REFINE_LIB')
     names = list(build.kernel_shas(built))
     assert len(names) == N_KERNELS and sum('refine_apply_kernel' in n for n in names) == 10
     assert sum('refine_affinity_kernel' in n for n in names) == 2 and sum('refine_copy_kernel' in n for n in names) == 1
-
-
-def test_the_other_libraries_lists_are_what_they_were():
-    from daam_amd import build
-    assert len(build.SOURCES) == 20 and len(build.HEADERS) == 25 and 'daam_refine.hip' not in build.SOURCES
-    assert build.ANALYSIS_SOURCES == ['daam_key_scores.hip', 'daam_token_gram.hip', 'daam_key_blend.hip']
-    assert build.EVAL_SOURCES == ['daam_threshold_sweep.hip'] and build.LOCATE_SOURCES == ['daam_locate.hip']
-    assert build.COMPONENTS_SOURCES == ['daam_components.hip']
-    assert not any('refine' in f for f in build.SOURCES + build.HEADERS + build.ANALYSIS_HEADERS + build.EVAL_HEADERS + build.LOCATE_HEADERS +
-                   build.COMPONENTS_HEADERS)
 
 
 def test_refine_header_is_c99(tmp_path):
@@ -82,7 +61,7 @@ def test_refine_header_is_c99(tmp_path):
 def test_no_kernel_has_scratch_or_lds(built):
     """Private segment size 0, group segment size 0 and the private-segment enable bit clear in every kernel descriptor."""
     from daam_amd import build
-    kds = _kernel_descriptors(built)
+    kds = LC.kernel_descriptors(built)
     names = list(build.kernel_shas(built))
     assert len(names) == N_KERNELS and all(k in kds for k in names)
     for k in names:

@@ -5,7 +5,6 @@ inside the bounds and the mutants are outside them; and the Python layer (``trac
 ``GlobalHeatMap.propagate``) on numpy stand-ins of the libraries.  The kernels run in ``test_gpu_self_affinity.py``."""
 import math
 import os
-import re
 import struct
 import subprocess
 
@@ -14,9 +13,9 @@ import pytest
 import torch
 
 import _fake_native as FN
+import _libcheck as LC
 import _self_affinity_domain as A
 from oracle import fake_diffusers as fd
-from test_tap_walk_cpu import _kernel_descriptors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID = -1
@@ -41,33 +40,13 @@ def test_library_builds_and_exports_its_header(built, lib):
     from daam_amd import _native as nat, build
     assert os.path.exists(built) and os.path.basename(built) == 'libdaam_selfaff.so' and not build.self_affinity_stale()
     assert build.SELFAFF_SOURCES == ['daam_self_affinity.hip']
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.SELFAFF_SOURCES + build.SELFAFF_HEADERS)
-    mine = set(build.SELFAFF_SOURCES) | {os.path.join('..', '..', 'include', 'daam_self_affinity.h')}
-    assert mine <= set(build.SELFAFF_SOURCES + build.SELFAFF_HEADERS)
-    others = (set(build.SOURCES) | set(build.HEADERS) | set(build.ANALYSIS_SOURCES) | set(build.ANALYSIS_HEADERS) | set(build.EVAL_SOURCES) |
-              set(build.EVAL_HEADERS) | set(build.LOCATE_SOURCES) | set(build.LOCATE_HEADERS) | set(build.COMPONENTS_SOURCES) |
-              set(build.COMPONENTS_HEADERS) | set(build.REFINE_SOURCES) | set(build.REFINE_HEADERS))
-    assert not mine & others
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_self_affinity.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.SELFAFF_EXPORTS) and len(exported) == 6
+    exported = LC.exported(built)
+    assert exported == LC.declared('daam_self_affinity.h') == sorted(nat.SELFAFF_EXPORTS) and len(exported) == 6
     assert lib.daam_self_affinity_abi_version() == 1 == nat.SELFAFF_ABI_VERSION
     assert len(lib.daam_self_affinity_accumulate.argtypes) == 20 and len(lib.daam_self_affinity_propagate.argtypes) == 9
     names = list(build.kernel_shas(built))
     assert len(names) == N_KERNELS and sum('selfaff_stats_kernel' in n for n in names) == 8
     assert sum('selfaff_sums_kernel' in n for n in names) == 8 and sum('selfaff_propagate_kernel' in n for n in names) == 12
-
-
-def test_the_other_libraries_lists_are_what_they_were():
-    from daam_amd import build
-    assert len(build.SOURCES) == 20 and len(build.HEADERS) == 25 and build.csrc_sha() == '75aa74ff4390'
-    assert build.ANALYSIS_SOURCES == ['daam_key_scores.hip', 'daam_token_gram.hip', 'daam_key_blend.hip']
-    assert build.EVAL_SOURCES == ['daam_threshold_sweep.hip'] and build.LOCATE_SOURCES == ['daam_locate.hip']
-    assert build.COMPONENTS_SOURCES == ['daam_components.hip'] and build.REFINE_SOURCES == ['daam_refine.hip']
-    assert not any('self_affinity' in f for f in build.SOURCES + build.HEADERS + build.ANALYSIS_HEADERS + build.EVAL_HEADERS + build.LOCATE_HEADERS +
-                   build.COMPONENTS_HEADERS + build.REFINE_HEADERS)
 
 
 def test_self_affinity_header_is_c99(tmp_path):
@@ -82,7 +61,7 @@ def test_self_affinity_header_is_c99(tmp_path):
 def test_no_kernel_has_scratch(built):
     """Private segment size 0 and the private-segment enable bit clear in every kernel descriptor; LDS only in the MFMA kernels."""
     from daam_amd import build
-    kds = _kernel_descriptors(built)
+    kds = LC.kernel_descriptors(built)
     names = list(build.kernel_shas(built))
     assert len(names) == N_KERNELS and all(k in kds for k in names)
     for k in names:

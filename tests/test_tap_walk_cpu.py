@@ -7,6 +7,8 @@ import struct
 
 import pytest
 
+from _libcheck import kernel_descriptors as _kernel_descriptors
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the two tap_pair_kernel instances (not in profiles/r06_counters.json: they were never profiled)
@@ -48,43 +50,6 @@ def test_walk_kernel_fingerprint(built, name):
     """The machine code of every tap_walk_kernel instance is what it was before the tile moved to daam_tap_tile64.h."""
     _, have = built
     assert have.get(name) == WALK_SHAS[name]
-
-
-def _kernel_descriptors(lib):
-    """{kernel name: its 64-byte kernel descriptor} of the gfx950 code objects in ``lib`` (the ``<name>.kd`` objects)."""
-    data = open(lib, 'rb').read()
-    magic = b'__CLANG_OFFLOAD_BUNDLE__'
-    out = {}
-    pos = data.find(magic)
-    while pos >= 0:
-        n, = struct.unpack_from('<Q', data, pos + len(magic))
-        o = pos + len(magic) + 8
-        for _ in range(n):
-            off, size, ts = struct.unpack_from('<QQQ', data, o)
-            o += 24
-            triple = data[o:o + ts].decode()
-            o += ts
-            if 'gfx950' not in triple or not size:
-                continue
-            elf = data[pos + off:pos + off + size]
-            shoff, = struct.unpack_from('<Q', elf, 0x28)
-            shentsize, shnum, _ = struct.unpack_from('<HHH', elf, 0x3A)
-            secs = [struct.unpack_from('<IIQQQQIIQQ', elf, shoff + i * shentsize) for i in range(shnum)]
-            for (_, typ, _, _, soff, ssize, link, _, _, entsize) in secs:
-                if typ != 2:                                     # SHT_SYMTAB
-                    continue
-                str_off = secs[link][4]
-                for i in range(ssize // entsize):
-                    name_i, _, _, shndx, value, osize = struct.unpack_from('<IBBHQQ', elf, soff + i * entsize)
-                    end = elf.index(b'\0', str_off + name_i)
-                    name = elf[str_off + name_i:end].decode()
-                    if not name.endswith('.kd') or osize != 64 or shndx >= len(secs):
-                        continue
-                    sec = secs[shndx]
-                    start = sec[4] + (value - sec[3])
-                    out[name[:-3]] = elf[start:start + 64]
-        pos = data.find(magic, pos + 1)
-    return out
 
 
 def test_walk_kernel_budget(built):

@@ -5,8 +5,6 @@ argument the header rules out is refused before any HIP call; the Python layer (
 oracle alone, that the cases ``test_gpu_threshold_sweep.py`` holds to it leave few pixels ambiguous.  The kernels run in that file."""
 import ctypes
 import os
-import re
-import struct
 import subprocess
 
 import numpy as np
@@ -14,9 +12,9 @@ import pytest
 import torch
 
 import _epilogue_domain as D
+import _libcheck as LC
 import _sweep_domain as S
 from oracle import fake_diffusers as fd
-from test_tap_walk_cpu import _kernel_descriptors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ('sweep_init_kernel', 'sweep_minmax_kernel', 'sweep_count_kernel', 'sweep_finalize_kernel')
@@ -41,15 +39,8 @@ def test_library_builds_and_exports_its_header(built, lib):
     from daam_amd import _native as nat, build
     assert os.path.exists(built) and os.path.basename(built) == 'libdaam_eval.so' and not build.eval_stale()
     assert build.EVAL_SOURCES == ['daam_threshold_sweep.hip']
-    assert all(os.path.exists(os.path.join(build.HERE, 'csrc', f)) for f in build.EVAL_SOURCES + build.EVAL_HEADERS)
-    mine = set(build.EVAL_SOURCES) | {os.path.join('..', '..', 'include', 'daam_eval.h')}
-    assert mine <= set(build.EVAL_SOURCES + build.EVAL_HEADERS)
-    assert not mine & (set(build.SOURCES) | set(build.HEADERS) | set(build.ANALYSIS_SOURCES) | set(build.ANALYSIS_HEADERS))
-    nm = subprocess.run(['nm', '-D', '--defined-only', built], capture_output=True, text=True, check=True).stdout
-    exported = sorted(re.findall(r' T (\w+)$', nm, flags=re.M))
-    header = open(os.path.join(ROOT, 'include', 'daam_eval.h')).read()
-    declared = sorted(re.findall(r'DAAM_API [\w \*]*?(daam_\w+)\(', header))
-    assert exported == declared == sorted(nat.EVAL_EXPORTS) and len(exported) == 4
+    exported = LC.exported(built)
+    assert exported == LC.declared('daam_eval.h') == sorted(nat.EVAL_EXPORTS) and len(exported) == 4
     assert lib.daam_eval_abi_version() == 1 == nat.EVAL_ABI_VERSION
     assert len(lib.daam_threshold_sweep.argtypes) == 17
     assert nat.EVAL_LIB_PATH == built or os.environ.get('DAAM_EVAL_LIB')
@@ -67,24 +58,9 @@ def test_eval_header_is_c99(tmp_path):
 def test_no_kernel_has_scratch(built):
     """Private segment size 0 and the private-segment enable bit clear in every kernel descriptor."""
     from daam_amd import build
-    kds = _kernel_descriptors(built)
     names = list(build.kernel_shas(built))
-    assert len(names) == 4 and all(k in kds for k in names)
-    for k in names:
-        private, = struct.unpack_from('<I', kds[k], 4)
-        _, rsrc2 = struct.unpack_from('<II', kds[k], 48)
-        assert private == 0 and not (rsrc2 & 1), (k, private)
-
-
-def test_deleted_eval_library_is_rebuilt_alone(built):
-    from daam_amd import build
-    others = (build.OUT, build.ANALYSIS_OUT, build.fastpath_out())
-    stamps = [os.path.getmtime(p) for p in others]
-    os.remove(built)
-    assert not build.stale() and not build.analysis_stale() and build.eval_stale()
-    build.build(verbose=False)
-    assert os.path.exists(built) and not build.eval_stale()
-    assert [os.path.getmtime(p) for p in others] == stamps
+    assert len(names) == 4
+    LC.assert_no_scratch(built, names)
 
 
 # ---- argument checks: all of them before any HIP call, so they run here ---------------------------------------------------------------
