@@ -240,6 +240,17 @@ SELFAFF = Library('libdaam_selfaff.so', 'DAAM_SELFAFF_LIB', 'self_affinity', 1, 
 
 LIBRARIES = (MAIN, ANALYSIS, EVAL, LOCATE, COMPONENTS, REFINE, SELFAFF)
 
+# ---- libdaam_joint.so (C ABI: include/daam_joint_tap.h): the text columns of the joint softmax of an MMDiT attention call -------------
+# A record beside LIBRARIES, not in it: `build.build()` does not make this file (`build.build_joint` does).
+JOINT_LIBRARY = Library('libdaam_joint.so', 'DAAM_JOINT_LIB', 'trace_joint', 1, 'daam_joint_tap_abi_version', 'daam_joint_tap_last_error', {
+    'daam_joint_tap_accumulate': _sig([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                       c_float, c_float, c_int, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    'daam_joint_tap_workspace': _sig([c_int, c_int, c_int], c_size_t),
+    'daam_joint_tap_abi_version': _sig(None),
+    'daam_joint_tap_last_error': _sig(None, c_char_p),
+})
+
 # The names the engine, the tools and the tests use: one line per library, all of it read off the record.
 LIB_NAME, LIB_PATH, ABI_VERSION, EXPORTS = MAIN.file, MAIN.path, MAIN.abi_version, MAIN.exports
 ANALYSIS_LIB_NAME, ANALYSIS_LIB_PATH, ANALYSIS_ABI_VERSION, ANALYSIS_EXPORTS = ANALYSIS.file, ANALYSIS.path, ANALYSIS.abi_version, ANALYSIS.exports
@@ -256,6 +267,8 @@ load_locate, check_locate = _bind(LOCATE, 'load_locate')
 load_components, check_components = _bind(COMPONENTS, 'load_components')
 load_refine, check_refine = _bind(REFINE, 'load_refine')
 load_self_affinity, check_self_affinity = _bind(SELFAFF, 'load_self_affinity')
+JOINT_LIB_NAME, JOINT_LIB_PATH, JOINT_ABI_VERSION, JOINT_EXPORTS = JOINT_LIBRARY.file, JOINT_LIBRARY.path, JOINT_LIBRARY.abi_version, JOINT_LIBRARY.exports
+load_joint, check_joint = _bind(JOINT_LIBRARY, 'load_joint')
 
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -165,6 +165,14 @@ analysis_stale, eval_stale, locate_stale, components_stale, refine_stale, self_a
 build_analysis, build_eval, build_locate, build_components, build_refine, build_self_affinity = (partial(build_side, lib) for lib in SIDE_LIBRARIES)
 
 
+# libdaam_joint.so (include/daam_joint_tap.h): the joint-attention tap of MMDiT pipelines (text columns of a softmax over text and image
+# keys, MFMA kernels of its own).  It reads no header of csrc/.  The record stands beside SIDE_LIBRARIES, not in it: build() makes the
+# six of the tuple, `python -m daam_amd.build` and the entry point make this one after them, by the same recipe.
+JOINT = SideLibrary('joint', ['daam_joint_tap.hip'], [_api('daam_hip.h'), _api('daam_joint_tap.h')], os.path.join(HERE, 'libdaam_joint.so'))
+JOINT_SOURCES, JOINT_HEADERS, JOINT_LIB = JOINT[1:]
+joint_stale, build_joint = partial(side_stale, JOINT), partial(build_side, JOINT)
+
+
 def fastpath_out() -> str:
     import sysconfig
     return os.path.join(HERE, '_fastpath' + sysconfig.get_config_var('EXT_SUFFIX'))
@@ -242,4 +250,5 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
 
 if __name__ == '__main__':
     build(force='--force' in sys.argv)
+    build_joint(force='--force' in sys.argv)
     print(OUT)

@@ -1767,6 +1767,77 @@ class SelfAffinityState:
         self.slices += batch * heads
 
 
+MAX_JOINT_CELLS, MAX_JOINT_TOKENS, MAX_JOINT_SLICES = 16384, 512, 4096     # include/daam_joint_tap.h
+JOINT_HEAD_DIMS = (64, 128)
+
+
+class JointTapState:
+    """The heat-map sums of one trace of an MMDiT pipeline (include/daam_joint_tap.h): one f32 ``[T, h w]`` tensor (with
+    ``per_head`` ``[heads, T, h w]``) into which every tapped joint-attention call adds the text columns of its softmax over text and
+    image keys (``daam_joint_tap_accumulate``), the statistics workspace, and the counts of calls and slices.  Nothing is allocated
+    before the first tapped call, whose launch overwrites the tensor (``accumulate = 0``)."""
+
+    def __init__(self, h: int, w: int, tokens: int, per_head: bool = False):
+        self.grid = (int(h), int(w))
+        self.cells = self.grid[0] * self.grid[1]
+        self.tokens = int(tokens)
+        self.per_head = bool(per_head)
+        if not 1 <= self.cells <= MAX_JOINT_CELLS:
+            raise ValueError(f'a grid of {h} x {w} cells: the joint tap takes 1..{MAX_JOINT_CELLS} cells')
+        if not 1 <= self.tokens <= MAX_JOINT_TOKENS:
+            raise ValueError(f'{tokens} text tokens: the joint tap takes 1..{MAX_JOINT_TOKENS}')
+        self.sums: Optional[torch.Tensor] = None
+        self._ws: Optional[torch.Tensor] = None
+        self.heads = 0
+        self.calls = 0
+        self.slices = 0
+
+    def reset(self) -> None:
+        """A new generation: the next tapped call overwrites the sums."""
+        self.calls = self.slices = 0
+
+    def tap(self, q: torch.Tensor, k_txt: torch.Tensor, k_img: torch.Tensor, heads: int, scale: float, weight: float = 1.0) -> None:
+        """``q`` / ``k_txt`` / ``k_img``: what the projections (and their norms) gave, fp16 or bf16 ``[batch, rows, heads * d]`` on the
+        device with ``rows`` = cells / tokens / image keys, read in place through their strides."""
+        lib = nat.load_joint()
+        _check_on_device(q, k_txt)
+        _check_on_device(q, k_img)
+        if q.dtype not in (torch.float16, torch.bfloat16) or k_txt.dtype != q.dtype or k_img.dtype != q.dtype:
+            raise RuntimeError(f'daam_amd: the joint tap reads fp16 or bf16 Q and K, got {q.dtype} / {k_txt.dtype} / {k_img.dtype}')
+        if (q.dim() != 3 or k_txt.dim() != 3 or k_img.dim() != 3 or q.shape[1] != self.cells or k_txt.shape[1] != self.tokens
+                or not k_txt.shape[0] == k_img.shape[0] == q.shape[0] or not k_txt.shape[2] == k_img.shape[2] == q.shape[2]
+                or q.shape[2] % heads or k_img.shape[1] > MAX_JOINT_CELLS):
+            raise ValueError(f'joint tap: Q {tuple(q.shape)} / text K {tuple(k_txt.shape)} / image K {tuple(k_img.shape)} on a grid of '
+                             f'{self.cells} cells with {self.tokens} tokens, {heads} heads')
+        batch, cells, channels = q.shape
+        d = channels // heads
+        if d not in JOINT_HEAD_DIMS:
+            raise ValueError(f'joint tap: head dim {d}: one of {JOINT_HEAD_DIMS}')
+        if self.per_head and self.sums is not None and self.calls and heads != self.heads:
+            raise ValueError(f'joint tap: {heads} heads after calls with {self.heads}: per-head planes need one head count')
+        q, k_txt, k_img = (t if t.stride(2) == 1 else t.contiguous() for t in (q, k_txt, k_img))
+        need = lib.daam_joint_tap_workspace(batch, heads, cells)
+        if not need:
+            raise ValueError(f'joint tap: batch {batch} x {heads} heads: at most {MAX_JOINT_SLICES} slices')
+        dev = q.device
+        shape = (heads, self.tokens, cells) if self.per_head else (self.tokens, cells)
+        if self.sums is None or self.sums.device != dev or self.sums.shape != shape:
+            self.sums = torch.empty(shape, dtype=torch.float32, device=dev)
+            self.calls = self.slices = 0
+        if self._ws is None or self._ws.device != dev or self._ws.numel() * 8 < need:
+            self._ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+        self.heads = heads
+        with torch.cuda.device(dev):
+            nat.check_joint(lib.daam_joint_tap_accumulate(
+                q.data_ptr(), k_txt.data_ptr(), k_img.data_ptr() if k_img.shape[1] else None, _DTYPE_CODE[q.dtype], batch, heads, cells,
+                self.tokens, k_img.shape[1], d, q.stride(0), d, q.stride(1), k_txt.stride(0), d, k_txt.stride(1), k_img.stride(0), d,
+                k_img.stride(1), float(scale), float(weight), int(self.calls > 0), self.sums.data_ptr(),
+                self.tokens * cells if self.per_head else 0, self._ws.data_ptr(), self._ws.numel() * 8,
+                torch.cuda.current_stream(dev).cuda_stream))
+        self.calls += 1
+        self.slices += batch * heads
+
+
 def _launch_propagate(sums: torch.Tensor, maps: torch.Tensor, iterations: int) -> torch.Tensor:
     """One ``daam_self_affinity_propagate`` call: ``maps`` [N <= 32, P] fp32, contiguous -> f32 [N, P]."""
     lib = nat.load_self_affinity()
