@@ -7,6 +7,7 @@ from .heatmap import *       # noqa: F401,F403
 from .coattention import *   # noqa: F401,F403
 from .trace import *         # noqa: F401,F403
 from .joint import *         # noqa: F401,F403
+from .flux import *          # noqa: F401,F403
 from .experiment import *    # noqa: F401,F403
 from .evaluate import compute_iou, compute_ioa, load_mask, MeanEvaluator, UnsupervisedEvaluator  # noqa: F401
 from .evaluate import mask_overlap_matrix, MaskOverlaps, SweepEvaluator  # noqa: F401

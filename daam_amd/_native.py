@@ -49,6 +49,14 @@ class KeyPlanes(Structure):
     _fields_ = [('base', c_void_p), ('win_stride', c_int64), ('h', c_int32), ('w', c_int32), ('n_win', c_int32), ('pad', c_int32)]
 
 
+class RopeJob(Structure):
+    """``daam_rope_job`` (include/daam_rope.h), 104 bytes."""
+    _fields_ = [('x', c_void_p), ('out', c_void_p), ('cos', c_void_p), ('sin', c_void_p),
+                ('batch', c_int32), ('heads', c_int32), ('rows', c_int32),
+                ('x_stride_b', c_int64), ('x_stride_r', c_int64), ('x_stride_h', c_int64),
+                ('out_stride_b', c_int64), ('out_stride_r', c_int64), ('out_stride_h', c_int64), ('table_stride', c_int64)]
+
+
 @dataclasses.dataclass(frozen=True)
 class Library:
     """How one library of the project is found, checked and typed."""
@@ -251,6 +259,14 @@ JOINT_LIBRARY = Library('libdaam_joint.so', 'DAAM_JOINT_LIB', 'trace_joint', 1, 
     'daam_joint_tap_last_error': _sig(None, c_char_p),
 })
 
+# ---- libdaam_rope.so (C ABI: include/daam_rope.h): the rotary embedding of a FLUX-class attention call, up to four tensors a launch ----
+# Beside LIBRARIES like JOINT_LIBRARY: `build.build_rope` makes the file.
+ROPE_LIBRARY = Library('libdaam_rope.so', 'DAAM_ROPE_LIB', 'trace_flux', 1, 'daam_rope_abi_version', 'daam_rope_last_error', {
+    'daam_rope_apply': _sig([POINTER(RopeJob), c_int, c_int, c_int, c_void_p]),
+    'daam_rope_abi_version': _sig(None),
+    'daam_rope_last_error': _sig(None, c_char_p),
+})
+
 # The names the engine, the tools and the tests use: one line per library, all of it read off the record.
 LIB_NAME, LIB_PATH, ABI_VERSION, EXPORTS = MAIN.file, MAIN.path, MAIN.abi_version, MAIN.exports
 ANALYSIS_LIB_NAME, ANALYSIS_LIB_PATH, ANALYSIS_ABI_VERSION, ANALYSIS_EXPORTS = ANALYSIS.file, ANALYSIS.path, ANALYSIS.abi_version, ANALYSIS.exports
@@ -269,6 +285,8 @@ load_refine, check_refine = _bind(REFINE, 'load_refine')
 load_self_affinity, check_self_affinity = _bind(SELFAFF, 'load_self_affinity')
 JOINT_LIB_NAME, JOINT_LIB_PATH, JOINT_ABI_VERSION, JOINT_EXPORTS = JOINT_LIBRARY.file, JOINT_LIBRARY.path, JOINT_LIBRARY.abi_version, JOINT_LIBRARY.exports
 load_joint, check_joint = _bind(JOINT_LIBRARY, 'load_joint')
+ROPE_LIB_NAME, ROPE_LIB_PATH, ROPE_ABI_VERSION, ROPE_EXPORTS = ROPE_LIBRARY.file, ROPE_LIBRARY.path, ROPE_LIBRARY.abi_version, ROPE_LIBRARY.exports
+load_rope, check_rope = _bind(ROPE_LIBRARY, 'load_rope')
 
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

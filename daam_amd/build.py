@@ -172,6 +172,12 @@ JOINT = SideLibrary('joint', ['daam_joint_tap.hip'], [_api('daam_hip.h'), _api('
 JOINT_SOURCES, JOINT_HEADERS, JOINT_LIB = JOINT[1:]
 joint_stale, build_joint = partial(side_stale, JOINT), partial(build_side, JOINT)
 
+# libdaam_rope.so (include/daam_rope.h): the rotary embedding of a FLUX-class attention call on up to four tensors in one launch, what
+# trace_flux runs before the joint tap.  It reads no header of csrc/.  Like JOINT it stands beside SIDE_LIBRARIES and is made after it.
+ROPE = SideLibrary('rope', ['daam_rope.hip'], [_api('daam_hip.h'), _api('daam_rope.h')], os.path.join(HERE, 'libdaam_rope.so'))
+ROPE_SOURCES, ROPE_HEADERS, ROPE_LIB = ROPE[1:]
+rope_stale, build_rope = partial(side_stale, ROPE), partial(build_side, ROPE)
+
 
 def fastpath_out() -> str:
     import sysconfig
@@ -251,4 +257,5 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0) -> str:
 if __name__ == '__main__':
     build(force='--force' in sys.argv)
     build_joint(force='--force' in sys.argv)
+    build_rope(force='--force' in sys.argv)
     print(OUT)

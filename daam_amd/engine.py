@@ -1838,6 +1838,81 @@ class JointTapState:
         self.slices += batch * heads
 
 
+MAX_ROPE_JOBS, MAX_ROPE_ROWS, MAX_ROPE_SLICES = 4, 16896, 4096                 # include/daam_rope.h
+ROPE_HEAD_DIMS = (64, 128)
+
+
+class RopeTable:
+    """The cos / sin tables of a generation in the form ``rope_apply`` reads: f32, ``stride(-1) == 1``, rows a multiple of 4 floats
+    apart, 16-byte aligned.  A table that is so already is handed back as it is; anything else goes through ``.float().contiguous()``
+    ONCE and is found again by its ``data_ptr`` (the pipeline passes the same table to every block of every step).  The source is
+    kept alive beside its copy so that its address cannot be given to another tensor; ``reset()`` (a new generation) forgets both."""
+
+    def __init__(self):
+        self._cache: Dict[Tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
+
+    def reset(self) -> None:
+        self._cache.clear()
+
+    def __len__(self) -> int:
+        return len(self._cache)
+
+    @staticmethod
+    def fits(table: torch.Tensor) -> bool:
+        return (table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1 and table.stride(0) % 4 == 0
+                and table.stride(0) >= table.shape[1] and table.data_ptr() % 16 == 0)
+
+    def get(self, table: torch.Tensor) -> torch.Tensor:
+        if table.dim() != 2:
+            raise ValueError(f'rope table: {tuple(table.shape)}: [rows, d]')
+        if self.fits(table):
+            return table
+        key = (table.data_ptr(), table.dtype, tuple(table.shape), table.stride(), table.device)
+        hit = self._cache.get(key)
+        if hit is None:
+            hit = self._cache[key] = (table, table.float().contiguous())
+        return hit[1]
+
+
+def rope_apply(jobs: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, int]], d: int) -> None:
+    """One ``daam_rope_apply`` launch (include/daam_rope.h) on the current stream.  A job is ``(x, out, cos, sin, heads)``:
+    ``x`` fp16 or bf16 ``[batch, rows, heads * d]`` on the device -- what a projection gave, or a row range of it --, ``out`` a view of
+    the same shape and dtype that does not overlap it, ``cos`` / ``sin`` f32 ``[rows, d]`` with ``stride(-1) == 1`` (``RopeTable.get``
+    of the pipeline's table, sliced to the job's rows).  Strides are read off the tensors; the head stride is ``d``."""
+    lib = nat.load_rope()
+    if not 1 <= len(jobs) <= MAX_ROPE_JOBS:
+        raise ValueError(f'rope_apply: {len(jobs)} jobs: 1..{MAX_ROPE_JOBS}')
+    if d not in ROPE_HEAD_DIMS:
+        raise ValueError(f'rope_apply: head dim {d}: one of {ROPE_HEAD_DIMS}')
+    first = jobs[0][0]
+    if first.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError(f'daam_amd: rope_apply rotates fp16 or bf16 tensors, got {first.dtype}')
+    table = (nat.RopeJob * len(jobs))()
+    for n, (x, out, cos, sin, heads) in enumerate(jobs):
+        for t in (out, cos, sin):
+            _check_on_device(x, t)
+        if x.device != first.device:
+            raise RuntimeError('daam_amd: rope_apply: the jobs of one launch live on one device')
+        if x.dtype != first.dtype or out.dtype != x.dtype:
+            raise RuntimeError(f'daam_amd: rope_apply: job {n}: x {x.dtype} / out {out.dtype} in a launch of {first.dtype}')
+        if x.dim() != 3 or out.shape != x.shape or heads < 1 or x.shape[2] != heads * d or x.stride(2) != 1 or out.stride(2) != 1:
+            raise ValueError(f'rope_apply: job {n}: x {tuple(x.shape)} / out {tuple(out.shape)}: [batch, rows, {heads} heads * {d}], channels contiguous')
+        batch, rows, _ = x.shape
+        if not 1 <= rows <= MAX_ROPE_ROWS or batch < 1 or batch * heads > MAX_ROPE_SLICES:
+            raise ValueError(f'rope_apply: job {n}: {rows} rows (1..{MAX_ROPE_ROWS}), batch {batch} x {heads} heads (at most {MAX_ROPE_SLICES} slices)')
+        for name, t in (('cos', cos), ('sin', sin)):
+            if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (rows, d) or t.stride(1) != 1:
+                raise ValueError(f'rope_apply: job {n}: {name} {t.dtype} {tuple(t.shape)}: f32 [{rows}, {d}] with stride(-1) == 1 (RopeTable.get)')
+        if rows > 1 and cos.stride(0) != sin.stride(0):
+            raise ValueError(f'rope_apply: job {n}: cos rows {cos.stride(0)} floats apart, sin rows {sin.stride(0)}: one table_stride')
+        table[n] = nat.RopeJob(x.data_ptr(), out.data_ptr(), cos.data_ptr(), sin.data_ptr(), batch, heads, rows,
+                               x.stride(0) if batch > 1 else 0, x.stride(1) if rows > 1 else d * heads, d,
+                               out.stride(0) if batch > 1 else 0, out.stride(1) if rows > 1 else d * heads, d,
+                               cos.stride(0) if rows > 1 else d)
+    with _device_guard(first.device):
+        nat.check_rope(lib.daam_rope_apply(table, len(jobs), _DTYPE_CODE[first.dtype], d, torch.cuda.current_stream(first.device).cuda_stream))
+
+
 def _launch_propagate(sums: torch.Tensor, maps: torch.Tensor, iterations: int) -> torch.Tensor:
     """One ``daam_self_affinity_propagate`` call: ``maps`` [N <= 32, P] fp32, contiguous -> f32 [N, P]."""
     lib = nat.load_self_affinity()
