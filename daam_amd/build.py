@@ -29,6 +29,9 @@ def _api(header: str) -> str:
     return os.path.join('..', '..', 'include', header)
 
 
+# The MFMA row-softmax parts and host checks that the self-affinity and the joint tap share: read by those two alone.
+ROWSOFTMAX = 'daam_rowsoftmax32.h'
+
 # Every side library is kept out of SOURCES / HEADERS so that csrc_sha() and the kernels of libdaam_hip.so stay what the committed
 # profiles were measured on.  The order is the build order.
 SIDE_LIBRARIES = (
@@ -53,8 +56,8 @@ SIDE_LIBRARIES = (
     # header of csrc/.
     SideLibrary('refine', ['daam_refine.hip'], [_api('daam_hip.h'), _api('daam_refine.h')], os.path.join(HERE, 'libdaam_refine.so')),
     # libdaam_selfaff.so (include/daam_self_affinity.h): the self-attention affinity (head-summed softmax(Q K^T) of attn1, an MFMA
-    # kernel of its own) and the propagation of word maps along it.  It reads no header of csrc/.
-    SideLibrary('selfaff', ['daam_self_affinity.hip'], [_api('daam_hip.h'), _api('daam_self_affinity.h')],
+    # kernel of its own) and the propagation of word maps along it.  Of csrc/ it reads ROWSOFTMAX alone.
+    SideLibrary('selfaff', ['daam_self_affinity.hip'], [ROWSOFTMAX, _api('daam_hip.h'), _api('daam_self_affinity.h')],
                 os.path.join(HERE, 'libdaam_selfaff.so')),
 )
 ANALYSIS, EVAL, LOCATE, COMPONENTS, REFINE, SELFAFF = SIDE_LIBRARIES
@@ -166,9 +169,10 @@ build_analysis, build_eval, build_locate, build_components, build_refine, build_
 
 
 # libdaam_joint.so (include/daam_joint_tap.h): the joint-attention tap of MMDiT pipelines (text columns of a softmax over text and image
-# keys, MFMA kernels of its own).  It reads no header of csrc/.  The record stands beside SIDE_LIBRARIES, not in it: build() makes the
-# six of the tuple, `python -m daam_amd.build` and the entry point make this one after them, by the same recipe.
-JOINT = SideLibrary('joint', ['daam_joint_tap.hip'], [_api('daam_hip.h'), _api('daam_joint_tap.h')], os.path.join(HERE, 'libdaam_joint.so'))
+# keys, MFMA kernels of its own).  Of csrc/ it reads ROWSOFTMAX alone.  The record stands beside SIDE_LIBRARIES, not in it: build() makes
+# the six of the tuple, `python -m daam_amd.build` and the entry point make this one after them, by the same recipe.
+JOINT = SideLibrary('joint', ['daam_joint_tap.hip'], [ROWSOFTMAX, _api('daam_hip.h'), _api('daam_joint_tap.h')],
+                    os.path.join(HERE, 'libdaam_joint.so'))
 JOINT_SOURCES, JOINT_HEADERS, JOINT_LIB = JOINT[1:]
 joint_stale, build_joint = partial(side_stale, JOINT), partial(build_side, JOINT)
 

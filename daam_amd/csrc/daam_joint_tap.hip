@@ -1,6 +1,8 @@
 // daam_joint_tap_accumulate (include/daam_joint_tap.h): the text columns of the joint softmax of an MMDiT attention call -- image
-// queries over text AND image keys -- summed over slices into heat-map planes f32 [T][P].  The plan is that of
-// daam_self_affinity.hip: row statistics first, then a second kernel that recomputes a tile and normalises it.
+// queries over text AND image keys -- summed over slices into heat-map planes f32 [T][P].  Row statistics first, then a second
+// kernel that recomputes a tile and normalises it.  The MFMA wrapper, acc_row, the normalise-add, the weighted store and the common host
+// checks are those of daam_rowsoftmax32.h; the online step and the merge of the lane halves stand here and, the same text, in
+// daam_self_affinity.hip (as a function either of them reschedules the statistics kernels): a fix to one is a fix to both.
 //   * joint_stats_kernel<DT, D>  : a workgroup of four waves owns 128 query rows of one slice, 32 per wave, and walks first the text
 //                                  keys and then the image keys in tiles of 64 that go through LDS, two buffers deep: the next
 //                                  tile's global loads are issued before the current tile's MFMAs and land in the other buffer
@@ -17,40 +19,15 @@
 //                                  lane that stay in registers across the whole loop; one read-modify-write of sums at the end.
 // Rows past T / Pk / P are zero-filled in LDS, masked in the statistics and not stored in the epilogue.
 // No atomics, no dependence on the grid: two runs give the same bits.
-#include <hip/hip_runtime.h>
-
 #include "../../include/daam_joint_tap.h"
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
+#include "daam_rowsoftmax32.h"
 
 namespace daam {
 
-constexpr int kJtMaxP = 16384;
 constexpr int kJtMaxT = 512;
-constexpr int kJtMaxSlices = 4096;
 constexpr int kJtThreads = 256;
-constexpr int kJtRows = 128;                        // query rows of a statistics block, cells of an output tile
+constexpr int kJtRows = kRowTile;                   // query rows of a statistics block, cells of an output tile
 constexpr int kJtKeyTile = 64;                      // keys per step of the statistics walk, text rows of an output tile
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bfloat8 __attribute__((ext_vector_type(8)));
-
-template <int DT> struct JtMma;
-template <> struct JtMma<DAAM_F16> {
-    static __device__ __forceinline__ floatx16 run(const uint4& a, const uint4& b, const floatx16& c)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct JtMma<DAAM_BF16> {
-    static __device__ __forceinline__ floatx16 run(const uint4& a, const uint4& b, const floatx16& c)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bfloat8, a), __builtin_bit_cast(bfloat8, b), c, 0, 0, 0);
-    }
-};
 
 struct JtGeom {
     int heads, P, T, Pk, n_slices;
@@ -59,9 +36,6 @@ struct JtGeom {
     long long plane_stride;                         // floats between two planes
     long long q_sb, q_sh, q_sp, kt_sb, kt_sh, kt_sp, ki_sb, ki_sh, ki_sp;
 };
-
-// The row of a 32 x 32 accumulator block that register `reg` of lane half `half` holds (the column is lane & 31).
-__device__ __forceinline__ int jt_acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // A tile of ROWS rows x D elements, rows row0 .. of a [limit][D] matrix with row stride `stride`, as 16-byte chunks: chunk c of the
 // tile (row c / CH, chunk c % CH of the row) is thread c % 256's element c / 256 of `stage`.  Rows >= limit are zero.
@@ -139,11 +113,11 @@ __global__ __launch_bounds__(kJtThreads) void joint_stats_kernel(const uint16_t*
             if (k0 >= limit) break;                 // no key at all in this step
             floatx16 x = {0};
 #pragma unroll
-            for (int kk = 0; kk < KK; ++kk) x = JtMma<DT>::run(cur[(sub * 32 + r) * (CH + 1) + kk * 2 + half], qf[kk], x);
+            for (int kk = 0; kk < KK; ++kk) x = Mma32<DT>::run(cur[(sub * 32 + r) * (CH + 1) + kk * 2 + half], qf[kk], x);
             if (k0 + 32 > limit) {
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg)
-                    if (k0 + jt_acc_row(reg, half) >= limit) x[reg] = -INFINITY;
+                    if (k0 + acc_row(reg, half) >= limit) x[reg] = -INFINITY;
             }
             float top = x[0];
 #pragma unroll
@@ -211,13 +185,12 @@ __global__ __launch_bounds__(kJtThreads) void joint_text_kernel(const uint16_t* 
         for (int kk = 0; kk < KK; ++kk) {
             const uint4 bq = lds_q[(wave * 32 + r) * (CH + 1) + kk * 2 + half];
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) x[mi] = JtMma<DT>::run(lds_k[(mi * 32 + r) * (CH + 1) + kk * 2 + half], bq, x[mi]);
+            for (int mi = 0; mi < 2; ++mi) x[mi] = Mma32<DT>::run(lds_k[(mi * 32 + r) * (CH + 1) + kk * 2 + half], bq, x[mi]);
         }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-            for (int reg = 0; reg < 16; ++reg)
-                acc[mi][reg] = __fmaf_rn(__builtin_amdgcn_exp2f(__fmaf_rn(x[mi][reg], c, st.x)), st.y, acc[mi][reg]);
+            for (int reg = 0; reg < 16; ++reg) acc[mi][reg] = add_prob(x[mi][reg], c, st, acc[mi][reg]);
     }
 
     float* const out_plane = sums + plane * g.plane_stride;
@@ -225,39 +198,12 @@ __global__ __launch_bounds__(kJtThreads) void joint_text_kernel(const uint16_t* 
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int tok = t0 + mi * 32 + jt_acc_row(reg, half);
-            if (tok < g.T && cell < g.P) {
-                float* out = out_plane + (size_t)tok * g.P + cell;
-                *out = __fmaf_rn(weight, acc[mi][reg], accumulate ? *out : 0.f);
-            }
+            const int tok = t0 + mi * 32 + acc_row(reg, half);
+            if (tok < g.T && cell < g.P) store_weighted(out_plane + (size_t)tok * g.P + cell, weight, acc[mi][reg], accumulate);
         }
 }
 
 namespace {
-
-thread_local char joint_error[256] = "";
-
-int joint_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int joint_fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(joint_error, sizeof(joint_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-size_t round8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
-
-int pad_rows(int P) { return (P + kJtRows - 1) / kJtRows * kJtRows; }
-
-bool slices_ok(int batch, int heads) { return batch >= 1 && heads >= 1 && (long long)batch * heads <= kJtMaxSlices; }
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
 
 template <int DT, int D>
 void launch(hipStream_t s, const void* q, const void* k_txt, const void* k_img, float2* stats, float* sums, const JtGeom& g, int planes,
@@ -278,13 +224,9 @@ using namespace daam;
 
 int daam_joint_tap_abi_version(void) { return DAAM_JOINT_TAP_ABI_VERSION; }
 
-const char* daam_joint_tap_last_error(void) { return joint_error; }
+const char* daam_joint_tap_last_error(void) { return last_error; }
 
-size_t daam_joint_tap_workspace(int batch, int heads, int P)
-{
-    if (!slices_ok(batch, heads) || P < 1 || P > kJtMaxP) return 0;
-    return round8(sizeof(float2) * (size_t)batch * heads * pad_rows(P));
-}
+size_t daam_joint_tap_workspace(int batch, int heads, int P) { return stats_workspace(batch, heads, P); }
 
 int daam_joint_tap_accumulate(const void* q, const void* k_txt, const void* k_img, int in_dtype, int batch, int heads, int P, int T, int Pk,
                               int d, int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_p, int64_t kt_stride_b, int64_t kt_stride_h,
@@ -292,38 +234,28 @@ int daam_joint_tap_accumulate(const void* q, const void* k_txt, const void* k_im
                               int accumulate, float* sums, int64_t sums_stride_h, void* workspace, size_t workspace_bytes, void* stream)
 {
     const char* who = "joint_tap_accumulate";
-    if (in_dtype != DAAM_F16 && in_dtype != DAAM_BF16) return joint_fail(DAAM_E_INVALID, "%s: dtype %d: DAAM_F16 or DAAM_BF16", who, in_dtype);
-    if (!slices_ok(batch, heads))
-        return joint_fail(DAAM_E_INVALID, "%s: batch %d x heads %d: each >= 1, at most %d slices", who, batch, heads, kJtMaxSlices);
-    if (P < 1 || P > kJtMaxP) return joint_fail(DAAM_E_INVALID, "%s: P %d: 1..%d", who, P, kJtMaxP);
-    if (T < 1 || T > kJtMaxT) return joint_fail(DAAM_E_INVALID, "%s: T %d: 1..%d", who, T, kJtMaxT);
-    if (Pk < 0 || Pk > kJtMaxP) return joint_fail(DAAM_E_INVALID, "%s: Pk %d: 0..%d", who, Pk, kJtMaxP);
-    if (d != 64 && d != 128) return joint_fail(DAAM_E_INVALID, "%s: head dim %d: 64 or 128", who, d);
-    if (!std::isfinite(scale) || !(scale > 0.f)) return joint_fail(DAAM_E_INVALID, "%s: scale %g: finite and > 0", who, (double)scale);
-    if (!std::isfinite(weight)) return joint_fail(DAAM_E_INVALID, "%s: weight %g is not finite", who, (double)weight);
+    if (const int rc = check_shape(who, in_dtype, batch, heads, P)) return rc;
+    if (T < 1 || T > kJtMaxT) return fail(DAAM_E_INVALID, "%s: T %d: 1..%d", who, T, kJtMaxT);
+    if (Pk < 0 || Pk > kRowMaxP) return fail(DAAM_E_INVALID, "%s: Pk %d: 0..%d", who, Pk, kRowMaxP);
+    if (d != 64 && d != 128) return fail(DAAM_E_INVALID, "%s: head dim %d: 64 or 128", who, d);
+    if (const int rc = check_scale_weight(who, scale, weight)) return rc;
     if (!q || !k_txt || (Pk > 0 && !k_img) || !sums || !workspace)
-        return joint_fail(DAAM_E_INVALID, "%s: q, k_txt, k_img (with Pk > 0), sums and workspace must not be NULL", who);
+        return fail(DAAM_E_INVALID, "%s: q, k_txt, k_img (with Pk > 0), sums and workspace must not be NULL", who);
     if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k_txt) | (Pk > 0 ? reinterpret_cast<uintptr_t>(k_img) : 0)) & 15)
-        return joint_fail(DAAM_E_INVALID, "%s: q, k_txt and k_img must be 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(sums) & 3) return joint_fail(DAAM_E_INVALID, "%s: sums are not 4-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7) return joint_fail(DAAM_E_INVALID, "%s: the workspace is not 8-byte aligned", who);
-    const int64_t strides[] = {q_stride_b, q_stride_h, q_stride_p, kt_stride_b, kt_stride_h, kt_stride_t, ki_stride_b, ki_stride_h, ki_stride_p};
-    for (const int64_t st : strides)
-        if (st < 0 || (st & 7) || st > ((int64_t)1 << 40))
-            return joint_fail(DAAM_E_INVALID, "%s: stride %lld: >= 0 and a multiple of 8 elements (16-byte rows)", who, (long long)st);
+        return fail(DAAM_E_INVALID, "%s: q, k_txt and k_img must be 16-byte aligned", who);
+    if (const int rc = check_outputs_and_strides(who, sums, workspace, {q_stride_b, q_stride_h, q_stride_p, kt_stride_b, kt_stride_h, kt_stride_t,
+                                                                       ki_stride_b, ki_stride_h, ki_stride_p}))
+        return rc;
     if (q_stride_p < d || kt_stride_t < d || (Pk > 0 && ki_stride_p < d))
-        return joint_fail(DAAM_E_INVALID, "%s: row strides %lld / %lld / %lld below the head dim %d", who, (long long)q_stride_p,
-                          (long long)kt_stride_t, (long long)ki_stride_p, d);
+        return fail(DAAM_E_INVALID, "%s: row strides %lld / %lld / %lld below the head dim %d", who, (long long)q_stride_p,
+                    (long long)kt_stride_t, (long long)ki_stride_p, d);
     const int64_t plane = (int64_t)T * P;
     if (sums_stride_h != 0 && sums_stride_h < plane)
-        return joint_fail(DAAM_E_INVALID, "%s: sums_stride_h %lld: 0 (one plane) or >= T * P = %lld", who, (long long)sums_stride_h, (long long)plane);
-    if (sums_stride_h > ((int64_t)1 << 40)) return joint_fail(DAAM_E_INVALID, "%s: sums_stride_h %lld is out of range", who, (long long)sums_stride_h);
-    const size_t need = daam_joint_tap_workspace(batch, heads, P);
-    if (workspace_bytes < need)
-        return joint_fail(DAAM_E_INVALID, "%s: workspace of %zu bytes: %d slices of %d rows need %zu", who, workspace_bytes, batch * heads, P, need);
+        return fail(DAAM_E_INVALID, "%s: sums_stride_h %lld: 0 (one plane) or >= T * P = %lld", who, (long long)sums_stride_h, (long long)plane);
+    if (sums_stride_h > ((int64_t)1 << 40)) return fail(DAAM_E_INVALID, "%s: sums_stride_h %lld is out of range", who, (long long)sums_stride_h);
     const int planes = sums_stride_h ? heads : 1;
-    if (overlap(sums, sizeof(float) * ((size_t)(planes - 1) * (size_t)sums_stride_h + (size_t)plane), workspace, workspace_bytes))
-        return joint_fail(DAAM_E_INVALID, "%s: sums overlap the workspace", who);
+    const size_t sums_bytes = sizeof(float) * ((size_t)(planes - 1) * (size_t)sums_stride_h + (size_t)plane);
+    if (const int rc = check_workspace(who, batch, heads, P, sums, sums_bytes, workspace, workspace_bytes)) return rc;
 
     JtGeom g;
     g.heads = heads; g.P = P; g.T = T; g.Pk = Pk; g.n_slices = batch * heads; g.p_pad = pad_rows(P);
@@ -331,7 +263,7 @@ int daam_joint_tap_accumulate(const void* q, const void* k_txt, const void* k_im
     g.q_sb = q_stride_b; g.q_sh = q_stride_h; g.q_sp = q_stride_p;
     g.kt_sb = kt_stride_b; g.kt_sh = kt_stride_h; g.kt_sp = kt_stride_t;
     g.ki_sb = Pk ? ki_stride_b : 0; g.ki_sh = Pk ? ki_stride_h : 0; g.ki_sp = Pk ? ki_stride_p : 0;
-    const float c = (float)((double)scale * 1.4426950408889634);       // scale log2(e), rounded once
+    const float c = log2e_scale(scale);
     const hipStream_t s = (hipStream_t)stream;
     float2* const stats = static_cast<float2*>(workspace);
     const void* const ki = Pk ? k_img : k_txt;                         // never read with Pk == 0
@@ -343,7 +275,5 @@ int daam_joint_tap_accumulate(const void* q, const void* k_txt, const void* k_im
         if (d == 64) launch<DAAM_BF16, 64>(s, q, k_txt, ki, stats, sums, g, planes, c, weight, acc);
         else launch<DAAM_BF16, 128>(s, q, k_txt, ki, stats, sums, g, planes, c, weight, acc);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return joint_fail((int)e, "%s: %s", who, hipGetErrorString(e));
-    return 0;
+    return launched(who);
 }

@@ -17,50 +17,22 @@
 // d = 40 / 80 / 160 are the same templates with the depth zero-padded to a multiple of 16 in LDS (DP = 48 / 80 / 160); a depth above
 // 80 goes through LDS in two halves.  Rows past P are zero-filled in LDS, masked in the statistics and not stored in the epilogue.
 // No atomics, no dependence on the grid: two runs give the same bits.
-#include <hip/hip_runtime.h>
-
 #include "../../include/daam_self_affinity.h"
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
+#include "daam_rowsoftmax32.h"
 
 namespace daam {
 
-constexpr int kSaMaxP = 16384;
-constexpr int kSaMaxSlices = 4096;
 constexpr int kSaMaxMaps = 32;
 constexpr int kSaMaxIterations = 16;
 constexpr int kSaThreads = 256;
-constexpr int kSaTile = 128;                        // rows of a statistics block, rows and columns of a tile of sums
+constexpr int kSaTile = kRowTile;                   // rows of a statistics block, rows and columns of a tile of sums
 constexpr int kSaKeyTile = 64;                      // keys per step of the statistics walk
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bfloat8 __attribute__((ext_vector_type(8)));
-
-template <int DT> struct SaMma;
-template <> struct SaMma<DAAM_F16> {
-    static __device__ __forceinline__ floatx16 run(const uint4& a, const uint4& b, const floatx16& c)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-    }
-};
-template <> struct SaMma<DAAM_BF16> {
-    static __device__ __forceinline__ floatx16 run(const uint4& a, const uint4& b, const floatx16& c)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bfloat8, a), __builtin_bit_cast(bfloat8, b), c, 0, 0, 0);
-    }
-};
 
 struct SaGeom {
     int heads, P, d, n_slices;
     int p_pad;                                      // P rounded up to whole tiles: the row count of a slice's statistics
     long long q_sb, q_sh, q_sp, k_sb, k_sh, k_sp;
 };
-
-// The row of a 32 x 32 accumulator block that register `reg` of lane half `half` holds (the column is lane & 31).
-__device__ __forceinline__ int sa_acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // ROWS rows x DC elements of depth, from depth `depth0` on, of a [P][d] matrix with row stride `stride` into LDS as 16-byte chunks,
 // DC / 8 + 1 chunks to a row (one of padding).  Rows >= P and depth >= d are zero.
@@ -110,11 +82,11 @@ __global__ __launch_bounds__(kSaThreads) void selfaff_stats_kernel(const uint16_
         for (int sub = 0; sub < kSaKeyTile / 32; ++sub) {
             floatx16 x = {0};
 #pragma unroll
-            for (int kk = 0; kk < KK; ++kk) x = SaMma<DT>::run(lds_k[(sub * 32 + r) * (CH + 1) + kk * 2 + half], qf[kk], x);
+            for (int kk = 0; kk < KK; ++kk) x = Mma32<DT>::run(lds_k[(sub * 32 + r) * (CH + 1) + kk * 2 + half], qf[kk], x);
             float top = -INFINITY;
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                if (j0 + sub * 32 + sa_acc_row(reg, half) >= g.P) x[reg] = -INFINITY;
+                if (j0 + sub * 32 + acc_row(reg, half) >= g.P) x[reg] = -INFINITY;
                 top = fmaxf(top, x[reg]);
             }
             const float m_new = fmaxf(m, top);
@@ -189,17 +161,16 @@ __global__ __launch_bounds__(kSaThreads) void selfaff_sums_kernel(const uint16_t
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) x[mi][ni] = SaMma<DT>::run(a[mi], bf[ni], x[mi][ni]);
+                    for (int ni = 0; ni < 2; ++ni) x[mi][ni] = Mma32<DT>::run(a[mi], bf[ni], x[mi][ni]);
             }
         }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const float2 st = lds_stat[wr * 64 + mi * 32 + sa_acc_row(reg, half)];
+                const float2 st = lds_stat[wr * 64 + mi * 32 + acc_row(reg, half)];
 #pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-                    acc[mi][ni][reg] = __fmaf_rn(__builtin_amdgcn_exp2f(__fmaf_rn(x[mi][ni][reg], c, st.x)), st.y, acc[mi][ni][reg]);
+                for (int ni = 0; ni < 2; ++ni) acc[mi][ni][reg] = add_prob(x[mi][ni][reg], c, st, acc[mi][ni][reg]);
             }
     }
 
@@ -207,14 +178,11 @@ __global__ __launch_bounds__(kSaThreads) void selfaff_sums_kernel(const uint16_t
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int row = i0 + wr * 64 + mi * 32 + sa_acc_row(reg, half);
+            const int row = i0 + wr * 64 + mi * 32 + acc_row(reg, half);
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
                 const int col = j0 + wc * 64 + ni * 32 + r;
-                if (row < g.P && col < g.P) {
-                    float* out = sums + (size_t)row * g.P + col;
-                    *out = __fmaf_rn(weight, acc[mi][ni][reg], accumulate ? *out : 0.f);
-                }
+                if (row < g.P && col < g.P) store_weighted(sums + (size_t)row * g.P + col, weight, acc[mi][ni][reg], accumulate);
             }
         }
 }
@@ -297,30 +265,6 @@ __global__ __launch_bounds__(kSaThreads) void selfaff_copy_kernel(const float* _
 
 namespace {
 
-thread_local char selfaff_error[256] = "";
-
-int selfaff_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int selfaff_fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(selfaff_error, sizeof(selfaff_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-size_t round8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
-
-int pad_rows(int P) { return (P + kSaTile - 1) / kSaTile * kSaTile; }
-
-bool slices_ok(int batch, int heads) { return batch >= 1 && heads >= 1 && (long long)batch * heads <= kSaMaxSlices; }
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 template <int DT, int DP>
 void launch_accumulate(hipStream_t s, const void* q, const void* k, float2* stats, float* sums, const SaGeom& g, float c, float weight,
                        int accumulate)
@@ -359,17 +303,13 @@ using namespace daam;
 
 int daam_self_affinity_abi_version(void) { return DAAM_SELF_AFFINITY_ABI_VERSION; }
 
-const char* daam_self_affinity_last_error(void) { return selfaff_error; }
+const char* daam_self_affinity_last_error(void) { return last_error; }
 
-size_t daam_self_affinity_workspace(int batch, int heads, int P)
-{
-    if (!slices_ok(batch, heads) || P < 1 || P > kSaMaxP) return 0;
-    return round8(sizeof(float2) * (size_t)batch * heads * pad_rows(P));
-}
+size_t daam_self_affinity_workspace(int batch, int heads, int P) { return stats_workspace(batch, heads, P); }
 
 size_t daam_self_affinity_propagate_workspace(int N, int P)
 {
-    if (N < 1 || N > kSaMaxMaps || P < 1 || P > kSaMaxP) return 0;
+    if (N < 1 || N > kSaMaxMaps || P < 1 || P > kRowMaxP) return 0;
     return round8(sizeof(float) * ((size_t)N + 1) * P);
 }
 
@@ -379,68 +319,54 @@ int daam_self_affinity_accumulate(const void* q, const void* k, int in_dtype, in
                                   void* stream)
 {
     const char* who = "self_affinity_accumulate";
-    if (in_dtype != DAAM_F16 && in_dtype != DAAM_BF16) return selfaff_fail(DAAM_E_INVALID, "%s: dtype %d: DAAM_F16 or DAAM_BF16", who, in_dtype);
-    if (!slices_ok(batch, heads))
-        return selfaff_fail(DAAM_E_INVALID, "%s: batch %d x heads %d: each >= 1, at most %d slices", who, batch, heads, kSaMaxSlices);
-    if (P < 1 || P > kSaMaxP) return selfaff_fail(DAAM_E_INVALID, "%s: P %d: 1..%d", who, P, kSaMaxP);
-    if (d != 40 && d != 64 && d != 80 && d != 160) return selfaff_fail(DAAM_E_INVALID, "%s: head dim %d: 40, 64, 80 or 160", who, d);
-    if (!std::isfinite(scale) || !(scale > 0.f)) return selfaff_fail(DAAM_E_INVALID, "%s: scale %g: finite and > 0", who, (double)scale);
-    if (!std::isfinite(weight)) return selfaff_fail(DAAM_E_INVALID, "%s: weight %g is not finite", who, (double)weight);
-    if (!q || !k || !sums || !workspace) return selfaff_fail(DAAM_E_INVALID, "%s: q, k, sums and workspace must not be NULL", who);
+    if (const int rc = check_shape(who, in_dtype, batch, heads, P)) return rc;
+    if (d != 40 && d != 64 && d != 80 && d != 160) return fail(DAAM_E_INVALID, "%s: head dim %d: 40, 64, 80 or 160", who, d);
+    if (const int rc = check_scale_weight(who, scale, weight)) return rc;
+    if (!q || !k || !sums || !workspace) return fail(DAAM_E_INVALID, "%s: q, k, sums and workspace must not be NULL", who);
     if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15)
-        return selfaff_fail(DAAM_E_INVALID, "%s: q and k must be 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(sums) & 3) return selfaff_fail(DAAM_E_INVALID, "%s: sums are not 4-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7) return selfaff_fail(DAAM_E_INVALID, "%s: the workspace is not 8-byte aligned", who);
-    const int64_t strides[] = {q_stride_b, q_stride_h, q_stride_p, k_stride_b, k_stride_h, k_stride_p};
-    for (const int64_t st : strides)
-        if (st < 0 || (st & 7) || st > ((int64_t)1 << 40))
-            return selfaff_fail(DAAM_E_INVALID, "%s: stride %lld: >= 0 and a multiple of 8 elements (16-byte rows)", who, (long long)st);
+        return fail(DAAM_E_INVALID, "%s: q and k must be 16-byte aligned", who);
+    if (const int rc = check_outputs_and_strides(who, sums, workspace, {q_stride_b, q_stride_h, q_stride_p, k_stride_b, k_stride_h, k_stride_p}))
+        return rc;
     if (q_stride_p < d || k_stride_p < d)
-        return selfaff_fail(DAAM_E_INVALID, "%s: row strides %lld / %lld below the head dim %d", who, (long long)q_stride_p, (long long)k_stride_p, d);
-    const size_t need = daam_self_affinity_workspace(batch, heads, P);
-    if (workspace_bytes < need)
-        return selfaff_fail(DAAM_E_INVALID, "%s: workspace of %zu bytes: %d slices of %d rows need %zu", who, workspace_bytes, batch * heads, P, need);
-    if (overlap(sums, sizeof(float) * (size_t)P * P, workspace, workspace_bytes))
-        return selfaff_fail(DAAM_E_INVALID, "%s: sums overlap the workspace", who);
+        return fail(DAAM_E_INVALID, "%s: row strides %lld / %lld below the head dim %d", who, (long long)q_stride_p, (long long)k_stride_p, d);
+    if (const int rc = check_workspace(who, batch, heads, P, sums, sizeof(float) * (size_t)P * P, workspace, workspace_bytes)) return rc;
 
     SaGeom g;
     g.heads = heads; g.P = P; g.d = d; g.n_slices = batch * heads; g.p_pad = pad_rows(P);
     g.q_sb = q_stride_b; g.q_sh = q_stride_h; g.q_sp = q_stride_p;
     g.k_sb = k_stride_b; g.k_sh = k_stride_h; g.k_sp = k_stride_p;
-    const float c = (float)((double)scale * 1.4426950408889634);       // scale log2(e), rounded once
+    const float c = log2e_scale(scale);
     const hipStream_t s = (hipStream_t)stream;
     float2* const stats = static_cast<float2*>(workspace);
     if (in_dtype == DAAM_F16) launch_accumulate_depth<DAAM_F16>(s, q, k, stats, sums, g, c, weight, accumulate != 0);
     else launch_accumulate_depth<DAAM_BF16>(s, q, k, stats, sums, g, c, weight, accumulate != 0);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return selfaff_fail((int)e, "%s: %s", who, hipGetErrorString(e));
-    return 0;
+    return launched(who);
 }
 
 int daam_self_affinity_propagate(const float* sums, int P, const float* maps, int N, int iterations, float* refined, void* workspace,
                                  size_t workspace_bytes, void* stream)
 {
     const char* who = "self_affinity_propagate";
-    if (P < 1 || P > kSaMaxP) return selfaff_fail(DAAM_E_INVALID, "%s: P %d: 1..%d", who, P, kSaMaxP);
-    if (N < 1 || N > kSaMaxMaps) return selfaff_fail(DAAM_E_INVALID, "%s: %d maps: 1..%d", who, N, kSaMaxMaps);
+    if (P < 1 || P > kRowMaxP) return fail(DAAM_E_INVALID, "%s: P %d: 1..%d", who, P, kRowMaxP);
+    if (N < 1 || N > kSaMaxMaps) return fail(DAAM_E_INVALID, "%s: %d maps: 1..%d", who, N, kSaMaxMaps);
     if (iterations < 0 || iterations > kSaMaxIterations)
-        return selfaff_fail(DAAM_E_INVALID, "%s: %d iterations: 0..%d", who, iterations, kSaMaxIterations);
+        return fail(DAAM_E_INVALID, "%s: %d iterations: 0..%d", who, iterations, kSaMaxIterations);
     if (!sums || !maps || !refined || !workspace)
-        return selfaff_fail(DAAM_E_INVALID, "%s: sums, maps, refined and workspace must not be NULL", who);
+        return fail(DAAM_E_INVALID, "%s: sums, maps, refined and workspace must not be NULL", who);
     if ((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(maps) | reinterpret_cast<uintptr_t>(refined) |
          reinterpret_cast<uintptr_t>(workspace)) & 3)
-        return selfaff_fail(DAAM_E_INVALID, "%s: sums, maps, refined and workspace must be 4-byte aligned", who);
+        return fail(DAAM_E_INVALID, "%s: sums, maps, refined and workspace must be 4-byte aligned", who);
     const size_t need = daam_self_affinity_propagate_workspace(N, P);
     if (workspace_bytes < need)
-        return selfaff_fail(DAAM_E_INVALID, "%s: workspace of %zu bytes: %d maps of %d cells need %zu", who, workspace_bytes, N, P, need);
+        return fail(DAAM_E_INVALID, "%s: workspace of %zu bytes: %d maps of %d cells need %zu", who, workspace_bytes, N, P, need);
     const size_t bytes = sizeof(float) * (size_t)N * P;
-    if (overlap(refined, bytes, maps, bytes)) return selfaff_fail(DAAM_E_INVALID, "%s: refined overlaps maps", who);
-    if (overlap(refined, bytes, workspace, workspace_bytes)) return selfaff_fail(DAAM_E_INVALID, "%s: refined overlaps the workspace", who);
+    if (overlap(refined, bytes, maps, bytes)) return fail(DAAM_E_INVALID, "%s: refined overlaps maps", who);
+    if (overlap(refined, bytes, workspace, workspace_bytes)) return fail(DAAM_E_INVALID, "%s: refined overlaps the workspace", who);
     // the launches read maps and sums while they write refined and the workspace
-    if (overlap(maps, bytes, workspace, workspace_bytes)) return selfaff_fail(DAAM_E_INVALID, "%s: maps overlap the workspace", who);
+    if (overlap(maps, bytes, workspace, workspace_bytes)) return fail(DAAM_E_INVALID, "%s: maps overlap the workspace", who);
     const size_t sums_bytes = sizeof(float) * (size_t)P * P;
-    if (overlap(sums, sums_bytes, refined, bytes)) return selfaff_fail(DAAM_E_INVALID, "%s: sums overlap refined", who);
-    if (overlap(sums, sums_bytes, workspace, workspace_bytes)) return selfaff_fail(DAAM_E_INVALID, "%s: sums overlap the workspace", who);
+    if (overlap(sums, sums_bytes, refined, bytes)) return fail(DAAM_E_INVALID, "%s: sums overlap refined", who);
+    if (overlap(sums, sums_bytes, workspace, workspace_bytes)) return fail(DAAM_E_INVALID, "%s: sums overlap the workspace", who);
 
     const hipStream_t s = (hipStream_t)stream;
     if (iterations == 0) {
@@ -462,7 +388,5 @@ int daam_self_affinity_propagate(const float* sums, int P, const float* maps, in
             src = dst;
         }
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return selfaff_fail((int)e, "%s: %s", who, hipGetErrorString(e));
-    return 0;
+    return launched(who);
 }
