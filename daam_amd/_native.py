@@ -267,6 +267,18 @@ ROPE_LIBRARY = Library('libdaam_rope.so', 'DAAM_ROPE_LIB', 'trace_flux', 1, 'daa
     'daam_rope_last_error': _sig(None, c_char_p),
 })
 
+# ---- libdaam_jointaff.so (C ABI: include/daam_joint_affinity.h): the image columns of the joint softmax, from the tap's statistics ----
+# Beside LIBRARIES like JOINT_LIBRARY: `build.build_joint_affinity` makes the file.
+JOINT_AFFINITY_LIBRARY = Library('libdaam_jointaff.so', 'DAAM_JOINT_AFFINITY_LIB', 'self_affinity on trace_joint / trace_flux', 1,
+                                 'daam_joint_affinity_abi_version', 'daam_joint_affinity_last_error', {
+    'daam_joint_affinity_accumulate': _sig([c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_float, c_int, c_void_p,
+                                            c_void_p]),
+    'daam_joint_affinity_stats_bytes': _sig([c_int, c_int, c_int], c_size_t),
+    'daam_joint_affinity_abi_version': _sig(None),
+    'daam_joint_affinity_last_error': _sig(None, c_char_p),
+})
+
 # The names the engine, the tools and the tests use: one line per library, all of it read off the record.
 LIB_NAME, LIB_PATH, ABI_VERSION, EXPORTS = MAIN.file, MAIN.path, MAIN.abi_version, MAIN.exports
 ANALYSIS_LIB_NAME, ANALYSIS_LIB_PATH, ANALYSIS_ABI_VERSION, ANALYSIS_EXPORTS = ANALYSIS.file, ANALYSIS.path, ANALYSIS.abi_version, ANALYSIS.exports
@@ -287,6 +299,9 @@ JOINT_LIB_NAME, JOINT_LIB_PATH, JOINT_ABI_VERSION, JOINT_EXPORTS = JOINT_LIBRARY
 load_joint, check_joint = _bind(JOINT_LIBRARY, 'load_joint')
 ROPE_LIB_NAME, ROPE_LIB_PATH, ROPE_ABI_VERSION, ROPE_EXPORTS = ROPE_LIBRARY.file, ROPE_LIBRARY.path, ROPE_LIBRARY.abi_version, ROPE_LIBRARY.exports
 load_rope, check_rope = _bind(ROPE_LIBRARY, 'load_rope')
+JOINT_AFFINITY_LIB_NAME, JOINT_AFFINITY_LIB_PATH, JOINT_AFFINITY_ABI_VERSION, JOINT_AFFINITY_EXPORTS = \
+    JOINT_AFFINITY_LIBRARY.file, JOINT_AFFINITY_LIBRARY.path, JOINT_AFFINITY_LIBRARY.abi_version, JOINT_AFFINITY_LIBRARY.exports
+load_joint_affinity, check_joint_affinity = _bind(JOINT_AFFINITY_LIBRARY, 'load_joint_affinity')
 
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

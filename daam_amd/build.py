@@ -182,6 +182,15 @@ ROPE = SideLibrary('rope', ['daam_rope.hip'], [_api('daam_hip.h'), _api('daam_ro
 ROPE_SOURCES, ROPE_HEADERS, ROPE_LIB = ROPE[1:]
 rope_stale, build_rope = partial(side_stale, ROPE), partial(build_side, ROPE)
 
+# libdaam_jointaff.so (include/daam_joint_affinity.h): the image columns of the joint softmax, summed into an affinity matrix from the
+# statistics the joint tap has just written (`trace_joint` / `trace_flux` with self_affinity=True).  It reads no header of csrc/: the
+# readers of ROWSOFTMAX stay the two above, and this library restates the few device helpers it shares with them.
+# Like JOINT and ROPE it stands beside SIDE_LIBRARIES and is made after them.
+JOINT_AFFINITY = SideLibrary('jointaff', ['daam_joint_affinity.hip'], [_api('daam_hip.h'), _api('daam_joint_affinity.h')],
+                             os.path.join(HERE, 'libdaam_jointaff.so'))
+JOINT_AFFINITY_SOURCES, JOINT_AFFINITY_HEADERS, JOINT_AFFINITY_LIB = JOINT_AFFINITY[1:]
+joint_affinity_stale, build_joint_affinity = partial(side_stale, JOINT_AFFINITY), partial(build_side, JOINT_AFFINITY)
+
 
 def fastpath_out() -> str:
     import sysconfig
@@ -262,4 +271,5 @@ if __name__ == '__main__':
     build(force='--force' in sys.argv)
     build_joint(force='--force' in sys.argv)
     build_rope(force='--force' in sys.argv)
+    build_joint_affinity(force='--force' in sys.argv)
     print(OUT)

@@ -1837,6 +1837,86 @@ class JointTapState:
         self.calls += 1
         self.slices += batch * heads
 
+    @property
+    def stats(self) -> Optional[torch.Tensor]:
+        """The workspace of the last ``tap``, read-only to callers: per slice and query row the ``float2`` ``(-(m c), 1 / l)`` of the
+        joint softmax, slices ``pad128(cells)`` rows apart (the layout include/daam_joint_affinity.h states).  ``None`` before a tap."""
+        return self._ws
+
+
+JOINT_TAP_STATS_ABI = 1                             # the daam_joint_tap ABI whose workspace layout daam_joint_affinity.h reads
+_joint_affinity_checked = False
+
+
+def _load_joint_affinity():
+    """``nat.load_joint_affinity()``; the first call also holds ``libdaam_joint.so`` to the ABI whose workspace holds the statistics in
+    the layout the affinity reads."""
+    global _joint_affinity_checked
+    lib = nat.load_joint_affinity()
+    if not _joint_affinity_checked:
+        tap_abi = nat.load_joint().daam_joint_tap_abi_version()
+        if tap_abi != JOINT_TAP_STATS_ABI:
+            raise RuntimeError(f'daam_amd: the joint affinity reads the statistics of daam_joint_tap ABI {JOINT_TAP_STATS_ABI}, '
+                               f'libdaam_joint.so reports {tap_abi}; rebuild')
+        _joint_affinity_checked = True
+    return lib
+
+
+class JointAffinityState:
+    """The image-to-image affinity of one trace of an MMDiT / FLUX pipeline (include/daam_joint_affinity.h): one f32
+    ``[P, P]`` tensor, P = h w cells, into which every tapped joint-attention call adds the image columns of its softmax over text and
+    image keys (``daam_joint_affinity_accumulate``), and the counts of calls and slices.  It holds no statistics: each ``tap`` is fed
+    those the joint tap of the same call has just written (``JointTapState.stats``).  Nothing is allocated before the first tapped
+    call, whose launch overwrites the tensor (``accumulate = 0``).  A row of the tensor sums to ``slices`` minus the mass the cell gave
+    to the text keys."""
+
+    def __init__(self, h: int, w: int):
+        self.grid = (int(h), int(w))
+        self.cells = self.grid[0] * self.grid[1]
+        if not 1 <= self.cells <= MAX_JOINT_CELLS:
+            raise ValueError(f'a grid of {h} x {w} cells: the joint affinity takes 1..{MAX_JOINT_CELLS} cells')
+        self.sums: Optional[torch.Tensor] = None
+        self.calls = 0
+        self.slices = 0
+
+    def reset(self) -> None:
+        """A new generation: the next tapped call overwrites the sums."""
+        self.calls = self.slices = 0
+
+    def tap(self, q: torch.Tensor, k_img: torch.Tensor, heads: int, scale: float, stats: torch.Tensor, weight: float = 1.0) -> None:
+        """``q`` / ``k_img``: what ``JointTapState.tap`` was just given, fp16 or bf16 ``[batch, cells, heads * d]`` on the device, read
+        in place through their strides; ``stats``: that state's ``stats`` after the call; ``scale``: the scale of that call."""
+        lib = _load_joint_affinity()
+        _check_on_device(q, k_img)
+        if q.dtype not in (torch.float16, torch.bfloat16) or k_img.dtype != q.dtype:
+            raise RuntimeError(f'daam_amd: the joint affinity reads fp16 or bf16 Q and K, got {q.dtype} / {k_img.dtype}')
+        if (q.dim() != 3 or k_img.dim() != 3 or q.shape[1] != self.cells or k_img.shape[1] != self.cells or k_img.shape[0] != q.shape[0]
+                or k_img.shape[2] != q.shape[2] or q.shape[2] % heads):
+            raise ValueError(f'joint affinity tap: Q {tuple(q.shape)} / image K {tuple(k_img.shape)} on a grid of {self.cells} cells '
+                             f'(the affinity is square), {heads} heads')
+        batch, cells, channels = q.shape
+        d = channels // heads
+        if d not in JOINT_HEAD_DIMS:
+            raise ValueError(f'joint affinity tap: head dim {d}: one of {JOINT_HEAD_DIMS}')
+        q, k_img = (t if t.stride(2) == 1 else t.contiguous() for t in (q, k_img))
+        need = lib.daam_joint_affinity_stats_bytes(batch, heads, cells)
+        if not need:
+            raise ValueError(f'joint affinity tap: batch {batch} x {heads} heads: at most {MAX_JOINT_SLICES} slices')
+        if stats is None or stats.device != q.device or stats.numel() * stats.element_size() < need:
+            raise ValueError(f'joint affinity tap: the statistics of {batch * heads} slices of {cells} rows take {need} bytes on the '
+                             f'device of Q: pass JointTapState.stats of the same call')
+        dev = q.device
+        if self.sums is None or self.sums.device != dev:
+            self.sums = torch.empty(cells, cells, dtype=torch.float32, device=dev)
+            self.calls = self.slices = 0
+        with torch.cuda.device(dev):
+            nat.check_joint_affinity(lib.daam_joint_affinity_accumulate(
+                q.data_ptr(), k_img.data_ptr(), stats.data_ptr(), stats.numel() * stats.element_size(), _DTYPE_CODE[q.dtype], batch, heads,
+                cells, cells, d, q.stride(0), d, q.stride(1), k_img.stride(0), d, k_img.stride(1), float(scale), float(weight),
+                int(self.calls > 0), self.sums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        self.calls += 1
+        self.slices += batch * heads
+
 
 MAX_ROPE_JOBS, MAX_ROPE_ROWS, MAX_ROPE_SLICES = 4, 16896, 4096                 # include/daam_rope.h
 ROPE_HEAD_DIMS = (64, 128)

@@ -40,9 +40,9 @@ from typing import Dict, List, Optional
 import torch
 
 from . import engine as _engine
-from .heatmap import GlobalHeatMap
+from .heatmap import GlobalHeatMap, SelfAffinity
 from .hook import AggregateHooker, ObjectHooker
-from .joint import JointAttentionHooker, _head_dim, _transformer_dtype
+from .joint import JointAttentionHooker, _head_dim, _self_affinity_of, _transformer_dtype
 
 __all__ = ['trace_flux', 'FluxHeatMapHooker', 'T5RowTokenizer']
 
@@ -78,9 +78,16 @@ class FluxHeatMapHooker(AggregateHooker):
     to the untraced one.
 
     ``height`` / ``width``: the size of the generation in pixels; ``cell``: the pixels a token covers on a side (the VAE's factor 8
-    times the 2 x 2 packing of FLUX's latents); ``blocks``: ``'all'``, ``'double'`` or ``'single'``, the kind of block that is hooked."""
+    times the 2 x 2 packing of FLUX's latents); ``blocks``: ``'all'``, ``'double'`` or ``'single'``, the kind of block that is hooked.
 
-    def __init__(self, pipeline, per_head: bool = False, height: int = 1024, width: int = 1024, cell: int = 16, blocks: str = 'all'):
+    ``self_affinity=True``: every tapped call, double-stream or single-stream, also adds the IMAGE columns of the same
+    softmax to one f32 ``[h w, h w]`` matrix, on the same stream, from the same ROTATED Q and image K and the statistics the tap has
+    just written; ``compute_self_affinity()`` returns it as a ``SelfAffinity``.  One thing differs from the UNet: a row sums to
+    ``slices`` MINUS the mass the cell gave to the text keys (``matrix()``, ``of()`` and ``propagate()`` divide by the row sum, so they
+    hold as they are).  Without the option nothing of it is loaded or allocated."""
+
+    def __init__(self, pipeline, per_head: bool = False, height: int = 1024, width: int = 1024, cell: int = 16, blocks: str = 'all',
+                 self_affinity: bool = False):
         transformer = getattr(pipeline, 'transformer', None)
         if transformer is None or not hasattr(transformer, 'single_transformer_blocks') or not hasattr(transformer, 'transformer_blocks'):
             raise ValueError('trace_flux needs a pipeline with a `transformer` of `transformer_blocks` and `single_transformer_blocks` '
@@ -105,6 +112,7 @@ class FluxHeatMapHooker(AggregateHooker):
             if _head_dim(attn) not in _engine.JOINT_HEAD_DIMS:
                 raise ValueError(f'trace_flux: head dim {_head_dim(attn)}: one of {_engine.JOINT_HEAD_DIMS}')
         self.state: Optional[_engine.JointTapState] = None      # made by the first tapped call, which knows the context length
+        self.affinity = _engine.JointAffinityState(*self.grid) if self_affinity else None
         self.table = _engine.RopeTable()
         self.last_prompt: str = ''
         self._calls: Dict[str, int] = dict.fromkeys(KINDS, 0)
@@ -121,6 +129,8 @@ class FluxHeatMapHooker(AggregateHooker):
         self._tokens = None
         if self.state is not None:
             self.state.reset()
+        if self.affinity is not None:
+            self.affinity.reset()
 
     def _buffer(self, like: torch.Tensor, rows: int) -> torch.Tensor:
         buf = self._rotated
@@ -132,6 +142,8 @@ class FluxHeatMapHooker(AggregateHooker):
         if self.state is None or self.state.tokens != k_txt.shape[1]:
             self.state = _engine.JointTapState(self.grid[0], self.grid[1], k_txt.shape[1], self.per_head)
         self.state.tap(q, k_txt, k_img, heads, scale)
+        if self.affinity is not None:
+            self.affinity.tap(q, k_img, heads, scale, self.state.stats)
         self._calls[kind] += 1
         if kind == 'double':
             self._tokens = k_txt.shape[1]
@@ -166,6 +178,11 @@ class FluxHeatMapHooker(AggregateHooker):
             raise ValueError('the trace was built without per_head=True')
         sums = self._sums()
         return (sums / float(self.state.slices // self.state.heads)).view(sums.shape[0], sums.shape[1], *self.grid)
+
+    def compute_self_affinity(self) -> SelfAffinity:
+        """The image-to-image affinity of the last generation (a trace built with ``self_affinity=True``): the image columns of the
+        joint softmax on the rotated Q and K, summed over every tapped call and head (a copy: the next generation starts over)."""
+        return _self_affinity_of(self.affinity, 'trace_flux')
 
 
 class _FluxPipelineHooker(ObjectHooker):

@@ -21,7 +21,7 @@ from typing import Any, List, Optional, Union
 import torch
 
 from . import engine as _engine
-from .heatmap import GlobalHeatMap
+from .heatmap import GlobalHeatMap, SelfAffinity
 from .hook import AggregateHooker, ModuleLocator, ObjectHooker
 
 __all__ = ['trace_joint', 'JointHeatMapHooker', 'MMDiTJointAttentionLocator']
@@ -51,6 +51,15 @@ def _head_dim(attn) -> int:
     return int(inner) // int(attn.heads)
 
 
+def _self_affinity_of(affinity: Optional[_engine.JointAffinityState], who: str) -> SelfAffinity:
+    """``compute_self_affinity()`` of ``trace_joint`` and ``trace_flux``: a copy of the running sums as a ``SelfAffinity``."""
+    if affinity is None:
+        raise ValueError('the trace was built without self_affinity=True')
+    if affinity.sums is None or not affinity.calls:
+        raise RuntimeError(f'No affinity found. Did you forget to call `with {who}(..., self_affinity=True)` during generation?')
+    return SelfAffinity(affinity.sums.clone(), affinity.grid, affinity.slices, affinity.calls)
+
+
 class JointHeatMapHooker(AggregateHooker):
     """``with trace_joint(pipe) as tc: pipe(prompt); tc.compute_global_heat_map()``.
 
@@ -60,9 +69,17 @@ class JointHeatMapHooker(AggregateHooker):
     plane per head).  The generation itself is bit-identical to the untraced one.
 
     ``height`` / ``width``: the size of the generation in pixels where it is not the pipeline's default; the grid is
-    ``size / (vae_scale_factor * patch_size)``."""
+    ``size / (vae_scale_factor * patch_size)``.
 
-    def __init__(self, pipeline, per_head: bool = False, height: Optional[int] = None, width: Optional[int] = None):
+    ``self_affinity=True``: every tapped call also adds the IMAGE columns of the same softmax to one f32
+    ``[h w, h w]`` matrix, on the same stream, from the same Q and image K and the statistics the tap has just written;
+    ``compute_self_affinity()`` returns it as a ``SelfAffinity``, and ``compute_global_heat_map().propagate(aff, n)`` applies as on a
+    UNet trace.  One thing differs from the UNet: a row sums to ``slices`` MINUS the mass the cell gave to the text keys
+    (``matrix()``, ``of()`` and ``propagate()`` divide by the row sum, so they hold as they are).  Without the option nothing of it is
+    loaded or allocated."""
+
+    def __init__(self, pipeline, per_head: bool = False, height: Optional[int] = None, width: Optional[int] = None,
+                 self_affinity: bool = False):
         transformer = getattr(pipeline, 'transformer', None)
         if transformer is None or not hasattr(transformer, 'transformer_blocks'):
             raise ValueError('trace_joint needs a pipeline with a `transformer` of joint-attention blocks (SD3 class); '
@@ -87,6 +104,7 @@ class JointHeatMapHooker(AggregateHooker):
             if _head_dim(attn) not in _engine.JOINT_HEAD_DIMS:
                 raise ValueError(f'trace_joint: head dim {_head_dim(attn)}: one of {_engine.JOINT_HEAD_DIMS}')
         self.state: Optional[_engine.JointTapState] = None      # made by the first tapped call, which knows the context length
+        self.affinity = _engine.JointAffinityState(*self.grid) if self_affinity else None
         self.last_prompt: str = ''
         super().__init__([_JointPipelineHooker(pipeline, self)] + [JointAttentionHooker(attn, self) for attn in located])
 
@@ -95,11 +113,15 @@ class JointHeatMapHooker(AggregateHooker):
         self.last_prompt = prompt if isinstance(prompt, str) else prompt[0]
         if self.state is not None:
             self.state.reset()
+        if self.affinity is not None:
+            self.affinity.reset()
 
     def _tap(self, q, k_txt, k_img, heads: int, scale: float) -> None:
         if self.state is None or self.state.tokens != k_txt.shape[1]:
             self.state = _engine.JointTapState(self.grid[0], self.grid[1], k_txt.shape[1], self.per_head)
         self.state.tap(q, k_txt, k_img, heads, scale)
+        if self.affinity is not None:
+            self.affinity.tap(q, k_img, heads, scale, self.state.stats)
 
     # -- results ---------------------------------------------------------------------------------------------------------------------
     def _sums(self) -> torch.Tensor:
@@ -125,6 +147,11 @@ class JointHeatMapHooker(AggregateHooker):
             raise ValueError('the trace was built without per_head=True')
         sums = self._sums()
         return (sums / float(self.state.slices // self.state.heads)).view(sums.shape[0], sums.shape[1], *self.grid)
+
+    def compute_self_affinity(self) -> SelfAffinity:
+        """The image-to-image affinity of the last generation (a trace built with ``self_affinity=True``): the image columns of the
+        joint softmax summed over every tapped call and slice (a copy: the next generation starts over)."""
+        return _self_affinity_of(self.affinity, 'trace_joint')
 
 
 class _JointPipelineHooker(ObjectHooker):
