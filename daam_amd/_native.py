@@ -279,6 +279,18 @@ JOINT_AFFINITY_LIBRARY = Library('libdaam_jointaff.so', 'DAAM_JOINT_AFFINITY_LIB
     'daam_joint_affinity_last_error': _sig(None, c_char_p),
 })
 
+# ---- libdaam_discover.so (C ABI: include/daam_discover.h): segments from a self-affinity -- prepare, pair_kl, merge, labels -----------
+# Beside LIBRARIES like JOINT_LIBRARY: `build.build_discover` makes the file.
+DISCOVER_LIBRARY = Library('libdaam_discover.so', 'DAAM_DISCOVER_LIB', 'SelfAffinity.discover', 1, 'daam_discover_abi_version',
+                           'daam_discover_last_error', {
+    'daam_discover_prepare': _sig([c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'daam_discover_pair_kl': _sig([c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'daam_discover_merge': _sig([c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'daam_discover_labels': _sig([c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'daam_discover_abi_version': _sig(None),
+    'daam_discover_last_error': _sig(None, c_char_p),
+})
+
 # The names the engine, the tools and the tests use: one line per library, all of it read off the record.
 LIB_NAME, LIB_PATH, ABI_VERSION, EXPORTS = MAIN.file, MAIN.path, MAIN.abi_version, MAIN.exports
 ANALYSIS_LIB_NAME, ANALYSIS_LIB_PATH, ANALYSIS_ABI_VERSION, ANALYSIS_EXPORTS = ANALYSIS.file, ANALYSIS.path, ANALYSIS.abi_version, ANALYSIS.exports
@@ -302,6 +314,9 @@ load_rope, check_rope = _bind(ROPE_LIBRARY, 'load_rope')
 JOINT_AFFINITY_LIB_NAME, JOINT_AFFINITY_LIB_PATH, JOINT_AFFINITY_ABI_VERSION, JOINT_AFFINITY_EXPORTS = \
     JOINT_AFFINITY_LIBRARY.file, JOINT_AFFINITY_LIBRARY.path, JOINT_AFFINITY_LIBRARY.abi_version, JOINT_AFFINITY_LIBRARY.exports
 load_joint_affinity, check_joint_affinity = _bind(JOINT_AFFINITY_LIBRARY, 'load_joint_affinity')
+DISCOVER_LIB_NAME, DISCOVER_LIB_PATH, DISCOVER_ABI_VERSION, DISCOVER_EXPORTS = \
+    DISCOVER_LIBRARY.file, DISCOVER_LIBRARY.path, DISCOVER_LIBRARY.abi_version, DISCOVER_LIBRARY.exports
+load_discover, check_discover = _bind(DISCOVER_LIBRARY, 'load_discover')
 
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

@@ -191,6 +191,15 @@ JOINT_AFFINITY = SideLibrary('jointaff', ['daam_joint_affinity.hip'], [_api('daa
 JOINT_AFFINITY_SOURCES, JOINT_AFFINITY_HEADERS, JOINT_AFFINITY_LIB = JOINT_AFFINITY[1:]
 joint_affinity_stale, build_joint_affinity = partial(side_stale, JOINT_AFFINITY), partial(build_side, JOINT_AFFINITY)
 
+# libdaam_discover.so (include/daam_discover.h): segments from a self-affinity without a word list -- probability rows and their
+# logarithms, the symmetric KL divergence of anchor rows against all rows (a tiled VALU kernel), the merge of member rows and the label
+# map of the resized proposals (`SelfAffinity.discover`).  It reads no header of csrc/.  Like JOINT, ROPE and
+# JOINT_AFFINITY it stands beside SIDE_LIBRARIES and is made after them.
+DISCOVER = SideLibrary('discover', ['daam_discover.hip'], [_api('daam_hip.h'), _api('daam_discover.h')],
+                       os.path.join(HERE, 'libdaam_discover.so'))
+DISCOVER_SOURCES, DISCOVER_HEADERS, DISCOVER_LIB = DISCOVER[1:]
+discover_stale, build_discover = partial(side_stale, DISCOVER), partial(build_side, DISCOVER)
+
 
 def fastpath_out() -> str:
     import sysconfig
@@ -272,4 +281,5 @@ if __name__ == '__main__':
     build_joint(force='--force' in sys.argv)
     build_rope(force='--force' in sys.argv)
     build_joint_affinity(force='--force' in sys.argv)
+    build_discover(force='--force' in sys.argv)
     print(OUT)

@@ -2045,6 +2045,116 @@ def affinity_propagate(sums: torch.Tensor, maps: torch.Tensor, iterations: int =
     return (parts[0] if len(parts) == 1 else torch.cat(parts)).reshape(n, h, w)
 
 
+MAX_DISCOVER_ROWS, MAX_DISCOVER_CELLS, MAX_DISCOVER_GROUPS = 16384, 16384, 1024            # include/daam_discover.h
+MAX_DISCOVER_PROPOSALS, MAX_DISCOVER_GRID, MAX_DISCOVER_OUT = 255, 128, 2048
+
+
+def _check_discover(name: str, t: torch.Tensor, dtype: torch.dtype, dims: int, like: Optional[torch.Tensor] = None) -> None:
+    """What every operand of the discovery launchers owes: the dtype, the rank, the HIP device (that of ``like``)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dims:
+        got = f'{t.dtype} {tuple(t.shape)}' if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f'{name}: {got}: a {dtype} tensor of {dims} dimensions')
+    _check_discover_device(t, like)
+
+
+def _check_discover_device(t: torch.Tensor, like: Optional[torch.Tensor]) -> None:
+    if t.device.type != 'cuda' or (like is not None and t.device != like.device):
+        raise RuntimeError('daam_amd: the discovery passes read their operands on one HIP device (no CPU fallback)')
+
+
+def _stream_of(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def discover_prepare(src: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``daam_discover_prepare`` (include/daam_discover.h): ``src`` f32 [R, N] on the device with ``stride(1) == 1`` (rows
+    may be further apart than N) -> ``(P, L)``, f32 [R, N] each: the rows divided by their sums, and ``logf(max(P, 2^-120))``.  A row
+    whose sum is 0 or not finite gives ``P = 0``.  ``out``: the caller's own contiguous ``(P, L)`` to be overwritten."""
+    lib = nat.load_discover()
+    _check_discover('discover_prepare: src', src, torch.float32, 2)
+    rows, n = src.shape
+    if not (1 <= rows <= MAX_DISCOVER_ROWS and 1 <= n <= MAX_DISCOVER_CELLS):
+        raise ValueError(f'discover_prepare: src {tuple(src.shape)}: 1..{MAX_DISCOVER_ROWS} rows of 1..{MAX_DISCOVER_CELLS} cells')
+    if (n > 1 and src.stride(1) != 1) or (rows > 1 and src.stride(0) < n):
+        raise ValueError(f'discover_prepare: src strides {src.stride()}: cells contiguous, rows at least {n} apart')
+    p, l = out if out is not None else (torch.empty(rows, n, dtype=torch.float32, device=src.device) for _ in range(2))
+    for name, t in (('P', p), ('L', l)):
+        _check_discover(f'discover_prepare: {name}', t, torch.float32, 2, src)
+        if tuple(t.shape) != (rows, n) or not t.is_contiguous():
+            raise ValueError(f'discover_prepare: {name} {tuple(t.shape)}: contiguous [{rows}, {n}]')
+    with torch.cuda.device(src.device):
+        nat.check_discover(lib.daam_discover_prepare(src.data_ptr(), src.stride(0) if rows > 1 else n, rows, n, p.data_ptr(), l.data_ptr(),
+                                                     _stream_of(src.device)))
+    return p, l
+
+
+def discover_pair_kl(pa: torch.Tensor, la: torch.Tensor, pb: torch.Tensor, lb: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``daam_discover_pair_kl``: ``D[a][b] = 1/2 sum_j (pa[a][j] - pb[b][j]) (la[a][j] - lb[b][j])``, f32 [A, B], of contiguous f32
+    ``pa`` / ``la`` [A, N] and ``pb`` / ``lb`` [B, N] on the device (``discover_prepare`` gives such pairs)."""
+    lib = nat.load_discover()
+    for name, t in (('pa', pa), ('la', la), ('pb', pb), ('lb', lb)):
+        _check_discover(f'discover_pair_kl: {name}', t, torch.float32, 2, pa)
+        if not t.is_contiguous():
+            raise ValueError(f'discover_pair_kl: {name} must be contiguous')
+    (a, n), (b, nb) = pa.shape, pb.shape
+    if la.shape != pa.shape or lb.shape != pb.shape or nb != n:
+        raise ValueError(f'discover_pair_kl: pa {tuple(pa.shape)} / la {tuple(la.shape)} / pb {tuple(pb.shape)} / lb {tuple(lb.shape)}: [A, N], [A, N], [B, N], [B, N]')
+    if not (1 <= a <= MAX_DISCOVER_ROWS and 1 <= b <= MAX_DISCOVER_ROWS and 1 <= n <= MAX_DISCOVER_CELLS):
+        raise ValueError(f'discover_pair_kl: {a} x {b} rows of {n} cells: 1..{MAX_DISCOVER_ROWS} rows, 1..{MAX_DISCOVER_CELLS} cells')
+    d = out if out is not None else torch.empty(a, b, dtype=torch.float32, device=pa.device)
+    _check_discover('discover_pair_kl: out', d, torch.float32, 2, pa)
+    if tuple(d.shape) != (a, b) or not d.is_contiguous():
+        raise ValueError(f'discover_pair_kl: out {tuple(d.shape)}: contiguous [{a}, {b}]')
+    with torch.cuda.device(pa.device):
+        nat.check_discover(lib.daam_discover_pair_kl(pa.data_ptr(), la.data_ptr(), a, pb.data_ptr(), lb.data_ptr(), b, n, d.data_ptr(),
+                                                     _stream_of(pa.device)))
+    return d
+
+
+def discover_merge(p: torch.Tensor, member: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``daam_discover_merge``: ``p`` f32 [R, N] and ``member`` uint8 [K, R], contiguous on the device -> ``(out, cnt)``: f32 [K, N],
+    the mean of the rows ``r`` with ``member[k][r] != 0`` added in ascending ``r`` (zeros where there is none), and int32 [K], their
+    number."""
+    lib = nat.load_discover()
+    _check_discover('discover_merge: p', p, torch.float32, 2)
+    _check_discover('discover_merge: member', member, torch.uint8, 2, p)
+    (rows, n), k = p.shape, member.shape[0]
+    if member.shape[1] != rows or not p.is_contiguous() or not member.is_contiguous():
+        raise ValueError(f'discover_merge: p {tuple(p.shape)} / member {tuple(member.shape)}: contiguous [R, N] and [K, R]')
+    if not (1 <= rows <= MAX_DISCOVER_ROWS and 1 <= n <= MAX_DISCOVER_CELLS and 1 <= k <= MAX_DISCOVER_GROUPS):
+        raise ValueError(f'discover_merge: {rows} rows of {n} cells into {k} groups: 1..{MAX_DISCOVER_ROWS}, 1..{MAX_DISCOVER_CELLS}, 1..{MAX_DISCOVER_GROUPS}')
+    merged, cnt = out if out is not None else (torch.empty(k, n, dtype=torch.float32, device=p.device),
+                                               torch.empty(k, dtype=torch.int32, device=p.device))
+    _check_discover('discover_merge: out', merged, torch.float32, 2, p)
+    _check_discover('discover_merge: cnt', cnt, torch.int32, 1, p)
+    if tuple(merged.shape) != (k, n) or cnt.shape[0] != k or not merged.is_contiguous() or not cnt.is_contiguous():
+        raise ValueError(f'discover_merge: out {tuple(merged.shape)} / cnt {tuple(cnt.shape)}: contiguous [{k}, {n}] and [{k}]')
+    with torch.cuda.device(p.device):
+        nat.check_discover(lib.daam_discover_merge(p.data_ptr(), rows, n, member.data_ptr(), k, merged.data_ptr(), cnt.data_ptr(),
+                                                   _stream_of(p.device)))
+    return merged, cnt
+
+
+def discover_labels(props: torch.Tensor, out_h: int, out_w: int, values: bool = False):
+    """``daam_discover_labels``: ``props`` f32 [K, h, w], contiguous on the device -> uint8 [out_h, out_w], at every pixel the lowest
+    index among the largest bilinearly resized proposals (``F.interpolate(mode='bilinear', align_corners=False)``; a plain argmax when
+    the size is the grid's).  ``values=True``: ``(labels, f32 [out_h, out_w])`` with the winner's resized value."""
+    lib = nat.load_discover()
+    _check_discover('discover_labels: props', props, torch.float32, 3)
+    k, h, w = props.shape
+    out_h, out_w = int(out_h), int(out_w)
+    if not props.is_contiguous() or not (1 <= k <= MAX_DISCOVER_PROPOSALS and 1 <= h <= MAX_DISCOVER_GRID and 1 <= w <= MAX_DISCOVER_GRID):
+        raise ValueError(f'discover_labels: props {tuple(props.shape)}: contiguous, 1..{MAX_DISCOVER_PROPOSALS} proposals on a grid of 1..{MAX_DISCOVER_GRID} cells a side')
+    if not (1 <= out_h <= MAX_DISCOVER_OUT and 1 <= out_w <= MAX_DISCOVER_OUT):
+        raise ValueError(f'discover_labels: output {out_h} x {out_w}: 1..{MAX_DISCOVER_OUT} a side')
+    labels = torch.empty(out_h, out_w, dtype=torch.uint8, device=props.device)
+    vals = torch.empty(out_h, out_w, dtype=torch.float32, device=props.device) if values else None
+    with torch.cuda.device(props.device):
+        nat.check_discover(lib.daam_discover_labels(props.data_ptr(), k, h, w, out_h, out_w, labels.data_ptr(),
+                                                    vals.data_ptr() if values else None, _stream_of(props.device)))
+    return (labels, vals) if values else labels
+
+
 def _check_maps(maps: torch.Tensor) -> None:
     if maps.device.type != 'cuda':
         raise RuntimeError('daam_amd: heat maps must live on the HIP device (no CPU fallback)')

@@ -13,7 +13,7 @@ from . import engine as _engine
 from .utils import cached_nlp, compute_token_merge_indices
 
 __all__ = ['GlobalHeatMap', 'RawHeatMapCollection', 'WordHeatMap', 'ParsedHeatMap', 'SyntacticHeatMapPair', 'Segmentation',
-           'RegionAttribution', 'KeyScores', 'ThresholdSweep', 'Localization', 'SelfAffinity']
+           'RegionAttribution', 'KeyScores', 'ThresholdSweep', 'Localization', 'SelfAffinity', 'Discovery']
 
 RawHeatMapKey = Tuple[int, int, int]  # factor, layer, head
 
@@ -473,8 +473,146 @@ class SelfAffinity:
             raise ValueError(f'the affinity is of a grid of {self.grid[0]} x {self.grid[1]} cells, the maps are {got}')
         return _engine.affinity_propagate(self.sums, maps, iterations)
 
+    def discover(self, anchors=16, threshold: float = 1.1, iterations: int = 3, size=None) -> 'Discovery':
+        """Segments without a word list, in the DiffSeg manner (``libdaam_discover.so``): cells whose attention maps are
+        close in symmetric KL divergence are merged into proposals, proposals are merged again, and every pixel takes the proposal
+        that is largest there.
+
+        1. ``engine.discover_prepare`` turns ``sums`` into probability rows ``P`` and their logarithms.
+        2. ``anchors`` x ``anchors`` cells (a count per side, or a ``(rows, columns)`` pair; anchor ``(r, c)`` is the cell
+           ``floor((r + 1/2) h / rows), floor((c + 1/2) w / columns)``) are compared with every cell (``engine.discover_pair_kl``); an
+           anchor's proposal is the mean (``engine.discover_merge``) of the rows of the cells closer than ``threshold`` and of its own.
+        3. ``iterations - 1`` times: the proposals are prepared and compared with each other, the matrix goes to the host (the one
+           synchronisation of a round), ``discover_groups`` joins them greedily in list order, and the groups are merged.
+        4. ``engine.discover_labels`` resizes the proposals to ``size`` -- an image (its ``size`` is read as ``(W, H)``), an ``(H, W)``
+           pair, or ``None`` for the grid -- and labels every pixel.
+
+        ``ValueError`` for ``threshold <= 0``, ``iterations < 1``, an anchor count below 1 and more than 255 proposals left."""
+        threshold, iterations = float(threshold), int(iterations)
+        if not threshold > 0:
+            raise ValueError(f'threshold {threshold}: above 0')
+        if iterations < 1:
+            raise ValueError(f'iterations {iterations}: at least 1')
+        h, w = self.grid
+        cells = discover_anchors(self.grid, anchors)
+        if size is None:
+            out_h, out_w = h, w
+        elif hasattr(size, 'size') and not isinstance(size, torch.Tensor):
+            out_w, out_h = (int(v) for v in size.size)
+        else:
+            out_h, out_w = (int(v) for v in size)
+        if not (1 <= out_h <= _engine.MAX_DISCOVER_OUT and 1 <= out_w <= _engine.MAX_DISCOVER_OUT):
+            raise ValueError(f'size {out_h} x {out_w}: 1..{_engine.MAX_DISCOVER_OUT} a side')
+        if len(cells) > _engine.MAX_DISCOVER_GROUPS:
+            raise ValueError(f'{len(cells)} anchors: at most {_engine.MAX_DISCOVER_GROUPS}')
+        sums = self.sums if self.sums.dtype == torch.float32 else self.sums.float()
+        p, l = _engine.discover_prepare(sums)
+        idx = torch.as_tensor(cells, dtype=torch.int64, device=p.device)
+        d = _engine.discover_pair_kl(p[idx].contiguous(), l[idx].contiguous(), p, l)
+        member = (d < threshold).to(torch.uint8)
+        member[torch.arange(len(cells), device=p.device), idx] = 1            # an anchor always holds its own cell
+        props, _ = _engine.discover_merge(p, member)
+        for _ in range(iterations - 1):
+            pp, lp = _engine.discover_prepare(props)
+            groups = discover_groups(_engine.discover_pair_kl(pp, lp, pp, lp).cpu(), threshold)
+            if len(groups) > _engine.MAX_DISCOVER_GROUPS:
+                raise ValueError(f'{len(groups)} proposals are left: merging takes at most {_engine.MAX_DISCOVER_GROUPS}')
+            member = torch.zeros(len(groups), props.shape[0], dtype=torch.uint8)
+            for k, group in enumerate(groups):
+                member[k, group] = 1
+            props, _ = _engine.discover_merge(pp, member.to(p.device))
+        if props.shape[0] > _engine.MAX_DISCOVER_PROPOSALS:
+            raise ValueError(f'{props.shape[0]} proposals are left after {iterations} iterations: a label map orders at most '
+                             f'{_engine.MAX_DISCOVER_PROPOSALS}; raise iterations or the threshold, or lower anchors')
+        props = props.view(-1, h, w)
+        return Discovery(props, _engine.discover_labels(props, out_h, out_w))
+
     def cpu(self) -> 'SelfAffinity':
         return SelfAffinity(self.sums.cpu(), self.grid, self.slices, self.calls)
+
+
+def discover_anchors(grid: Tuple[int, int], anchors) -> List[int]:
+    """The cells ``y w + x`` of the anchors of ``SelfAffinity.discover`` on a grid of ``h x w``, row-major: ``anchors`` is a count per
+    side or a ``(rows, columns)`` pair, anchor ``(r, c)`` sits at ``floor((r + 1/2) h / rows)`` / ``floor((c + 1/2) w / columns)``,
+    clipped to the grid."""
+    h, w = int(grid[0]), int(grid[1])
+    rows, cols = (anchors, anchors) if isinstance(anchors, int) else (int(v) for v in anchors)
+    if rows < 1 or cols < 1:
+        raise ValueError(f'anchors {anchors!r}: at least one per side')
+    ys = [min(((2 * r + 1) * h) // (2 * rows), h - 1) for r in range(rows)]
+    xs = [min(((2 * c + 1) * w) // (2 * cols), w - 1) for c in range(cols)]
+    return [y * w + x for y in ys for x in xs]
+
+
+def discover_groups(d, threshold: float) -> List[List[int]]:
+    """The greedy pass of ``SelfAffinity.discover`` on the host: ``d`` [K, K] (a tensor or nested lists) is walked in list order; the
+    first unused proposal takes every unused one with ``d[first][other] < threshold`` into its group, and they are marked used."""
+    rows = d.tolist() if hasattr(d, 'tolist') else [list(r) for r in d]
+    used = [False] * len(rows)
+    groups = []
+    for i, row in enumerate(rows):
+        if used[i]:
+            continue
+        group = [i] + [j for j in range(len(rows)) if j != i and not used[j] and row[j] < threshold]
+        for j in group:
+            used[j] = True
+        groups.append(group)
+    return groups
+
+
+class Discovery:
+    """What ``SelfAffinity.discover`` found: ``proposals`` f32 [K, h, w], the merged attention maps, and ``labels`` uint8 [H, W], at
+    every pixel the proposal that is largest there.  ``n`` = K; a proposal that wins no pixel has an area of 0."""
+
+    def __init__(self, proposals: torch.Tensor, labels: torch.Tensor):
+        self.proposals, self.labels = proposals, labels
+        self.n = int(proposals.shape[0])
+        self._masks: Optional[torch.Tensor] = None
+
+    @property
+    def areas(self) -> torch.Tensor:
+        """int64 [K]: the pixels of every segment."""
+        return torch.bincount(self.labels.reshape(-1).long(), minlength=self.n)
+
+    @property
+    def masks(self) -> torch.Tensor:
+        """uint8 [K, H, W], built on the first use: ``masks[k] = labels == k``; they sum to 1 at every pixel."""
+        if self._masks is None:
+            ks = torch.arange(self.n, device=self.labels.device, dtype=self.labels.dtype)
+            self._masks = (self.labels[None] == ks[:, None, None]).to(torch.uint8)
+        return self._masks
+
+    def mask(self, k: int) -> torch.Tensor:
+        if not 0 <= int(k) < self.n:
+            raise ValueError(f'segment {k}: 0..{self.n - 1}')
+        return self.masks[int(k)]
+
+    def _owners(self, ghm: 'GlobalHeatMap', words) -> List[Optional[int]]:
+        """Per segment the index of the word of ``words`` that puts most attention inside it; ``None`` for a segment without a pixel
+        or without any attention."""
+        if not words:
+            raise ValueError('names needs at least one word')
+        values, indices = ghm.attribute(self.masks).top_words(words)
+        values, indices, areas = values[:, 0].tolist(), indices[:, 0].tolist(), self.areas.tolist()
+        return [i if a > 0 and v > 0 else None for v, i, a in zip(values, indices, areas)]
+
+    def names(self, ghm: 'GlobalHeatMap', words: Sequence[Union[str, Tuple[str, Optional[int]]]]) -> List[Optional[str]]:
+        """One word of ``words``, or ``None``, per segment: ``ghm.attribute(masks).top_words(words)``."""
+        names = [w if isinstance(w, str) else w[0] for w in words]
+        return [None if i is None else names[i] for i in self._owners(ghm, words)]
+
+    def word_masks(self, ghm: 'GlobalHeatMap', words: Sequence[Union[str, Tuple[str, Optional[int]]]]) -> torch.Tensor:
+        """uint8 [len(words), H, W]: the union of the segments each word owns -- the shape ``evaluate.mask_overlap_matrix``,
+        ``evaluate.mask_components`` and ``Segmentation.iou`` take."""
+        owners = self._owners(ghm, words)
+        table = torch.zeros(len(words), self.n, dtype=torch.uint8)
+        for k, i in enumerate(owners):
+            if i is not None:
+                table[i, k] = 1
+        return table.to(self.labels.device)[:, self.labels.long()]
+
+    def cpu(self) -> 'Discovery':
+        return Discovery(self.proposals.cpu(), self.labels.cpu())
 
 
 class GlobalHeatMap:
