@@ -291,6 +291,20 @@ DISCOVER_LIBRARY = Library('libdaam_discover.so', 'DAAM_DISCOVER_LIB', 'SelfAffi
     'daam_discover_last_error': _sig(None, c_char_p),
 })
 
+# ---- libdaam_jointattend.so (C ABI: include/daam_joint_attend.h): the joint attention itself, statistics as a by-product -------------
+# Beside LIBRARIES like JOINT_LIBRARY: `build.build_joint_attend` makes the file.
+JOINT_ATTEND_LIBRARY = Library('libdaam_jointattend.so', 'DAAM_JOINT_ATTEND_LIB', 'trace_joint(attend=True)', 1,
+                               'daam_joint_attend_abi_version', 'daam_joint_attend_last_error', {
+    'daam_joint_attend_forward': _sig([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_float,
+                                       c_void_p, c_size_t, c_void_p]),
+    'daam_joint_attend_text': _sig([c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64,
+                                    c_int64, c_int64, c_int64, c_int64, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
+    'daam_joint_attend_stats_bytes': _sig([c_int, c_int, c_int], c_size_t),
+    'daam_joint_attend_abi_version': _sig(None),
+    'daam_joint_attend_last_error': _sig(None, c_char_p),
+})
+
 # The names the engine, the tools and the tests use: one line per library, all of it read off the record.
 LIB_NAME, LIB_PATH, ABI_VERSION, EXPORTS = MAIN.file, MAIN.path, MAIN.abi_version, MAIN.exports
 ANALYSIS_LIB_NAME, ANALYSIS_LIB_PATH, ANALYSIS_ABI_VERSION, ANALYSIS_EXPORTS = ANALYSIS.file, ANALYSIS.path, ANALYSIS.abi_version, ANALYSIS.exports
@@ -317,6 +331,9 @@ load_joint_affinity, check_joint_affinity = _bind(JOINT_AFFINITY_LIBRARY, 'load_
 DISCOVER_LIB_NAME, DISCOVER_LIB_PATH, DISCOVER_ABI_VERSION, DISCOVER_EXPORTS = \
     DISCOVER_LIBRARY.file, DISCOVER_LIBRARY.path, DISCOVER_LIBRARY.abi_version, DISCOVER_LIBRARY.exports
 load_discover, check_discover = _bind(DISCOVER_LIBRARY, 'load_discover')
+JOINT_ATTEND_LIB_NAME, JOINT_ATTEND_LIB_PATH, JOINT_ATTEND_ABI_VERSION, JOINT_ATTEND_EXPORTS = \
+    JOINT_ATTEND_LIBRARY.file, JOINT_ATTEND_LIBRARY.path, JOINT_ATTEND_LIBRARY.abi_version, JOINT_ATTEND_LIBRARY.exports
+load_joint_attend, check_joint_attend = _bind(JOINT_ATTEND_LIBRARY, 'load_joint_attend')
 
 __all__ = ['load', 'check', 'DaamError', 'QKDesc', 'AttendDesc', 'DAAM_F16', 'DAAM_F32', 'DAAM_BF16', 'EXPORTS', 'LIB_PATH',
            'byref', 'c_void_p', 'c_int', 'c_uint8', 'c_int32', 'c_size_t', 'E_NOMAPS']

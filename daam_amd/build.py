@@ -200,6 +200,15 @@ DISCOVER = SideLibrary('discover', ['daam_discover.hip'], [_api('daam_hip.h'), _
 DISCOVER_SOURCES, DISCOVER_HEADERS, DISCOVER_LIB = DISCOVER[1:]
 discover_stale, build_discover = partial(side_stale, DISCOVER), partial(build_side, DISCOVER)
 
+# libdaam_jointattend.so (include/daam_joint_attend.h): the joint attention of an MMDiT block itself -- softmax(Q K^T) V for image and
+# text queries with the image rows' statistics as a by-product of the key walk -- and the text columns from those statistics
+# (`trace_joint(attend=True)`).  It reads no header of csrc/ and restates the device helpers it shares with the joint tap,
+# as JOINT_AFFINITY does.  Like JOINT, ROPE, JOINT_AFFINITY and DISCOVER it stands beside SIDE_LIBRARIES and is made after them.
+JOINT_ATTEND = SideLibrary('jointattend', ['daam_joint_attend.hip'], [_api('daam_hip.h'), _api('daam_joint_attend.h')],
+                           os.path.join(HERE, 'libdaam_jointattend.so'))
+JOINT_ATTEND_SOURCES, JOINT_ATTEND_HEADERS, JOINT_ATTEND_LIB = JOINT_ATTEND[1:]
+joint_attend_stale, build_joint_attend = partial(side_stale, JOINT_ATTEND), partial(build_side, JOINT_ATTEND)
+
 
 def fastpath_out() -> str:
     import sysconfig
@@ -281,5 +290,6 @@ if __name__ == '__main__':
     build_joint(force='--force' in sys.argv)
     build_rope(force='--force' in sys.argv)
     build_joint_affinity(force='--force' in sys.argv)
+    build_joint_attend(force='--force' in sys.argv)
     build_discover(force='--force' in sys.argv)
     print(OUT)

@@ -1787,7 +1787,8 @@ class JointTapState:
         if not 1 <= self.tokens <= MAX_JOINT_TOKENS:
             raise ValueError(f'{tokens} text tokens: the joint tap takes 1..{MAX_JOINT_TOKENS}')
         self.sums: Optional[torch.Tensor] = None
-        self._ws: Optional[torch.Tensor] = None
+        self._ws: Optional[torch.Tensor] = None           # this state's own workspace: what `tap` has the library write
+        self._stats: Optional[torch.Tensor] = None        # the statistics of the last tapped call: `_ws`, or a view that was given
         self.heads = 0
         self.calls = 0
         self.slices = 0
@@ -1796,37 +1797,46 @@ class JointTapState:
         """A new generation: the next tapped call overwrites the sums."""
         self.calls = self.slices = 0
 
-    def tap(self, q: torch.Tensor, k_txt: torch.Tensor, k_img: torch.Tensor, heads: int, scale: float, weight: float = 1.0) -> None:
-        """``q`` / ``k_txt`` / ``k_img``: what the projections (and their norms) gave, fp16 or bf16 ``[batch, rows, heads * d]`` on the
-        device with ``rows`` = cells / tokens / image keys, read in place through their strides."""
-        lib = nat.load_joint()
-        _check_on_device(q, k_txt)
-        _check_on_device(q, k_img)
-        if q.dtype not in (torch.float16, torch.bfloat16) or k_txt.dtype != q.dtype or k_img.dtype != q.dtype:
-            raise RuntimeError(f'daam_amd: the joint tap reads fp16 or bf16 Q and K, got {q.dtype} / {k_txt.dtype} / {k_img.dtype}')
-        if (q.dim() != 3 or k_txt.dim() != 3 or k_img.dim() != 3 or q.shape[1] != self.cells or k_txt.shape[1] != self.tokens
-                or not k_txt.shape[0] == k_img.shape[0] == q.shape[0] or not k_txt.shape[2] == k_img.shape[2] == q.shape[2]
-                or q.shape[2] % heads or k_img.shape[1] > MAX_JOINT_CELLS):
-            raise ValueError(f'joint tap: Q {tuple(q.shape)} / text K {tuple(k_txt.shape)} / image K {tuple(k_img.shape)} on a grid of '
-                             f'{self.cells} cells with {self.tokens} tokens, {heads} heads')
-        batch, cells, channels = q.shape
-        d = channels // heads
+    def _checked(self, q, k_txt, k_img, heads: int):
+        """What ``tap`` and ``tap_from_stats`` (``k_img`` None) hold their tensors to: ``(tensors with a unit last stride, batch, d)``."""
+        given = [t for t in (q, k_txt, k_img) if t is not None]
+        for t in given[1:]:
+            _check_on_device(q, t)
+        if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for t in given):
+            raise RuntimeError(f'daam_amd: the joint tap reads fp16 or bf16 Q and K, got {" / ".join(str(t.dtype) for t in given)}')
+        if (any(t.dim() != 3 for t in given) or q.shape[1] != self.cells or k_txt.shape[1] != self.tokens
+                or any(t.shape[0] != q.shape[0] or t.shape[2] != q.shape[2] for t in given) or q.shape[2] % heads
+                or (k_img is not None and k_img.shape[1] > MAX_JOINT_CELLS)):
+            shapes = ' / '.join(f'{name} {tuple(t.shape)}' for name, t in zip(('Q', 'text K', 'image K'), given))
+            raise ValueError(f'joint tap: {shapes} on a grid of {self.cells} cells with {self.tokens} tokens, {heads} heads')
+        d = q.shape[2] // heads
         if d not in JOINT_HEAD_DIMS:
             raise ValueError(f'joint tap: head dim {d}: one of {JOINT_HEAD_DIMS}')
         if self.per_head and self.sums is not None and self.calls and heads != self.heads:
             raise ValueError(f'joint tap: {heads} heads after calls with {self.heads}: per-head planes need one head count')
-        q, k_txt, k_img = (t if t.stride(2) == 1 else t.contiguous() for t in (q, k_txt, k_img))
+        return [t if t.stride(2) == 1 else t.contiguous() for t in given], q.shape[0], d
+
+    def _sums_on(self, dev, heads: int) -> None:
+        """The sums of this call: allocated anew (and the counts reset) where there are none on ``dev`` in this call's shape."""
+        shape = (heads, self.tokens, self.cells) if self.per_head else (self.tokens, self.cells)
+        if self.sums is None or self.sums.device != dev or self.sums.shape != shape:
+            self.sums = torch.empty(shape, dtype=torch.float32, device=dev)
+            self.calls = self.slices = 0
+        self.heads = heads
+
+    def tap(self, q: torch.Tensor, k_txt: torch.Tensor, k_img: torch.Tensor, heads: int, scale: float, weight: float = 1.0) -> None:
+        """``q`` / ``k_txt`` / ``k_img``: what the projections (and their norms) gave, fp16 or bf16 ``[batch, rows, heads * d]`` on the
+        device with ``rows`` = cells / tokens / image keys, read in place through their strides."""
+        lib = nat.load_joint()
+        (q, k_txt, k_img), batch, d = self._checked(q, k_txt, k_img, heads)
+        cells = self.cells
         need = lib.daam_joint_tap_workspace(batch, heads, cells)
         if not need:
             raise ValueError(f'joint tap: batch {batch} x {heads} heads: at most {MAX_JOINT_SLICES} slices')
         dev = q.device
-        shape = (heads, self.tokens, cells) if self.per_head else (self.tokens, cells)
-        if self.sums is None or self.sums.device != dev or self.sums.shape != shape:
-            self.sums = torch.empty(shape, dtype=torch.float32, device=dev)
-            self.calls = self.slices = 0
+        self._sums_on(dev, heads)
         if self._ws is None or self._ws.device != dev or self._ws.numel() * 8 < need:
             self._ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
-        self.heads = heads
         with torch.cuda.device(dev):
             nat.check_joint(lib.daam_joint_tap_accumulate(
                 q.data_ptr(), k_txt.data_ptr(), k_img.data_ptr() if k_img.shape[1] else None, _DTYPE_CODE[q.dtype], batch, heads, cells,
@@ -1834,14 +1844,43 @@ class JointTapState:
                 k_img.stride(1), float(scale), float(weight), int(self.calls > 0), self.sums.data_ptr(),
                 self.tokens * cells if self.per_head else 0, self._ws.data_ptr(), self._ws.numel() * 8,
                 torch.cuda.current_stream(dev).cuda_stream))
+        self._stats = self._ws
+        self.calls += 1
+        self.slices += batch * heads
+
+    def tap_from_stats(self, q: torch.Tensor, k_txt: torch.Tensor, heads: int, scale: float, stats: torch.Tensor, weight: float = 1.0) -> None:
+        """The text columns from statistics that are there already (``daam_joint_attend_text``, include/daam_joint_attend.h): ``q`` /
+        ``k_txt`` as ``tap`` takes them (and holds them to: the same checks, the same errors), ``stats`` a view of
+        ``JointAttendState.forward``'s statistics that begins at the first slice of ``q``'s first batch entry.  Allocation, bookkeeping
+        and the first-call-overwrites rule are those of ``tap``; ``self.stats`` becomes ``stats``, so that the affinity reads the same
+        thing.  The view is only read and is never taken for this state's own workspace."""
+        lib = _load_joint_attend()
+        (q, k_txt), batch, d = self._checked(q, k_txt, None, heads)
+        cells = self.cells
+        need = lib.daam_joint_attend_stats_bytes(batch, heads, cells)
+        if not need:
+            raise ValueError(f'joint tap: batch {batch} x {heads} heads: at most {MAX_JOINT_SLICES} slices')
+        if stats is None or stats.device != q.device or stats.numel() * stats.element_size() < need:
+            raise ValueError(f'joint tap: the statistics of {batch * heads} slices of {cells} rows take {need} bytes on the device of Q: '
+                             f'pass the statistics JointAttendState.forward returned, offset to the first batch entry of Q')
+        dev = q.device
+        self._sums_on(dev, heads)
+        with torch.cuda.device(dev):
+            nat.check_joint_attend(lib.daam_joint_attend_text(
+                q.data_ptr(), k_txt.data_ptr(), stats.data_ptr(), stats.numel() * stats.element_size(), _DTYPE_CODE[q.dtype], batch, heads,
+                cells, self.tokens, d, q.stride(0), d, q.stride(1), k_txt.stride(0), d, k_txt.stride(1), float(scale), float(weight),
+                int(self.calls > 0), self.sums.data_ptr(), self.tokens * cells if self.per_head else 0,
+                torch.cuda.current_stream(dev).cuda_stream))
+        self._stats = stats
         self.calls += 1
         self.slices += batch * heads
 
     @property
     def stats(self) -> Optional[torch.Tensor]:
-        """The workspace of the last ``tap``, read-only to callers: per slice and query row the ``float2`` ``(-(m c), 1 / l)`` of the
-        joint softmax, slices ``pad128(cells)`` rows apart (the layout include/daam_joint_affinity.h states).  ``None`` before a tap."""
-        return self._ws
+        """The statistics of the last tapped call, read-only to callers: the workspace ``tap`` wrote, or the view ``tap_from_stats`` was
+        given.  Per slice and query row the ``float2`` ``(-(m c), 1 / l)`` of the joint softmax, slices ``pad128(cells)`` rows apart
+        (the layout include/daam_joint_affinity.h states).  ``None`` before a tap."""
+        return self._stats
 
 
 JOINT_TAP_STATS_ABI = 1                             # the daam_joint_tap ABI whose workspace layout daam_joint_affinity.h reads
@@ -1916,6 +1955,74 @@ class JointAffinityState:
                 int(self.calls > 0), self.sums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         self.calls += 1
         self.slices += batch * heads
+
+
+JOINT_ATTEND_ABI = 1                                # include/daam_joint_attend.h
+
+
+def _load_joint_attend():
+    """``nat.load_joint_attend()``, held to the ABI this module's calls are written for."""
+    lib = nat.load_joint_attend()
+    abi = lib.daam_joint_attend_abi_version()
+    if abi != JOINT_ATTEND_ABI:
+        raise RuntimeError(f'daam_amd: libdaam_jointattend.so reports ABI {abi}, this module calls ABI {JOINT_ATTEND_ABI}; rebuild')
+    return lib
+
+
+def pad128(rows: int) -> int:
+    """Rows of a slice's statistics (include/daam_joint_affinity.h)."""
+    return -(-int(rows) // 128) * 128
+
+
+class JointAttendState:
+    """The joint attention of an MMDiT block computed by the library (include/daam_joint_attend.h): softmax(Q K^T) V for
+    the image and the text queries over text and image keys, with the image rows' softmax statistics left behind by the same walk.
+    It holds the statistics buffer between calls and nothing else; the library is loaded by the first ``forward``."""
+
+    def __init__(self):
+        self._stats: Optional[torch.Tensor] = None
+        self.calls = 0
+
+    def forward(self, q_img: torch.Tensor, k_img: torch.Tensor, v_img: torch.Tensor, q_txt: torch.Tensor, k_txt: torch.Tensor,
+                v_txt: torch.Tensor, heads: int, scale: float):
+        """Six fp16 or bf16 ``[B, rows, heads * d]`` tensors as the projections (and their norms) gave them, ``rows`` = P for the
+        image three and T for the text three, read in place through their strides.  Returns ``(out_img [B, P, heads d],
+        out_txt [B, T, heads d], stats)``; ``stats`` is an int64 view of ``B * heads * pad128(P)`` ``float2`` pairs, overwritten by
+        the next ``forward``."""
+        lib = _load_joint_attend()
+        img, txt = (q_img, k_img, v_img), (q_txt, k_txt, v_txt)
+        for t in img + txt:
+            _check_on_device(q_img, t)
+        if q_img.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q_img.dtype for t in img + txt):
+            raise ValueError(f'joint attend: fp16 or bf16 Q, K and V of one dtype, got {[str(t.dtype) for t in img + txt]}')
+        if (any(t.dim() != 3 for t in img + txt) or any(t.shape != q_img.shape for t in img) or any(t.shape != q_txt.shape for t in txt)
+                or q_txt.shape[0] != q_img.shape[0] or q_txt.shape[2] != q_img.shape[2] or q_img.shape[2] % heads
+                or not 1 <= q_img.shape[1] <= MAX_JOINT_CELLS or not 1 <= q_txt.shape[1] <= MAX_JOINT_TOKENS):
+            raise ValueError(f'joint attend: image Q / K / V {[tuple(t.shape) for t in img]}, text Q / K / V {[tuple(t.shape) for t in txt]}, '
+                             f'{heads} heads: [B, 1..{MAX_JOINT_CELLS}, heads d] and [B, 1..{MAX_JOINT_TOKENS}, heads d]')
+        batch, cells, channels = q_img.shape
+        tokens = q_txt.shape[1]
+        d = channels // heads
+        if d not in JOINT_HEAD_DIMS:
+            raise ValueError(f'joint attend: head dim {d}: one of {JOINT_HEAD_DIMS}')
+        need = lib.daam_joint_attend_stats_bytes(batch, heads, cells)
+        if not need:
+            raise ValueError(f'joint attend: batch {batch} x {heads} heads: at most {MAX_JOINT_SLICES} slices')
+        img = tuple(t if t.stride(2) == 1 else t.contiguous() for t in img)
+        txt = tuple(t if t.stride(2) == 1 else t.contiguous() for t in txt)
+        dev = q_img.device
+        out_img = torch.empty(batch, cells, channels, dtype=q_img.dtype, device=dev)
+        out_txt = torch.empty(batch, tokens, channels, dtype=q_img.dtype, device=dev)
+        if self._stats is None or self._stats.device != dev or self._stats.numel() * 8 != need:
+            self._stats = torch.empty(need // 8, dtype=torch.int64, device=dev)
+        strides = lambda ts: (ctypes.c_int64 * (3 * len(ts)))(*[v for t in ts for v in (t.stride(0), d, t.stride(1))])
+        with torch.cuda.device(dev):
+            nat.check_joint_attend(lib.daam_joint_attend_forward(
+                *[t.data_ptr() for t in img + txt], out_img.data_ptr(), out_txt.data_ptr(), _DTYPE_CODE[q_img.dtype], batch, heads, cells,
+                tokens, d, strides(img), strides(txt), strides((out_img, out_txt)), float(scale), self._stats.data_ptr(), need,
+                torch.cuda.current_stream(dev).cuda_stream))
+        self.calls += 1
+        return out_img, out_txt, self._stats
 
 
 MAX_ROPE_JOBS, MAX_ROPE_ROWS, MAX_ROPE_SLICES = 4, 16896, 4096                 # include/daam_rope.h

@@ -76,10 +76,20 @@ class JointHeatMapHooker(AggregateHooker):
     ``compute_self_affinity()`` returns it as a ``SelfAffinity``, and ``compute_global_heat_map().propagate(aff, n)`` applies as on a
     UNet trace.  One thing differs from the UNet: a row sums to ``slices`` MINUS the mass the cell gave to the text keys
     (``matrix()``, ``of()`` and ``propagate()`` divide by the row sum, so they hold as they are).  Without the option nothing of it is
-    loaded or allocated."""
+    loaded or allocated.
+
+    ``attend=True``: a tappable call whose module also has ``add_q_proj``, ``add_v_proj`` and ``to_v`` is COMPUTED by
+    the hooker: Q, K and V are projected once for the whole batch, ``daam_joint_attend_forward`` gives the attention output of the
+    image and the text rows and leaves the image rows' softmax statistics behind, and the text columns (and, with
+    ``self_affinity=True``, the image columns) of the kept half are formed from those statistics: the attention is computed once
+    instead of twice.  This REPLACES the block's processor with the SD3 protocol of diffusers' ``JointAttnProcessor2_0`` for those
+    calls: a pipeline with a custom processor (IP-adapter and the like) should not use it, and the generation is no longer
+    bit-identical to the untraced one -- it is the same attention with the softmax in f32.  Every other call (a mask, no context,
+    another length, a missing projection) goes to the original processor, with the tap beside it where the predicate above holds.
+    Without the option nothing of it is loaded, located or allocated."""
 
     def __init__(self, pipeline, per_head: bool = False, height: Optional[int] = None, width: Optional[int] = None,
-                 self_affinity: bool = False):
+                 self_affinity: bool = False, attend: bool = False):
         transformer = getattr(pipeline, 'transformer', None)
         if transformer is None or not hasattr(transformer, 'transformer_blocks'):
             raise ValueError('trace_joint needs a pipeline with a `transformer` of joint-attention blocks (SD3 class); '
@@ -105,6 +115,7 @@ class JointHeatMapHooker(AggregateHooker):
                 raise ValueError(f'trace_joint: head dim {_head_dim(attn)}: one of {_engine.JOINT_HEAD_DIMS}')
         self.state: Optional[_engine.JointTapState] = None      # made by the first tapped call, which knows the context length
         self.affinity = _engine.JointAffinityState(*self.grid) if self_affinity else None
+        self.attend = _engine.JointAttendState() if attend else None
         self.last_prompt: str = ''
         super().__init__([_JointPipelineHooker(pipeline, self)] + [JointAttentionHooker(attn, self) for attn in located])
 
@@ -122,6 +133,18 @@ class JointHeatMapHooker(AggregateHooker):
         self.state.tap(q, k_txt, k_img, heads, scale)
         if self.affinity is not None:
             self.affinity.tap(q, k_img, heads, scale, self.state.stats)
+
+    def _attend(self, q_img, k_img, v_img, q_txt, k_txt, v_txt, heads: int, scale: float):
+        """The fused route of a tappable call: the attention of the whole batch, then the planes of the kept half from its statistics."""
+        out_img, out_txt, stats = self.attend.forward(q_img, k_img, v_img, q_txt, k_txt, v_txt, heads, scale)
+        first = q_img.shape[0] // 2
+        kept = stats[first * heads * _engine.pad128(self.cells):]
+        if self.state is None or self.state.tokens != k_txt.shape[1]:
+            self.state = _engine.JointTapState(self.grid[0], self.grid[1], k_txt.shape[1], self.per_head)
+        self.state.tap_from_stats(q_img[first:], k_txt[first:], heads, scale, kept)
+        if self.affinity is not None:
+            self.affinity.tap(q_img[first:], k_img[first:], heads, scale, kept)
+        return out_img, out_txt
 
     # -- results ---------------------------------------------------------------------------------------------------------------------
     def _sums(self) -> torch.Tensor:
@@ -173,9 +196,12 @@ class _JointPipelineHooker(ObjectHooker):
 
 
 class JointAttentionHooker(ObjectHooker):
-    """The processor installed on every located ``attn``.  The model's output is what the ORIGINAL processor returns for the original
-    arguments, so the traced generation is bit-identical to the untraced one.  Beside it, under ``no_grad``, a call with
-    ``encoder_hidden_states``, no attention mask and a query length equal to the grid's cell count is tapped (module docstring)."""
+    """The processor installed on every located ``attn``.  Without ``attend=True`` the model's output is what the ORIGINAL processor
+    returns for the original arguments, so the traced generation is bit-identical to the untraced one; beside it, under ``no_grad``, a
+    call with ``encoder_hidden_states``, no attention mask and a query length equal to the grid's cell count is tapped (module
+    docstring).  With ``attend=True`` such a call on a module that has ``add_q_proj``, ``add_v_proj`` and ``to_v`` does NOT reach the
+    original processor: ``_attend`` computes it by the SD3 protocol with the attention from ``daam_joint_attend_forward``, and the
+    generation is the same attention with the softmax in f32, no longer bit-identical (``JointHeatMapHooker``)."""
 
     def __init__(self, module, parent: JointHeatMapHooker):
         super().__init__(module)
@@ -196,11 +222,31 @@ class JointAttentionHooker(ObjectHooker):
             y = norm(y.view(batch, rows, heads, channels // heads)).reshape(batch, rows, channels)
         return y
 
+    def _attend(self, attn, hidden_states, context):
+        """``JointAttnProcessor2_0``'s protocol with the attention itself from ``daam_joint_attend_forward``: every projection once."""
+        heads = attn.heads
+        q_img = self._project(attn.to_q, getattr(attn, 'norm_q', None), hidden_states, heads)
+        k_img = self._project(attn.to_k, getattr(attn, 'norm_k', None), hidden_states, heads)
+        v_img = attn.to_v(hidden_states)
+        q_txt = self._project(attn.add_q_proj, getattr(attn, 'norm_added_q', None), context, heads)
+        k_txt = self._project(attn.add_k_proj, getattr(attn, 'norm_added_k', None), context, heads)
+        v_txt = attn.add_v_proj(context)
+        out_img, out_txt = self.parent._attend(q_img, k_img, v_img, q_txt, k_txt, v_txt, heads, attn.scale)
+        out_img = attn.to_out[1](attn.to_out[0](out_img))
+        if not getattr(attn, 'context_pre_only', False) and getattr(attn, 'to_add_out', None) is not None:
+            out_txt = attn.to_add_out(out_txt)
+        return out_img, out_txt
+
     def __call__(self, attn, hidden_states, *args, **kwargs):
-        out = self.original_processor(attn, hidden_states, *args, **kwargs)
         context = kwargs.get('encoder_hidden_states', args[0] if args else None)
         mask = kwargs.get('attention_mask', args[1] if len(args) > 1 else None)
-        if context is not None and mask is None and hidden_states.dim() == 3 and hidden_states.shape[1] == self.parent.cells:
+        tappable = context is not None and mask is None and hidden_states.dim() == 3 and hidden_states.shape[1] == self.parent.cells
+        if (tappable and self.parent.attend is not None
+                and all(getattr(attn, name, None) is not None for name in ('add_q_proj', 'add_v_proj', 'to_v'))):
+            with torch.no_grad():
+                return self._attend(attn, hidden_states, context)
+        out = self.original_processor(attn, hidden_states, *args, **kwargs)
+        if tappable:
             with torch.no_grad():
                 first = hidden_states.shape[0] // 2
                 kept, ctx = hidden_states[first:], context[first:]
